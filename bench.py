@@ -18,8 +18,9 @@ advanced by one take_step.
           RCCL send/recv each Heun stage ("scaling": "strong": total work fixed).
           The base of that strong-scaling curve is NOT the N = 1 line (a 1 M-cell
           system: 1.5e9 c-u/s) but the same 10 M-cell system on one GPU (1.9e9):
-          rank 0 measures it on its own GPU after the timed region and the line
-          carries it as `one_gpu_same_system` with `speedup_vs_one_gpu_same_system`.
+          with --full, rank 0 measures it on its own GPU after the timed region and
+          the line carries it as `one_gpu_same_system` with
+          `speedup_vs_one_gpu_same_system`.
           Started either by torch.distributed.run (RANK / WORLD_SIZE in the
           environment) or by this script itself: without WORLD_SIZE it starts the
           N rank processes (before anything touches a GPU) and relays rank 0's line.
@@ -28,6 +29,11 @@ Inputs are resident in HBM before the timed region; nothing inside it touches th
 host except take_step's own 4-byte read of n (and, on the slab path, one 8-byte
 read of the two ghost counts per step).  Prints ONE JSON line on rank 0 (see
 DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps, writes the last step's output
+if --dump-outputs DIR is given, and prints the line.  Everything else it can
+measure (the force kernel's events pass, tail_ab, the sustained and fast-tier
+lines, the CPU baseline, the one-GPU base of N > 1) runs only with --full.
 """
 import argparse
 import hashlib
@@ -123,17 +129,24 @@ def gather_model_bytes_per_cell_update(n_floats, dist):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; 3000 with --sustained)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures: the force kernel's "
+                         "events pass (roofline achieved / avg_launch_us) and its --sum-order 1 A/B (tail_ab), the "
+                         "sustained and fast-tier lines, the CPU baseline, and for N > 1 the same system on one GPU")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the cells' positions) as "
+                         "DIR/<name>.npy; outputs over 64 MB are cut to a fixed, seeded sample of rows")
     ap.add_argument("--cells-total", type=int, default=0,
                     help="cells of the whole system (default: 1 M on one GPU, 10 M on several)")
     ap.add_argument("--cells", type=int, default=0, help="same as --cells-total (kept for scripts)")
     ap.add_argument("--grid-size", type=int, default=0, help="0 = smallest that fits")
     ap.add_argument("--dist", type=float, default=0.5, help="random_sphere spacing")
     ap.add_argument("--cpu-steps", type=int, default=4, help="oracle steps for cpu_baseline (4 steps of 1 M cells: ~12 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-one-gpu-reference", action="store_true",
-                    help="N > 1: skip rank 0's untimed run of the same whole system on one GPU "
+                    help="--full, N > 1: skip rank 0's untimed run of the same whole system on one GPU "
                          "(the base of the strong-scaling curve)")
     ap.add_argument("--model", default="springs_grid",
                     help="named model of the harness (default: the headline springs_grid)")
@@ -158,7 +171,7 @@ def parse(argv=None):
                          "system (never on the system that is timed), so that the timed region does not start on an "
                          "idle GPU's clock ramp; 0 = none.  Reported as preheat_ms")
     ap.add_argument("--no-tail-ab-line", action="store_true",
-                    help="headline run: skip the extra untimed pass with --sum-order 1 (reported as tail_ab)")
+                    help="--full headline run: skip the extra untimed pass with --sum-order 1 (reported as tail_ab)")
     ap.add_argument("--force-variant", type=int, default=-1,
                     help="-1 = the engine's choice (default: grid_force_bits, or grid_force_coop below ~1.5e5 cells "
                          "when the model declared its functors stateless), 2 = grid_force_bits always, "
@@ -192,19 +205,21 @@ def parse(argv=None):
                          "builds, reductions, updates: all the work, none of the drift of the clumping springs system), "
                          "with the shader clock sampled beside it (ya_shader_clock_mhz) so that throttling shows")
     ap.add_argument("--no-sustained-line", action="store_true",
-                    help="headline run: skip the extra pass, outside the timed region, of --sustained-steps take_steps "
+                    help="--full headline run: skip the extra pass, outside the timed region, of --sustained-steps take_steps "
                          "with dt = 0 (reported as `sustained` beside the headline value)")
     ap.add_argument("--sustained-steps", type=int, default=3000)
     ap.add_argument("--no-fast-tier-line", action="store_true",
-                    help="headline run: skip the extra, untimed-by-the-contract pass on the fast-arithmetic build "
+                    help="--full headline run: skip the extra, untimed-by-the-contract pass on the fast-arithmetic build "
                          "(reported as fast_arith_tier beside the headline value)")
     ap.add_argument("--graph", type=int, default=0,
                     help="Heun_solver::graph_steps: 1 = replay the step as a hipGraph, -1 = below 400 k "
                          "cells only, 0 = plain launches (default)")
     args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = 3000 if args.sustained else 20
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.sustained:
-        if args.steps == 20:
-            args.steps = 3000
         if args.dt is None:
             args.dt = 0.0
     if args.model not in MODELS:
@@ -269,6 +284,46 @@ def measured_counters(kernel_key):
     return out, head
 
 
+# The springs systems started from random_sphere contract into clumps (profiles/r04_springs_drift.json: 40 pairs
+# inside the cut-off per cell at the start, 381 after 103 steps, 1211 after 203) and soon after that throw a cell
+# out of any grid, which the engine reports as the reference does: it aborts.  Their runs therefore take every
+# step as one of the first RESTART_EVERY steps from the seeded initial state, restarted from it once they have
+# taken that many (warm-up steps included), so that any --steps times the same workload.  A run of W + K <=
+# RESTART_EVERY steps is exactly the run from random_sphere it always was.
+RESTART_EVERY = 100
+RESTART_MODELS = ("springs_grid", "springs_links_grid", "springs_tile")
+
+
+class Restarting:
+    """take_step(dt, k) on `sim`, restarted from the state it has now (its initial state) after every `every`
+    steps (0 = never).  A restart puts back the points, n and old_v (copy_to_device, set_old_v); its time is
+    added up in `seconds`, which timed regions leave out."""
+
+    def __init__(self, sim, every):
+        self.sim, self.every, self.done, self.seconds = sim, every, 0, 0.0
+        if every:
+            self.n0 = sim.h_n
+            self.X0 = sim.h_X[:self.n0].copy()   # the host mirror random_sphere filled (and copied to the device)
+            self.V0 = sim.old_v()
+
+    def take_step(self, dt, k):
+        while k > 0:
+            if self.every and self.done == self.every:
+                self.sim.synchronize()   # (the steps before belong to the timed work)
+                t = time.perf_counter()
+                self.sim.h_n = self.n0
+                self.sim.h_X[:self.n0] = self.X0
+                self.sim.copy_to_device()
+                self.sim.set_old_v(self.V0)
+                self.sim.synchronize()
+                self.seconds += time.perf_counter() - t
+                self.done = 0
+            m = min(k, self.every - self.done) if self.every else k
+            self.sim.take_step(dt, m)
+            self.done += m
+            k -= m
+
+
 def springs_drift_note(warmup, steps, dist):
     """The springs workload is not stationary: what the committed measurement
     (tools/diag/springs_drift.py -> profiles/r04_springs_drift.json) says about it, or a pointer to the
@@ -281,8 +336,13 @@ def springs_drift_note(warmup, steps, dist):
         evidence = "pairs inside the cut-off per cell: %s (profiles/r04_springs_drift.json)" % pairs
     except (OSError, ValueError, KeyError, TypeError):
         evidence = "no measurement on file: run tools/diag/springs_drift.py"
-    return ("value is for steps %d..%d of a run started from random_sphere(%g); the springs system clumps as it "
-            "runs and a cell-update costs proportionally more -- %s" % (warmup + 1, warmup + steps, dist, evidence))
+    if warmup + steps <= RESTART_EVERY:
+        which = "steps %d..%d of a run started from random_sphere(%g)" % (warmup + 1, warmup + steps, dist)
+    else:
+        which = ("%d steps after %d warm-up steps of runs started from random_sphere(%g), restarted from it every %d "
+                 "steps (RESTART_EVERY)" % (steps, warmup, dist, RESTART_EVERY))
+    return ("value is for %s; the springs system clumps as it runs and a cell-update costs proportionally more -- %s"
+            % (which, evidence))
 
 
 def grid_size_for(n, dist):
@@ -321,6 +381,29 @@ def cpu_baseline(model, n, gs, dist, dt, steps, state=None, renumber_every=0):
         "sample": f"{steps} take_steps of the same {n}-cell {model} system, dt {dt:g} "
                   "(oracle/yalla_host.hpp, g++ -O3, 1 thread)",
     }
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(directory, arrays, suffix=""):
+    """Write each (name, array) as directory/<name>.npy in float32 / float64.  If they hold more than
+    DUMP_LIMIT_BYTES, every array keeps the same fixed, seeded sample of rows (ascending), and the
+    sampled row numbers go to directory/sample_rows<suffix>.npy (float64: exact for any row number)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = [(name, np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32))
+              for name, a in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        rows = len(arrays[0][1])
+        assert all(len(a) == rows for _, a in arrays)
+        per_row = total // rows + 8
+        keep = np.sort(np.random.default_rng(0).choice(rows, (DUMP_LIMIT_BYTES - 4096) // per_row, replace=False))
+        arrays = [(name, a[keep]) for name, a in arrays] + [("sample_rows" + suffix, keep.astype(np.float64))]
+    for name, a in arrays:
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def free_port():
@@ -551,11 +634,15 @@ def main(argv=None):
             n_links = len(link_pairs)
         return sim
 
+    def restarting(s):
+        return Restarting(s, RESTART_EVERY if args.model in RESTART_MODELS and state is None and dt != 0 else 0)
+
     if not slab_path:
         sim = make_sim()
+        run = restarting(sim)
 
         def advance(k):
-            sim.take_step(dt, k)
+            run.take_step(dt, k)
     else:
         # ONE system of n_total cells, cut into z-slabs, one slab per GPU, ghost
         # layers exchanged point-to-point over xGMI each stage (yalla_amd/slab.py).
@@ -672,13 +759,26 @@ def main(argv=None):
     if args.sustained and rank == 0:
         sampler, stop_sampling, clock_samples = start_clock_sampler()
     # ---- the timed region: K steps, nothing else (no events, no host work but take_step's own) ----
+    restarts_s = run.seconds if not slab_path else 0.0
     t0 = time.perf_counter()
     advance(args.steps)
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - ((run.seconds - restarts_s) if not slab_path else 0.0)
     if sampler is not None:
         stop_sampling.set()
         sampler.join()
+    if args.dump_outputs:
+        # what a caller of take_step receives after the last timed step: the cells' points (the slab path:
+        # this rank's own cells in global id order, with their ids)
+        if not slab_path:
+            dump_outputs(args.dump_outputs, [("positions", sim.positions())])
+        else:
+            import numpy as np
+            ids, X = my_slab.own_cells()
+            order = np.argsort(ids, kind="stable")
+            sfx = f"_rank{rank}" if world > 1 else ""
+            dump_outputs(args.dump_outputs, [("positions" + sfx, X[order]),
+                                             ("cell_ids" + sfx, ids[order].astype(np.float64))], sfx)
     # The force kernel's launch time: HIP events attached to the kernel's own dispatch on the stream it
     # is launched on -- in a SECOND, untimed pass.  On one GPU that pass repeats the timed region on a
     # fresh copy of the system (same seed, same warm-up, the same K steps: the launches measured are
@@ -695,19 +795,21 @@ def main(argv=None):
         sampler are switched on BEFORE the preheat (their first use allocates: events, a stream, pinned memory), so
         that nothing but the K steps happens between the warm-up and the end of the pass; only what falls into the
         K steps is reported."""
-        nonlocal sim
+        nonlocal sim, run
         sim.close()
         sim = make_sim(sum_order=sum_order)
+        run = restarting(sim)
         thread, stop, samples = start_clock_sampler(0.002)
         sim.profile(True, every=1)
         scratch, _ = preheat((lambda: headline_scratch(sum_order)) if springs_headline else (lambda: make_sim(sum_order=sum_order)))
         advance(args.warmup)
         barrier()
         sim.profile_read()   # (the warm-up's launches: dropped)
+        restarts_s = run.seconds
         t1 = time.perf_counter()
         advance(args.steps)
         barrier()
-        t2 = time.perf_counter()
+        t2 = time.perf_counter() - (run.seconds - restarts_s)
         stop.set()
         thread.join()
         ms, count = sim.profile_read()
@@ -717,7 +819,8 @@ def main(argv=None):
         return ms, count, t2 - t1, clock_summary([mhz for t, mhz in samples if t1 <= t <= t2])
 
     tail_ab = None
-    if not slab_path and not graph_mode and not args.sustained:
+    force_ms, launches, events_pass = 0.0, 0, None   # a plain run measures the headline figure only
+    if args.full and not slab_path and not graph_mode and not args.sustained:
         force_ms, launches, events_seconds, headline_clock = events_pass_on_fresh_copy()
         events_pass = "the timed steps repeated on a fresh copy of the system, events on every force launch"
         if (rank == 0 and world == 1 and args.model in STATELESS_MODELS and "grid" in args.model and args.sum_order == 0
@@ -735,7 +838,7 @@ def main(argv=None):
                         "--sum-order 0 (the default: the reference's one running sum per cell, whole tiles) and "
                         "--sum-order 1 (own plane | other planes, the last tiles of a launch as half-tile workgroups: "
                         "768 of 15625 at 10^6 cells); the ms_per_step figures include ~24 us of event overhead per step"}
-    else:
+    elif args.full:
         sim.profile(True, every=1 if graph_mode else args.time_every)
         advance(min(args.steps, 10 if graph_mode or slab_path else 20))
         barrier()
@@ -745,17 +848,19 @@ def main(argv=None):
     if not slab_path:
         assert sim.get_d_n() == n_total
         n_force = n_total
-    else:
+    elif args.full:
         slab_step(True)  # untimed: settle ownership, then count
         n_force = my_slab.n_own()   # cells a force launch computes (ghost cells get none)
         assert int(reduce_over_ranks(n_force)) == n_total, "cells were lost or duplicated in migration"
+    else:
+        n_force = my_slab.n_own()
 
     elapsed = reduce_over_ranks(elapsed, take_max=True)
 
     # The base of the strong-scaling curve: the SAME whole system, undivided, on one GPU (rank
     # 0's), same step counts, measured here and now -- outside the timed region.
     one_gpu = None
-    if slab_path and world > 1 and not args.no_one_gpu_reference:
+    if slab_path and world > 1 and args.full and not args.no_one_gpu_reference:
         if rank == 0:
             my_slab.close()
             with Solution(args.model, n_total, gs, 1.0) as whole:
@@ -841,11 +946,11 @@ def main(argv=None):
                 "traffic": counters.get("traffic"),
                 "traffic_head": counters_head,
                 "bytes_per_launch": n_force * force_bytes,
-                "avg_launch_us": force_s * 1e6,
+                "avg_launch_us": force_s * 1e6 if launches else None,
                 **({"avg_launch_note": "sum of a stage's two launches (boundary tiles + all others, overlapping): an "
                                        "upper bound of the stage's force time, so `achieved` is a lower bound"}
                    if split_force else {}),
-                "timed_launches": launches,
+                "timed_launches": launches if launches else None,
                 "events_pass": events_pass,
                 "launches": (4 if split_force else 2) * args.steps,
                 "whole_step_achieved_GBs": step_bytes_per_cell(n_floats) * value / world / 1e9,
@@ -891,7 +996,7 @@ def main(argv=None):
             out["roofline"]["stale_counters"] = True
         headline = (world == 1 and not args.slab and not args.sustained and state is None
                     and args.model == "springs_grid" and args.arith == "exact" and args.renumber_every == 0)
-        if headline and not args.no_sustained_line:
+        if headline and args.full and not args.no_sustained_line:
             # Beside the headline, never instead of it, and outside its timed region: the figure that does not
             # drift.  --sustained-steps take_steps with dt = 0 on a fresh copy of the system -- every step
             # recomputes the same rho ~ 9.8 state: both grid builds, both force launches, reductions, updates --
@@ -920,18 +1025,19 @@ def main(argv=None):
                 "what": "dt = 0 on a fresh copy of the system: every take_step does all its work on the same state "
                         "(40.2 pairs inside the cut-off per cell, no clumping), long enough for the clock to settle; "
                         "`value` above is steps %d..%d of the moving system" % (args.warmup + 1, args.warmup + args.steps)}
-        if headline and not args.no_fast_tier_line:
+        if headline and args.full and not args.no_fast_tier_line:
             # beside the headline, never instead of it: the same steps on the fast-arithmetic build of the same
             # sources (what nvcc's default contraction and norm3df give the reference's own CUDA build)
             sim.close()
             with make_sim(lib=_ffi.device_lib("fast")) as fast:
                 scratch, _ = preheat(headline_scratch)   # (as the headline: not on an idle GPU's clock ramp)
-                fast.take_step(dt, args.warmup)
+                fast_run = restarting(fast)
+                fast_run.take_step(dt, args.warmup)
                 fast.synchronize()
                 t1 = time.perf_counter()
-                fast.take_step(dt, args.steps)
+                fast_run.take_step(dt, args.steps)
                 fast.synchronize()
-                fast_s = time.perf_counter() - t1
+                fast_s = time.perf_counter() - t1 - fast_run.seconds
                 if scratch is not None:
                     scratch.close()
             out["fast_arith_tier"] = {
@@ -940,7 +1046,7 @@ def main(argv=None):
                         "v_rcp_f32, contracted multiply-adds); positions within 1e-5 relative of the exact tier in lock-step, "
                         "cube ids and cell counts bit-exact (tests/test_fast_arith_gpu.py).  Not the headline: `value` above "
                         "is the exact tier, bit-comparable with the CPU oracle"}
-        if world == 1 and not args.slab and not args.no_cpu_baseline:
+        if world == 1 and not args.slab and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.model, n_total, gs, args.dist, dt, args.cpu_steps, state,
                                                args.renumber_every)
         sys.stdout.flush()

@@ -5,15 +5,24 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
+def no_gpu_env():
+    """The environment of a child that sees no GPU, on any machine (these tests are about the no-GPU path), and
+    has no launcher around it."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    return env
+
+
 def test_bench_refuses_to_run_without_gpu():
     proc = subprocess.run([sys.executable, BENCH, "--steps", "1"],
-                          capture_output=True, text=True, timeout=300)
+                          capture_output=True, text=True, timeout=300, env=no_gpu_env())
     assert proc.returncode != 0
     assert "needs a GPU" in (proc.stderr + proc.stdout)
 
@@ -21,7 +30,7 @@ def test_bench_refuses_to_run_without_gpu():
 def test_bench_starts_its_own_ranks():
     """No launcher, no WORLD_SIZE: --gpus 2 must start two rank processes itself (here
     both refuse for want of a GPU, and the parent reports both exit codes)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env = no_gpu_env()
     proc = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1"],
                           capture_output=True, text=True, timeout=300, env=env)
     assert proc.returncode != 0
@@ -34,7 +43,7 @@ def test_a_dead_rank_takes_the_others_down():
     """One rank fails while the other is stuck (as in a collective its peer never joins): the
     parent must end the stuck one and report, not hang until the driver's limit."""
     import time
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env = no_gpu_env()
     env["YALLA_BENCH_TEST_HANG_RANK"] = "0"
     t0 = time.time()
     proc = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1"],
@@ -74,6 +83,117 @@ def test_defaults_follow_north_star():
     assert bench.force_kernel_label(name, -1, 130_000, "springs_grid") == name
 
 
+def test_steps_sets_the_timed_steps():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).steps == 20
+    assert bench.parse(["--sustained"]).steps == 3000
+    assert bench.parse(["--sustained", "--steps", "20"]).steps == 20
+    assert bench.parse(["--steps", "7"]).steps == 7 and not bench.parse([]).full
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    X = np.arange(3000, dtype=np.float32).reshape(1000, 3)
+    bench.dump_outputs(str(tmp_path / "all"), [("positions", X)])
+    assert np.array_equal(np.load(tmp_path / "all" / "positions.npy"), X)
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 100 * 20)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [("positions", X), ("cell_ids", np.arange(1000.0))])
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) <= 100 and np.all(np.diff(rows) > 0)
+    got = np.load(tmp_path / "a" / "positions.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, X[rows.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "a" / "cell_ids.npy"), rows)
+    for name in ("positions", "cell_ids", "sample_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+
+
+def test_restarting_takes_every_step_within_the_first_restart_every():
+    """Steps are handed to the system in rounds of at most `every`, each round from the initial state again."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Sim:   # stands in for a Solution: the state is the number of steps since the last restore
+        h_n = 4
+        h_X = np.zeros((4, 3), np.float32)
+
+        def __init__(self, limit):
+            self.limit, self.calls, self.since_start, self.restores = limit, [], 0, 0
+
+        def old_v(self):
+            return np.zeros((4, 3), np.float32)
+
+        def take_step(self, dt, k):
+            self.calls.append(k)
+            self.since_start += k
+            assert self.since_start <= self.limit
+
+        def copy_to_device(self):
+            self.restores += 1
+            self.since_start = 0
+
+        def set_old_v(self, v):
+            pass
+
+        def synchronize(self):
+            pass
+
+    sim = Sim(10)
+    run = bench.Restarting(sim, 10)
+    run.take_step(0.001, 3)
+    run.take_step(0.001, 25)
+    assert sim.calls == [3, 7, 10, 8] and sim.restores == 2 and sim.since_start == 8 and run.seconds >= 0
+    never = Sim(25)
+    bench.Restarting(never, 0).take_step(0.001, 25)
+    assert never.calls == [25] and never.restores == 0
+
+
+@pytest.mark.gpu
+def test_long_springs_runs_restart_from_the_initial_state(device, tmp_path):
+    """The springs system collapses a little after 200 steps: a run of more than RESTART_EVERY steps starts again
+    from random_sphere, so that the run whose last step is the 23rd of its second round ends where the 3 + 20-step
+    run ends, bit for bit, and is timed as the same workload."""
+    sys.path.insert(0, ROOT)
+    import bench
+    got = {}
+    for run, steps in (("short", 20), ("long", bench.RESTART_EVERY + 20)):
+        proc = subprocess.run([sys.executable, BENCH, "--cells-total", "100000", "--steps", str(steps), "--warmup", "3",
+                               "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        out = json.loads([l for l in proc.stdout.splitlines() if l.strip()][-1])
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        got[run] = (out, np.load(tmp_path / run / "positions.npy"))
+    assert "restarted from it every %d steps" % bench.RESTART_EVERY in got["long"][0]["workload_note"]
+    assert "steps 4..23 of a run" in got["short"][0]["workload_note"]
+    assert np.array_equal(got["short"][1].view(np.uint32), got["long"][1].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(device, tmp_path):
+    """Without --full the line holds the headline figure and nothing that takes runs of its own; --dump-outputs
+    writes the last timed step's positions, the same from run to run."""
+    dumps = []
+    for run in ("a", "b"):
+        proc = subprocess.run([sys.executable, BENCH, "--cells-total", "100000", "--steps", "3", "--warmup", "1",
+                               "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        lines = [l for l in proc.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, proc.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert abs(out["value"] - 100000 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+        for extra in ("cpu_baseline", "sustained", "fast_arith_tier", "tail_ab", "headline_clock_mhz"):
+            assert extra not in out
+        assert out["roofline"]["timed_launches"] is None and out["roofline"]["achieved"] is None
+        X = np.load(tmp_path / run / "positions.npy")
+        assert X.dtype == np.float32 and X.shape == (100000, 3) and np.isfinite(X).all()
+        dumps.append(X)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
+
+
 @pytest.mark.gpu
 def test_self_launched_two_ranks_on_one_gpu(device):
     """`python bench.py --gpus 2` exactly as the driver starts it (no torchrun), both ranks
@@ -82,7 +202,7 @@ def test_self_launched_two_ranks_on_one_gpu(device):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["YALLA_BENCH_DEVICE"] = "0"
     proc = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--steps", "4",
-                           "--warmup", "1", "--cells-total", "300000", "--migrate-every", "2"],
+                           "--warmup", "1", "--cells-total", "300000", "--migrate-every", "2", "--full"],
                           capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip()]
@@ -101,10 +221,10 @@ def test_self_launched_two_ranks_on_one_gpu(device):
 
 @pytest.mark.gpu
 def test_headline_line_carries_the_sustained_figure_and_untimed_events(device):
-    """The default run's extras: `sustained` measured outside the timed region
+    """The --full run's extras: `sustained` measured outside the timed region
     (dt = 0, here shortened), the force kernel's events taken in a second pass over the same steps."""
     proc = subprocess.run([sys.executable, BENCH, "--cells-total", "200000", "--steps", "5", "--warmup", "2",
-                           "--sustained-steps", "200", "--no-cpu-baseline", "--no-fast-tier-line"],
+                           "--sustained-steps", "200", "--no-cpu-baseline", "--no-fast-tier-line", "--full"],
                           capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     out = json.loads([l for l in proc.stdout.splitlines() if l.strip()][-1])
@@ -124,7 +244,7 @@ def test_slab_path_runs_the_id_indexed_sorting_model(device):
     env["YALLA_BENCH_DEVICE"] = "0"
     proc = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--model", "sorting_grid",
                            "--steps", "4", "--warmup", "1", "--cells-total", "60000", "--dt", "0.002",
-                           "--migrate-every", "2"], capture_output=True, text=True, timeout=900, env=env)
+                           "--migrate-every", "2", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     out = json.loads([l for l in proc.stdout.splitlines() if l.strip()][-1])
     assert out["n_gpus"] == 2 and out["config"]["model"] == "sorting_grid" and out["value"] > 0

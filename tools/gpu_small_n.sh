@@ -6,10 +6,10 @@ out=$GRAFT_REPO_ROOT/gpurun_out/$1; mkdir -p $out
 cd $GRAFT_REPO_ROOT
 rm -f $out/lines.jsonl
 for v in 2 3; do
-  python3 bench.py --no-cpu-baseline --model sorting_grid --cells-total 10000 --dt 0.05 --steps 300 --force-variant $v | tail -1 >> $out/lines.jsonl
+  python3 bench.py --full --no-cpu-baseline --model sorting_grid --cells-total 10000 --dt 0.05 --steps 300 --force-variant $v | tail -1 >> $out/lines.jsonl
   for n in 10000 30000 50000 100000 300000; do
     # 20 steps like the headline line: springs contract, a long run is a denser system
-    python3 bench.py --no-cpu-baseline --cells-total $n --steps 20 --force-variant $v | tail -1 >> $out/lines.jsonl
+    python3 bench.py --full --no-cpu-baseline --cells-total $n --steps 20 --force-variant $v | tail -1 >> $out/lines.jsonl
   done
 done
 python3 - <<PY

@@ -8,7 +8,7 @@ for rep in 1 2 3; do
     IFS=: read tier cells tail <<< "$cfg"
     set -- $tier $cells
     {
-      timeout 400 python bench.py --arith $1 --cells-total $2 --no-cpu-baseline --no-fast-tier-line --sustained-steps 1500 \
+      timeout 400 python bench.py --full --arith $1 --cells-total $2 --no-cpu-baseline --no-fast-tier-line --sustained-steps 1500 \
         --tail-tiles $tail > $out/b.json 2> $out/b.err || { echo "bench failed"; tail -3 $out/b.err; continue; }
       python3 -c "import json; d=json.load(open('$out/b.json')); s=d.get('sustained'); print('$1 $2 tail $tail', '%.4g'%d['value'], '%.4f ms'%d['ms_per_step'], 'force %.1f us'%d['roofline']['avg_launch_us'], ('sustained %.4g, force %.1f us'%(s['value'], s['force_us'])) if s else '')" | tee -a $out/lines.txt
     }

@@ -99,7 +99,7 @@ def main(src, dst, key, bench_args, head=None):
         "kernel_sha": kernel_source_sha(),
         "head": head or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
                                        text=True).stdout.strip() or None,
-        "command": "rocprofv3 --kernel-trace --pmc <pass> -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 "
+        "command": "rocprofv3 --kernel-trace --pmc <pass> -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 "
                    + bench_args + " (tools/gpu_profile_round.sh; FETCH_SIZE and WRITE_SIZE in passes of their own)",
     }
     try:
