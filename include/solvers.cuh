@@ -1447,92 +1447,334 @@ __global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
 
 #undef YA_ROW_BOUNDS
 
-// Gabriel-graph force (replaces compute_cube_gabriel, solvers.cuh:509-602): the
-// candidates inside the cut-off are collected per thread, ordered by distance,
-// and the pair (i, j) only interacts if no closer candidate lies inside the
-// sphere around the midpoint of i and j with radius coefficient * dist / 2.
-// Kept straightforward (thread-private lists in scratch memory): it is off the
-// benchmarked path and only used by models that ask for Gabriel_solver.
-constexpr int GABRIEL_MAX_NEIGHBOURS = 100;  // the reference's fixed list size
+// Gabriel-graph force (replaces compute_cube_gabriel, solvers.cuh:509-602).  The reference's thread, per
+// cell i: (1) collect every cell of the 27 cubes with dist < cube_size, the cell itself included, in
+// d_nhood order and grid order inside a cube; (2) order them by distance with its selection sort (strict
+// `<`, swaps: NOT stable); (3) from the farthest to the closest candidate m, drop the pair (i, j) if a
+// candidate q < m lies strictly inside the sphere around the midpoint of i and j with radius
+// 0.5f * dist * coefficient (never for j == i); (4) add the kept pairs' terms in that same order.
+//
+// Here GABRIEL_LANES lanes share a cell (GABRIEL_CELLS cells per one-wavefront workgroup):
+//   scan     the lanes stream the 9 stencil rows of the sorted arrays and compact the hits into the cell's
+//            LDS list in candidate order (ballot + popcount of the lower lanes' bits);
+//   rank     each lane ranks its own candidates: rank = #closer + #equally close earlier in the list.  With
+//            all distances distinct (and none NaN) the selection sort's permutation IS that ascending
+//            order, whatever the start order.  Where a cell has a tie (lattices are full of them) or a NaN,
+//            one lane runs the reference's selection sort itself on the LDS list: ties change the order of
+//            the sum, hence its bits (tests/test_gabriel_*.py hold both paths bit for bit);
+//   test     each lane tests its own candidates against those ranked before them -- and, for functors
+//            declared stateless (YA_STATELESS), evaluates the terms of the pairs it keeps;
+//   sum      one lane adds the kept pairs' terms (evaluating them itself for other functors: per-cell
+//            counters like `d_n_nbs[i] += 1` see one lane, in order), farthest first, as the reference does.
+// No private arrays (0 bytes of scratch).  A cell with more than GABRIEL_CAP candidates is not done here:
+// it is appended to a list, and ya::gabriel_force_dense does it with a global workspace (Gabriel_computer
+// sizes it from the counted candidates), so any number of candidates is right and in bounds.
+constexpr int GABRIEL_LANES = 16;
+constexpr int GABRIEL_CELLS = 64 / GABRIEL_LANES;
+constexpr int GABRIEL_CAP = 64;  // candidates of a cell the LDS list holds (~13 at random_sphere(0.75), ~41 at the springs state)
+constexpr int GABRIEL_DENSE_ARRAYS = 8;  // x, y, z, d, slot, rank, order, kept: the dense kernel's lists
 
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(64) void gabriel_force(const int n,
-    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
-    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
-    const int n_cubes, const float cube_size, const float gabriel_coefficient,
-    Pt* __restrict__ d_dX, const bool has_gen)
+namespace gabriel {
+// The reference's selection sort (solvers.cuh:550-566) of the list's indices by distance, one lane.
+template<typename Index>
+__device__ __forceinline__ void selection_sort(const int count, const float* d, Index* order)
 {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-
-    const Entry<Pt> self = sorted[s];
-    const Pt Xi = self.X;
-    const int i = self.id;
-    const int c = cube_id[s];
-
-    int slot[GABRIEL_MAX_NEIGHBOURS];
-    float distance[GABRIEL_MAX_NEIGHBOURS];
-    int n_neighs = 0;
-    for (int row = 0; row < 9; row++) {
-        const int mid = c + stencil_row_offset(row, gs);
-        const int k_end = offs[min(max(mid + 2, 0), n_cubes)];
-        for (int k = offs[min(max(mid - 1, 0), n_cubes)]; k < k_end; k++) {
-            const Pt r = Xi - sorted[k].X;
-            const float dist = dist3(r.x, r.y, r.z);
-            if (dist >= cube_size) continue;
-            D_ASSERT(n_neighs < GABRIEL_MAX_NEIGHBOURS);
-            slot[n_neighs] = k;
-            distance[n_neighs] = dist;
-            n_neighs++;
-        }
-    }
-    // selection sort by distance, closest first (solvers.cuh:550-566)
-    for (int m = 0; m < n_neighs - 1; m++) {
-        int closest = m;
-        for (int q = m + 1; q < n_neighs; q++)
-            if (distance[q] < distance[closest]) closest = q;
-        if (closest != m) {
-            const int ts = slot[closest];
-            slot[closest] = slot[m];
-            slot[m] = ts;
-            const float td = distance[closest];
-            distance[closest] = distance[m];
-            distance[m] = td;
-        }
-    }
-    // farthest first: keep (i, j) unless a closer candidate sits in its Gabriel sphere
-    Pt F = ya::zero<Pt>();
-    float3 sum_v{0.f, 0.f, 0.f};
-    float sum_friction = 0;
-    for (int m = n_neighs - 1; m >= 0; m--) {
-        const Entry<Pt> other = sorted[slot[m]];
-        const int j = other.id;
-        const float dist = distance[m];
-        bool keep = true;
-        if (j != i) {
-            const float radius = 0.5f * dist * gabriel_coefficient;
-            const Pt mid_point = 0.5f * (Xi + other.X);
-            for (int q = m - 1; q >= 0; q--) {
-                const Pt r_mk = mid_point - sorted[slot[q]].X;
-                if (dist3(r_mk.x, r_mk.y, r_mk.z) < radius) {
-                    keep = false;
-                    break;
-                }
+    for (int m = 0; m < count; m++) order[m] = (Index)m;
+    for (int m = 0; m < count - 1; m++) {
+        float min_val = d[order[m]];
+        int min_index = m;
+        for (int q = m + 1; q < count; q++) {
+            const float compare_val = d[order[q]];
+            if (compare_val < min_val) {
+                min_index = q;
+                min_val = compare_val;
             }
         }
-        if (!keep) continue;
+        if (min_index != m) {
+            const Index t = order[min_index];
+            order[min_index] = order[m];
+            order[m] = t;
+        }
+    }
+}
+// Is a candidate ranked below `rank` strictly inside the sphere (mx, my, mz; radius)?  (solvers.cuh:584-592:
+// the reference walks them from rank - 1 down and stops at the first; which one it finds does not matter.)
+template<typename Index>
+__device__ __forceinline__ bool occluded(const int rank, const float mx, const float my, const float mz,
+    const float radius, const Index* order, const float* x, const float* y, const float* z)
+{
+    for (int m = rank - 1; m >= 0; m--) {
+        const int q = order[m];
+        if (dist3(mx - x[q], my - y[q], mz - z[q]) < radius) return true;
+    }
+    return false;
+}
+// A cell's candidates into the list (x, y, z, d, slot) in the reference's order, by the `lanes` lanes
+// from `first_lane` of the wavefront; returns the number of candidates (entries beyond cap are not written).
+template<typename Pt>
+__device__ __forceinline__ int collect(const int lane, const int lanes, const int first_lane, const Pt Xi,
+    const int c, const Entry<Pt>* __restrict__ sorted, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cube_size, const int cap, float* x, float* y, float* z, float* d, int* slot)
+{
+    const unsigned long long group = (lanes == 64 ? ~0ull : ((1ull << lanes) - 1)) << first_lane;
+    const unsigned long long below = group & ((1ull << (first_lane + lane)) - 1);
+    int count = 0;
+    for (int row = 0; row < 9; row++) {
+        const int mid = c + stencil_row_offset(row, gs);
+        const int k_begin = offs[min(max(mid - 1, 0), n_cubes)];
+        const int k_end = offs[min(max(mid + 2, 0), n_cubes)];
+        for (int base = k_begin; base < k_end; base += lanes) {
+            const int k = base + lane;
+            bool hit = false;
+            Pt Xk;
+            float dist = 0;
+            if (k < k_end) {
+                Xk = sorted[k].X;
+                const Pt r = Xi - Xk;
+                dist = dist3(r.x, r.y, r.z);
+                hit = !(dist >= cube_size);  // (solvers.cuh:540: a NaN distance is a candidate)
+            }
+            const unsigned long long hits = __ballot(hit) & group;
+            if (hit) {
+                const int q = count + __popcll(hits & below);
+                if (q < cap) {
+                    x[q] = Xk.x;
+                    y[q] = Xk.y;
+                    z[q] = Xk.z;
+                    d[q] = dist;
+                    slot[q] = k;
+                }
+            }
+            count += __popcll(hits);
+        }
+    }
+    return count;
+}
+// rank[p] = the place of candidate p in the selection sort's order, order[rank] = p: ranked by the lanes
+// while the cell's distances are distinct, sorted by its first lane where they are not.
+template<typename Index>
+__device__ __forceinline__ void rank_list(const int lane, const int lanes, const int first_lane,
+    const int count, const float* d, Index* rank, Index* order)
+{
+    const unsigned long long group = (lanes == 64 ? ~0ull : ((1ull << lanes) - 1)) << first_lane;
+    bool odd = false;
+    for (int p = lane; p < count; p += lanes) {
+        const float dp = d[p];
+        int r = 0;
+        for (int q = 0; q < count; q++) {
+            const float dq = d[q];
+            r += (dq < dp || (dq == dp && q < p)) ? 1 : 0;
+            odd |= dq == dp && q != p;
+        }
+        odd |= dp != dp;
+        rank[p] = (Index)r;
+    }
+    const bool tied = (__ballot(odd) & group) != 0;
+    coop::wave_sync();
+    if (!tied) {
+        for (int p = lane; p < count; p += lanes) order[rank[p]] = (Index)p;
+    } else if (lane == 0) {
+        selection_sort(count, d, order);
+        for (int m = 0; m < count; m++) rank[order[m]] = (Index)m;
+    }
+    coop::wave_sync();
+}
+
+// The test and the sum of a cell whose list is ranked: kept[rank] by the lanes, then the kept pairs' terms
+// in one lane, farthest first (the functors are called for i from that lane alone, in the reference's order:
+// functors that count per cell, `d_n_nbs[i] += 1` of tests/test_solvers.cu:343-352, stay right).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Index>
+__device__ __forceinline__ void test_and_sum(const int lane, const int lanes, const int s, const Pt Xi,
+    const int i, const int count, const float gabriel_coefficient, const float* x, const float* y,
+    const float* z, const float* d, const int* slot, const Index* rank, const Index* order, Index* kept,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, Pt* __restrict__ d_dX,
+    const bool has_gen)
+{
+    for (int p = lane; p < count; p += lanes) {  // solvers.cuh:575-593
+        bool keep = true;
+        if (slot[p] != s) {  // j != i
+            const float radius = 0.5f * d[p] * gabriel_coefficient;
+            keep = !occluded((int)rank[p], 0.5f * (Xi.x + x[p]), 0.5f * (Xi.y + y[p]), 0.5f * (Xi.z + z[p]),
+                radius, order, x, y, z);
+        }
+        kept[rank[p]] = keep ? 1 : 0;
+    }
+    __threadfence_block();  // (the dense kernel's lists are in global memory)
+    coop::wave_sync();
+    if (lane != 0) return;
+    Pt F = ya::zero<Pt>();  // solvers.cuh:594-599
+    float3 sum_v{0.f, 0.f, 0.f};
+    float sum_friction = 0;
+    for (int m = count - 1; m >= 0; m--) {
+        if (!kept[m]) continue;
+        const int p = order[m];
+        const float dist = d[p];
+        const Entry<Pt> other = sorted[slot[p]];
         const Pt r = Xi - other.X;
-        F += pw_int(Xi, r, dist, i, j);
-        const float friction = pw_friction(Xi, r, dist, i, j);
+        F += pw_int(Xi, r, dist, i, other.id);
+        const float friction = pw_friction(Xi, r, dist, i, other.id);
         sum_friction += friction;
+        // the old_v term only where the friction is not zero: the same bits as the reference's
+        // unconditional `sum_v += friction * d_old_v[j]` unless old_v is not finite (0 * inf)
         if (friction != 0) {
-            const float4 v = sorted_v[slot[m]];
+            const float4 v = sorted_v[slot[p]];
             sum_v.x += friction * v.x;
             sum_v.y += friction * v.y;
             sum_v.z += friction * v.z;
         }
     }
     store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
+}
+}  // namespace gabriel
+
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(64) void gabriel_force(const int n,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int CAP = GABRIEL_CAP;
+    constexpr int SLOTS = CAP / GABRIEL_LANES;
+    // x, y, z, d while the list is tested; then, for stateless functors, the kept pairs' terms by rank:
+    // F (NF floats), friction, friction * old_v (3)
+    constexpr int WORDS = NF + 4;
+    __shared__ float sh_list[GABRIEL_CELLS][WORDS][CAP];
+    __shared__ int sh_slot[GABRIEL_CELLS][CAP];
+    __shared__ unsigned char sh_rank[GABRIEL_CELLS][3][CAP];  // rank, order, kept
+
+    const int cell = threadIdx.x / GABRIEL_LANES;
+    const int lane = threadIdx.x % GABRIEL_LANES;
+    const int s = blockIdx.x * GABRIEL_CELLS + cell;
+    if (s >= n) return;  // (whole groups leave: everything below is per group)
+
+    float* x = sh_list[cell][0];
+    float* y = sh_list[cell][1];
+    float* z = sh_list[cell][2];
+    float* d = sh_list[cell][3];
+    unsigned char* rank = sh_rank[cell][0];
+    unsigned char* order = sh_rank[cell][1];
+    unsigned char* kept = sh_rank[cell][2];
+    const Entry<Pt> self = sorted[s];
+    const Pt Xi = self.X;
+    const int i = self.id;
+    const int count = gabriel::collect(lane, GABRIEL_LANES, cell * GABRIEL_LANES, Xi, cube_id[s], sorted, offs, gs,
+        n_cubes, cube_size, CAP, x, y, z, d, sh_slot[cell]);
+    if (count > CAP) {  // ya::gabriel_force_dense does this cell
+        if (lane == 0) {
+            const int at = atomicAdd(&n_dense[0], 1);
+            dense[at] = s;
+            atomicMax(&n_dense[1], count);
+        }
+        return;
+    }
+    coop::wave_sync();
+    gabriel::rank_list(lane, GABRIEL_LANES, cell * GABRIEL_LANES, count, d, rank, order);
+    if constexpr (!stateless_pair<Pt, pw_int, pw_friction>()) {
+        gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, GABRIEL_LANES, s, Xi, i, count, gabriel_coefficient,
+            x, y, z, d, sh_slot[cell], rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+        return;
+    } else {
+        // Functors declared stateless (YA_STATELESS): each lane also evaluates the terms of the pairs it keeps
+        // (into the position arrays, free once every lane has tested), and one lane only adds them up.
+        bool keep[SLOTS];
+        float dist[SLOTS];
+        int rk[SLOTS], k[SLOTS];
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) {  // solvers.cuh:575-593, candidates p = lane + GABRIEL_LANES * a
+            const int p = lane + GABRIEL_LANES * a;
+            keep[a] = false;
+            if (p < count) {
+                dist[a] = d[p];
+                rk[a] = rank[p];
+                k[a] = sh_slot[cell][p];
+                keep[a] = true;
+                if (k[a] != s) {  // j != i
+                    const float radius = 0.5f * dist[a] * gabriel_coefficient;
+                    keep[a] = !gabriel::occluded(rk[a], 0.5f * (Xi.x + x[p]), 0.5f * (Xi.y + y[p]),
+                        0.5f * (Xi.z + z[p]), radius, order, x, y, z);
+                }
+            }
+        }
+        coop::wave_sync();
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) {
+            const int p = lane + GABRIEL_LANES * a;
+            if (p >= count) continue;
+            kept[rk[a]] = keep[a];
+            if (!keep[a]) continue;
+            const Entry<Pt> other = sorted[k[a]];
+            const Pt r = Xi - other.X;
+            const Pt F = pw_int(Xi, r, dist[a], i, other.id);
+            const float friction = pw_friction(Xi, r, dist[a], i, other.id);
+#pragma unroll
+            for (int q = 0; q < NF; q++) sh_list[cell][q][rk[a]] = field(F, q);
+            sh_list[cell][NF][rk[a]] = friction;
+            if (friction != 0) {  // (see test_and_sum)
+                const float4 v = sorted_v[k[a]];
+                sh_list[cell][NF + 1][rk[a]] = friction * v.x;
+                sh_list[cell][NF + 2][rk[a]] = friction * v.y;
+                sh_list[cell][NF + 3][rk[a]] = friction * v.z;
+            }
+        }
+        coop::wave_sync();
+        if (lane != 0) return;
+        Pt F = ya::zero<Pt>();  // solvers.cuh:594-599
+        float3 sum_v{0.f, 0.f, 0.f};
+        float sum_friction = 0;
+        for (int m = count - 1; m >= 0; m--) {
+            if (!kept[m]) continue;
+            Pt term;
+#pragma unroll
+            for (int q = 0; q < NF; q++) field(term, q) = sh_list[cell][q][m];
+            F += term;
+            const float friction = sh_list[cell][NF][m];
+            sum_friction += friction;
+            if (friction != 0) {
+                sum_v.x += sh_list[cell][NF + 1][m];
+                sum_v.y += sh_list[cell][NF + 2][m];
+                sum_v.z += sh_list[cell][NF + 3][m];
+            }
+        }
+        store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
+    }
+}
+
+// The cells ya::gabriel_force left (more than GABRIEL_CAP candidates): one wavefront per cell, the same
+// stages on lists in a global workspace of `stride` >= the largest count entries each, per workgroup.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(64) void gabriel_force_dense(const int* __restrict__ dense,
+    const int* __restrict__ n_dense, const Entry<Pt>* __restrict__ sorted,
+    const float4* __restrict__ sorted_v, const int* __restrict__ cube_id, const int* __restrict__ offs,
+    const int gs, const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen, float* __restrict__ workspace, const long stride)
+{
+    const int lane = threadIdx.x;
+    float* x = workspace + GABRIEL_DENSE_ARRAYS * stride * blockIdx.x;
+    float* y = x + stride;
+    float* z = y + stride;
+    float* d = z + stride;
+    int* slot = reinterpret_cast<int*>(d + stride);
+    int* rank = slot + stride;
+    int* order = rank + stride;
+    int* kept = order + stride;
+    for (int t = blockIdx.x; t < n_dense[0]; t += gridDim.x) {
+        const int s = dense[t];
+        const Entry<Pt> self = sorted[s];
+        const Pt Xi = self.X;
+        const int count = gabriel::collect(lane, 64, 0, Xi, cube_id[s], sorted, offs, gs, n_cubes, cube_size,
+            (int)stride, x, y, z, d, slot);
+        __threadfence_block();
+        coop::wave_sync();
+        gabriel::rank_list(lane, 64, 0, count, d, rank, order);
+        __threadfence_block();
+        coop::wave_sync();
+        gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, 64, s, Xi, self.id, count, gabriel_coefficient, x, y,
+            z, d, slot, rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+        __threadfence_block();
+        coop::wave_sync();  // the next cell reuses the workspace
+    }
 }
 
 // fix = what is subtracted from dX.xyz: 0 = mean (already in d_mean), 1 = the
@@ -3112,22 +3354,66 @@ template<typename Pt>
 class Gabriel_computer : public Grid_computer<Pt> {
 public:
     float gabriel_coefficient;
+    // -1 (default) = ya::gabriel_force (+ ya::gabriel_force_dense for cells with more than GABRIEL_CAP
+    // candidates); 0 = gabriel_force_direct, the A/B baseline of tools/ab/force_variants.cuh, only with
+    // -DYA_EXPERIMENTAL_FORCE_VARIANTS (at most 100 candidates per cell).  (Grid_computer::force_variant.)
     Gabriel_computer(
         int n_max, int grid_size = 50, float cube_size = 1, float gabriel_coefficient = 0.8)
         : Grid_computer<Pt>{n_max, grid_size, cube_size}, gabriel_coefficient{gabriel_coefficient}
-    {}
+    {
+        YA_CHECK(ya_malloc((void**)&d_dense, (size_t)(n_max + 2) * sizeof(int)));
+    }
+    ~Gabriel_computer()
+    {
+        ya_free(d_dense);
+        if (d_workspace) ya_free(d_workspace);
+    }
+    Gabriel_computer(const Gabriel_computer&) = delete;
     bool use_sorted_pipeline() const { return false; }
 
 protected:
+    int* d_dense = nullptr;  // [0] cells left to gabriel_force_dense, [1] their largest count, then the cells
+    float* d_workspace = nullptr;
+    size_t workspace_floats = 0;
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints(const int n, const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v,
         Pt* d_dX, const bool has_gen, const int n_active, const bool keep_sorted)
     {
         assert(n_active == n);
         this->grid.build_sorted(n, d_X, d_old_v, this->cube_size, this->d_sorted, this->d_sorted_v);
-        ya::gabriel_force<Pt, pw_int, pw_friction><<<(n + 63) / 64, 64>>>(n, this->d_sorted,
+        if (this->force_variant == 0) {
+#ifdef YA_EXPERIMENTAL_FORCE_VARIANTS
+            ya::gabriel_force_direct<Pt, pw_int, pw_friction><<<(n + 63) / 64, 64>>>(n, this->d_sorted,
+                this->d_sorted_v, this->grid.d_cube_id, this->grid.offsets(), this->grid.grid_size,
+                this->grid.n_cubes, this->cube_size, gabriel_coefficient, d_dX, has_gen);
+            return;
+#else
+            fprintf(stderr, "yalla-hip: Gabriel_computer::force_variant 0 is an A/B baseline kept in "
+                            "tools/ab/force_variants.cuh: compile with -DYA_EXPERIMENTAL_FORCE_VARIANTS -Itools/ab\n");
+            abort();
+#endif
+        }
+        YA_CHECK(ya_memset_async(d_dense, 0, 2 * sizeof(int), nullptr));
+        ya::gabriel_force<Pt, pw_int, pw_friction><<<(n + ya::GABRIEL_CELLS - 1) / ya::GABRIEL_CELLS, 64>>>(n,
+            this->d_sorted, this->d_sorted_v, this->grid.d_cube_id, this->grid.offsets(), this->grid.grid_size,
+            this->grid.n_cubes, this->cube_size, gabriel_coefficient, d_dX, has_gen, d_dense + 2, d_dense);
+        // the step waits for the count here (this solver has no captured or overlapped step to protect)
+        int h_dense[2];
+        YA_CHECK(ya_memcpy_d2h(h_dense, d_dense, sizeof(h_dense)));
+        if (h_dense[0] == 0) return;
+        // one wavefront per dense cell, each with lists of the largest count, within ~256 MiB if it can be
+        const long stride = h_dense[1];
+        const size_t per_block = ya::GABRIEL_DENSE_ARRAYS * (size_t)stride;
+        int blocks = (int)std::min<size_t>((size_t)h_dense[0], std::max<size_t>(1, (64u << 20) / per_block));
+        blocks = std::min(blocks, 2048);
+        if (per_block * blocks > workspace_floats) {
+            if (d_workspace) ya_free(d_workspace);
+            workspace_floats = per_block * blocks;
+            YA_CHECK(ya_malloc((void**)&d_workspace, workspace_floats * sizeof(float)));
+        }
+        ya::gabriel_force_dense<Pt, pw_int, pw_friction><<<blocks, 64>>>(d_dense + 2, d_dense, this->d_sorted,
             this->d_sorted_v, this->grid.d_cube_id, this->grid.offsets(), this->grid.grid_size,
-            this->grid.n_cubes, this->cube_size, gabriel_coefficient, d_dX, has_gen);
+            this->grid.n_cubes, this->cube_size, gabriel_coefficient, d_dX, has_gen, d_workspace, stride);
     }
 };
 

@@ -1,6 +1,7 @@
 // Earlier grid-force kernels, kept as A/B baselines and as independent statements of the same sums:
 //
 //   ya::grid_force_direct   the reference's structure -- every cell walks its 27 cubes through L1 / L2
+//   ya::gabriel_force_direct  the first Gabriel force, one thread per cell with scratch lists (below)
 //   ya::grid_force          round 1's LDS-staged two-phase kernel with a BYTE FIFO of hits, 256-thread
 //                           workgroups (grid_force_bits, the shipped kernel, keeps one BIT per candidate
 //                           in one-wavefront workgroups: 242 against 260 us at 1 M cells)
@@ -320,5 +321,93 @@ __global__ __launch_bounds__(FORCE_BLOCK) void grid_force(const int n,
 }
 
 
+
+// gabriel_force_direct: the first Gabriel-graph force (compute_cube_gabriel, solvers.cuh:509-602), one
+// thread per cell with thread-private lists in scratch memory (~800 B per lane), an O(k^2) selection sort
+// there and the Gabriel test gathering positions from global memory.  Kept as the A/B baseline of
+// ya::gabriel_force (Gabriel_computer::force_variant 0).  It has the reference's FIXED list size: more
+// than GABRIEL_MAX_NEIGHBOURS candidates inside the cut-off trip the device assert (out-of-bounds scratch
+// writes under NDEBUG) -- never run it on a dense system.
+constexpr int GABRIEL_MAX_NEIGHBOURS = 100;  // the reference's fixed list size
+
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(64) void gabriel_force_direct(const int n,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+
+    const Entry<Pt> self = sorted[s];
+    const Pt Xi = self.X;
+    const int i = self.id;
+    const int c = cube_id[s];
+
+    int slot[GABRIEL_MAX_NEIGHBOURS];
+    float distance[GABRIEL_MAX_NEIGHBOURS];
+    int n_neighs = 0;
+    for (int row = 0; row < 9; row++) {
+        const int mid = c + stencil_row_offset(row, gs);
+        const int k_end = offs[min(max(mid + 2, 0), n_cubes)];
+        for (int k = offs[min(max(mid - 1, 0), n_cubes)]; k < k_end; k++) {
+            const Pt r = Xi - sorted[k].X;
+            const float dist = dist3(r.x, r.y, r.z);
+            if (dist >= cube_size) continue;
+            D_ASSERT(n_neighs < GABRIEL_MAX_NEIGHBOURS);
+            slot[n_neighs] = k;
+            distance[n_neighs] = dist;
+            n_neighs++;
+        }
+    }
+    // selection sort by distance, closest first (solvers.cuh:550-566)
+    for (int m = 0; m < n_neighs - 1; m++) {
+        int closest = m;
+        for (int q = m + 1; q < n_neighs; q++)
+            if (distance[q] < distance[closest]) closest = q;
+        if (closest != m) {
+            const int ts = slot[closest];
+            slot[closest] = slot[m];
+            slot[m] = ts;
+            const float td = distance[closest];
+            distance[closest] = distance[m];
+            distance[m] = td;
+        }
+    }
+    // farthest first: keep (i, j) unless a closer candidate sits in its Gabriel sphere
+    Pt F = ya::zero<Pt>();
+    float3 sum_v{0.f, 0.f, 0.f};
+    float sum_friction = 0;
+    for (int m = n_neighs - 1; m >= 0; m--) {
+        const Entry<Pt> other = sorted[slot[m]];
+        const int j = other.id;
+        const float dist = distance[m];
+        bool keep = true;
+        if (j != i) {
+            const float radius = 0.5f * dist * gabriel_coefficient;
+            const Pt mid_point = 0.5f * (Xi + other.X);
+            for (int q = m - 1; q >= 0; q--) {
+                const Pt r_mk = mid_point - sorted[slot[q]].X;
+                if (dist3(r_mk.x, r_mk.y, r_mk.z) < radius) {
+                    keep = false;
+                    break;
+                }
+            }
+        }
+        if (!keep) continue;
+        const Pt r = Xi - other.X;
+        F += pw_int(Xi, r, dist, i, j);
+        const float friction = pw_friction(Xi, r, dist, i, j);
+        sum_friction += friction;
+        if (friction != 0) {
+            const float4 v = sorted_v[slot[m]];
+            sum_v.x += friction * v.x;
+            sum_v.y += friction * v.y;
+            sum_v.z += friction * v.z;
+        }
+    }
+    store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
+}
 
 }  // namespace ya

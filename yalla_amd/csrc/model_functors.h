@@ -48,6 +48,22 @@ __device__ inline float3 clipped_spring(float3 Xi, float3 r, float dist, int i, 
     return dF;
 }
 
+// --- examples/growth_w_wall.cu:45-63: that example's own relu_force (r_max = 1).  Node 0 is the wall: no
+// pairwise force on or from it.  `0.7 - dist` and `dist - 0.8` are binary64 differences that fmaxf takes as
+// binary32 (as the reference's CUDA fmaxf does), then F and r.x * F / dist are scalar binary32. ---------
+__device__ inline float3 wall_relu_force(float3 Xi, float3 r, float dist, int i, int j)
+{
+    float3 dF{0.f, 0.f, 0.f};
+    if (i == 0 or j == 0) return dF;
+    if (i == j) return dF;
+    if (dist > 1.0f) return dF;
+    const float F = fmaxf((float)(0.7 - (double)dist), 0.f) - fmaxf((float)((double)dist - 0.8), 0.f);
+    dF.x += r.x * F / dist;
+    dF.y += r.y * F / dist;
+    dF.z += r.z * F / dist;
+    return dF;
+}
+
 // A spring whose force fades to zero at the cut-off (NOT a reference model: the z-slab decomposition's
 // tests use it with friction_on_background).  Nothing about such a pair changes by a jump when it crosses
 // the cut-off, so a divided run has no pair "within rounding of the cut-off" to excuse a cell that differs
@@ -427,6 +443,7 @@ inline void proliferate(float rate, double mean_dist, unsigned seed, unsigned st
 #ifdef YA_STATELESS
 YA_STATELESS(float3, models::spring)
 YA_STATELESS(float3, models::clipped_spring)
+YA_STATELESS(float3, models::wall_relu_force)
 YA_STATELESS(float3, models::fading_spring)
 YA_STATELESS(float3, models::differential_adhesion)
 YA_STATELESS(float3, relu_force<float3>)

@@ -19,6 +19,11 @@
 
 #include "yalla_models.h"
 
+#ifdef YA_ORACLE
+// Gabriel_solver and wall_forces, restated host-serially for the CPU build (its engine header has neither)
+#include "gabriel_host.h"
+#endif
+
 namespace harness {
 
 struct Sim_base {
@@ -64,13 +69,17 @@ struct Sim_base {
 template<typename Pt>
 using Harness_slab_solver = Slab_grid_solver_impl<Pt, harness_ops>;
 
-template<typename Pt, bool GRID>
+// The solver of a model: Tile_solver (false), Grid_solver (true), Gabriel_solver
+enum Solver_kind { TILE = 0, GRID = 1, GABRIEL = 2 };
+
+template<typename Pt, int SOLVER>
 struct Cells;
 
 template<typename Pt>
-struct Cells<Pt, false> : public Solution<Pt, Tile_solver> {
+struct Cells<Pt, TILE> : public Solution<Pt, Tile_solver> {
     Cells(int n_max, int, float) : Solution<Pt, Tile_solver>{n_max} {}
     Grid* grid_ptr() { return nullptr; }
+    int set_gabriel_coefficient(float) { return -2; }
     int set_tile_lanes(int v)
     {
 #ifdef YA_ORACLE
@@ -105,9 +114,10 @@ struct Cells<Pt, false> : public Solution<Pt, Tile_solver> {
 };
 
 template<typename Pt>
-struct Cells<Pt, true> : public Solution<Pt, Harness_slab_solver> {
+struct Cells<Pt, GRID> : public Solution<Pt, Harness_slab_solver> {
     Cells(int n_max, int gs, float cs) : Solution<Pt, Harness_slab_solver>{n_max, gs, cs} {}
     Grid* grid_ptr() { return &this->grid; }
+    int set_gabriel_coefficient(float) { return -2; }
     int set_tile_lanes(int) { return -2; }
     int set_cube_size(float cs)
     {
@@ -210,6 +220,55 @@ struct Cells<Pt, true> : public Solution<Pt, Harness_slab_solver> {
 
 };
 
+// Gabriel_solver (examples/growth_w_wall.cu:142): the grid restricted to Gabriel-graph neighbours.  Single
+// GPU, d_X pipeline only: the slab, tile-lane and sorted-pipeline knobs are refused as for Tile_solver.
+template<typename Pt>
+struct Cells<Pt, GABRIEL> : public Solution<Pt, Gabriel_solver> {
+    Cells(int n_max, int gs, float cs) : Solution<Pt, Gabriel_solver>{n_max, gs, cs} {}
+    Grid* grid_ptr() { return &this->grid; }
+    int set_gabriel_coefficient(float c)
+    {
+        this->gabriel_coefficient = c;
+        return 0;
+    }
+    int set_tile_lanes(int) { return -2; }
+    int set_cube_size(float cs)
+    {
+        this->cube_size = cs;
+        return 0;
+    }
+    // -1 = ya::gabriel_force (default), 0 = the A/B baseline gabriel_force_direct (tools/ab/force_variants.cuh)
+    int set_force_variant(int v)
+    {
+#ifdef YA_ORACLE
+        return -2;
+#else
+        if (v != -1 && v != 0) return -1;
+        this->force_variant = v;
+        return 0;
+#endif
+    }
+    int set_coop_lanes(int) { return -2; }
+    int set_stage_v_max(int) { return -2; }
+    int set_tail_tiles(int) { return -2; }
+    int set_sum_order(int) { return -2; }
+    int set_sorted_pipeline(int) { return -2; }
+    int set_graph(int) { return -2; }
+    int set_slab_global_ids(int) { return -2; }
+    int slab_init(float, float, float, const int*, int) { return -2; }
+    int get_own(float*, int*) { return -2; }
+    int slab_adopt(const ya::Slab_plan&, int, const Pt*, int, Pt*, int*) { return -2; }
+    int slab_setup(int, int, int, int) { return -2; }
+    int slab_set_transport(ya_slab_exchange_fn, ya_slab_allreduce_fn, void*) { return -2; }
+    int slab_use_rccl(void*) { return -2; }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    int slab_step(float, int, Generic_forces<Pt>) { return -2; }
+    int set_slab_guard(int) { return -2; }
+    int set_slab_guard_lag(float) { return -2; }
+    int set_slab_local_order(int) { return -2; }
+    struct { int n_own = -2, n_local = -2, failed = 0; long rehalos = -2, guard_requests = -2; float* d_guard = nullptr; } slab;
+};
+
 inline int copy_grid_out(Grid& g, int n_max, int* cube_id, int* point_id, int* cube_start,
     int* cube_end)
 {
@@ -310,6 +369,22 @@ struct Default_links_gen : public Links_gen<Pt, linear_force<Pt>> {
             return link_forces<Pt>(*l, d_X, d_dX);
         };
     }
+};
+
+// examples/growth_w_wall.cu:155-157: the wall of node 0 as the generic force.  Node 0's identity is the
+// physics: no renumbering.
+struct Wall_gen : public No_gen<float3> {
+    template<typename C>
+    Generic_forces<float3> gen(C&)
+    {
+        return [](const int n, const float3* __restrict__ d_X, float3* d_dX) {
+            return wall_forces<float3, xy_wall_relu_force>(n, d_X, d_dX, 0);
+        };
+    }
+    template<typename C>
+    int renumber_now(C&) { return -2; }
+    template<typename C>
+    int keep_in_cube_order(C&, int) { return -2; }
 };
 
 struct Sorting_params {
@@ -472,10 +547,10 @@ struct Growth_policy : public No_gen<typename Rule::Pt> {
 };
 
 // ---- one model = point type x solver x functors x policy ------------------------
-template<typename Pt, bool GRID, Pairwise_interaction<Pt> pw_int,
+template<typename Pt, int SOLVER, Pairwise_interaction<Pt> pw_int,
     Pairwise_friction<Pt> pw_friction, typename Policy>
 struct Sim : public Sim_base {
-    Cells<Pt, GRID> cells;
+    Cells<Pt, SOLVER> cells;
     Policy policy;
     Sim(int n_max, int gs, float cs) : cells{n_max, gs, cs} {}
 
@@ -538,6 +613,7 @@ struct Sim : public Sim_base {
         if (std::string(name) == "graph") return cells.set_graph((int)v);
         if (std::string(name) == "tile_lanes") return cells.set_tile_lanes((int)v);
         if (std::string(name) == "slab_global_ids") return cells.set_slab_global_ids((int)v);
+        if (std::string(name) == "gabriel_coefficient") return cells.set_gabriel_coefficient((float)v);
         if (std::string(name) == "renumber_now") return policy.renumber_now(cells);
         // Solution::keep_in_cube_order with every id-indexed array of the model (0 = off again)
         if (std::string(name) == "renumber_every") return policy.keep_in_cube_order(cells, (int)v);
@@ -631,8 +707,9 @@ Sim_base* make_sim(int n_max, int gs, float cs)
     return new S{n_max, gs, cs};
 }
 
-#define YA_MODEL(name, Pt, GRID, pw_int, pw_friction, Policy) \
-    Model { name, &make_sim<Sim<Pt, GRID, pw_int, pw_friction, Policy>> }
+// SOLVER: false / true = Tile_solver / Grid_solver (as before the third one), or GABRIEL
+#define YA_MODEL(name, Pt, SOLVER, pw_int, pw_friction, Policy) \
+    Model { name, &make_sim<Sim<Pt, SOLVER, pw_int, pw_friction, Policy>> }
 
 static const Model model_table[] = {
     // BASELINE configs 1 and 5: springs (examples/springs.cu)
@@ -672,6 +749,11 @@ static const Model model_table[] = {
     // BASELINE config 3: examples/branching.cu (7-float Cell, Turing kinetics, atomics)
     YA_MODEL("branching_grid", Cell, true, models::epi_turing_mes_noturing, friction_w_neighbour<Cell>, Branching),
     YA_MODEL("relu_cell_grid", Cell, true, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
+    // Gabriel_solver (solvers.cuh:505-644): relaxation and tests/test_solvers.cu's clipped spring on the
+    // Gabriel graph, and the relaxation stage of examples/growth_w_wall.cu (:36-63, :161-174: wall node 0)
+    YA_MODEL("relu_gabriel", float3, GABRIEL, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_MODEL("clipped_gabriel", float3, GABRIEL, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_MODEL("wall_gabriel", float3, GABRIEL, models::wall_relu_force, friction_on_background<float3>, Wall_gen),
     YA_MODEL_EXTRA
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);

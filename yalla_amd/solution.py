@@ -7,7 +7,8 @@ and n, `take_step(dt)` advances by one two-stage Heun step, `set_fixed*`
 select what is held fixed, `get_d_n()` reads the device-side count.  A model
 name selects the point type, the solver and the pairwise functor (C++ template
 arguments in the reference), e.g. "springs_grid" = Solution<float3,
-Grid_solver> stepping `spring`.
+Grid_solver> stepping `spring`; "relu_gabriel", "clipped_gabriel" and "wall_gabriel" step
+Gabriel_solver (set_param("gabriel_coefficient", c), default 0.8).
 """
 import ctypes as C
 
