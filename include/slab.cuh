@@ -22,23 +22,10 @@
 #include "yalla_hip.h"
 
 namespace ya {
-__global__ void k_slab_mean_from_total(const float* total, int n_floats, float* fix, int fix_mode)
-{
-    // ya::fix_from_total (solvers.cuh): the mean as sum * float(1. / float(n)), the reference's Pt / n
-    // arithmetic (dtypes.cuh:202-217; the cell count crosses the float all-reduce as two exact pieces),
-    // or the fixed point's value
-    const float3 f = fix_from_total(total, n_floats, fix_mode);
-    if (threadIdx.x == 0) {
-        fix[0] = f.x;
-        fix[1] = f.y;
-        fix[2] = f.z;
-    }
-}
 // Backend operations of the slab logic on the device: thin wrappers over the C ABI.
 struct Slab_device_ops {
     static constexpr bool device = true;
     using Stream = hipStream_t;
-    using Guard_band = ya::Guard_band;
     static constexpr int guard_slots = ya::GUARD_SLOTS;
     template<typename Pt>
     static bool has_generic_forces(const Generic_forces<Pt>& gen) { return !ya::is_no_gen_forces<Pt>(gen); }
@@ -132,19 +119,9 @@ struct Slab_device_ops {
     }
     static void read_ints(const void* d, int k, int* out) { YA_CHECK(ya_memcpy_d2h(out, d, (size_t)k * sizeof(int))); }
     static void write_int(void* d, int v) { YA_CHECK(ya_memcpy_h2d(d, &v, sizeof(int))); }
-    static void mean_from_total(const float* total, int n_floats, float* fix, int fix_mode)
-    {
-        k_slab_mean_from_total<<<1, 64>>>(total, n_floats, fix, fix_mode);
-    }
     // drift guard and fixed point (include/yalla_hip.h)
     static void copy_z(const void* X, size_t stride, int n, float* z) { YA_CHECK(ya_copy_component(X, stride, 2, n, z, nullptr)); }
     static void find_id(const int* ids, int n, int id, int* index) { YA_CHECK(ya_find_id(ids, n, id, index, nullptr)); }
-    static int max_abs_diff(const float* a, size_t a_stride, const float* b, size_t b_stride, int n, float lo_face,
-        float hi_face, float width, float* partial)
-    {
-        YA_CHECK(ya_max_abs_diff(a, a_stride, b, b_stride, n, lo_face, hi_face, width, partial, nullptr));
-        return ya_max_abs_diff_partials(n);
-    }
     static void guard_update(float* moved, int n_moved, float* pred, int n_pred, float limit, float lag, float* state)
     {
         YA_CHECK(ya_slab_guard_update(moved, n_moved, pred, n_pred, limit, lag, state, nullptr));

@@ -186,11 +186,10 @@ public:
         int msg_in[2] = {0, 0};      // rows the neighbour below / above sends per stage: ghosts[] unless this rank
                                      // could not keep its mirrored cells (-5), see unpack_halo_state
         bool halo_valid = false;     // false: ownership changed, the next step starts with rehalo()
-        bool raw_corrector = false;  // this step's stage 1 left d_dX raw (slab_update)
         char* send_dx[2] = {nullptr, nullptr};  // a stage's right-hand sides of those cells, P bytes each
         void *comm_stream = nullptr, *rhs_packed = nullptr, *rhs_landed = nullptr;  // device build: hipStream_t, 2 x hipEvent_t
         int *d_gid = nullptr, *d_gid_tmp = nullptr;
-        float* d_fix = nullptr;
+        float* d_fix = nullptr;  // host backend: the stage's fixed velocity (the device's update kernels work it out)
         // drift guard (see guard_between_stages): z of own and mirrored cells when the mirrored cells were
         // chosen, the per-workgroup maxima the update kernels leave, {moved, predicted, request, error}
         float *d_z_selected = nullptr, *d_moved_partial = nullptr, *d_pred_partial = nullptr, *d_guard = nullptr;
@@ -201,7 +200,6 @@ public:
                                        // selection after the vote (moved + 2 predicted; + 25 % for a pace that grows)
         void* votes = nullptr;         // Ops::Votes: the all-reduced votes on their way to the host
         bool votes_pending = false, migrate_requested = false;
-        bool votes_by_kernel = false;  // this stage's corrector stores the all-reduced votes on the host itself
         int* d_fix_index = nullptr;    // set_fixed(i) / set_fixed_xy(i): local index of cell i, or -1 (not this rank's)
         int failed = 0;                // sticky: this rank's first failure (it keeps stepping until every rank knows)
         long rehalos = 0, guard_requests = 0;  // statistics: selections of the mirrored cells / those the guard asked for
@@ -266,7 +264,7 @@ public:
         slab.d_ws = (int*)Ops::alloc(Ops::select_workspace_bytes(this->n_max));
         slab.d_gid = (int*)Ops::alloc(ints);
         slab.d_gid_tmp = (int*)Ops::alloc(ints);
-        slab.d_fix = (float*)Ops::alloc(32);  // stage 1's and stage 2's fixed velocity
+        slab.d_fix = (float*)Ops::alloc(16);
         slab.d_z_selected = (float*)Ops::alloc((size_t)this->n_max * sizeof(float));
         const size_t partials = (size_t)std::max(this->n_max / 256 + 2, 1024) * sizeof(float);
         slab.d_moved_partial = (float*)Ops::alloc(partials);
@@ -609,61 +607,39 @@ public:
     int slab_update(int stage, float dt, const float* d_total, bool has_gen)
     {
         if (!slab.on) return -3;
-        // (each stage's fixed velocity in a place of its own: the raw corrector needs both)
-        float* fix = slab.d_fix + (stage == 1 ? 0 : 4);
         const int mode = fix_mode(stage);
         const bool guard = slab.guard && slab.world > 1;
-        // the drift guard's maxima for the plain update kernels (d_X1 exists then)
-        auto guard_plain = [&]() {
-            if (!guard) return;
-            if (stage == 1)
-                slab.n_pred_partials = Ops::max_abs_diff(reinterpret_cast<const float*>(this->d_X1) + 2, P,
-                    reinterpret_cast<const float*>(this->d_X) + 2, P, slab.n_local, slab.z_lo, slab.z_hi, guard_band_width(),
-                    slab.d_pred_partial);
-            else
-                slab.n_moved_partials = Ops::max_abs_diff(reinterpret_cast<const float*>(this->d_X) + 2, P,
-                    slab.d_z_selected, sizeof(float), slab.n_local, slab.z_lo, slab.z_hi, guard_band_width(),
-                    slab.d_moved_partial);
-        };
-        slab.votes_by_kernel = false;
         if constexpr (!Ops::device) {
-        Ops::mean_from_total(d_total, sizeof(Pt) / sizeof(float), fix, mode);
-        this->stage_update(stage, slab.n_local, dt, fix);
-        guard_plain();
+        Ops::mean_from_total(d_total, sizeof(Pt) / sizeof(float), slab.d_fix, mode);
+        this->stage_update(stage, slab.n_local, dt, slab.d_fix);
+        if (!guard) return 0;
+        // the drift guard's maxima (d_X1 exists here)
+        if (stage == 1)
+            slab.n_pred_partials = Ops::max_abs_diff(reinterpret_cast<const float*>(this->d_X1) + 2, P,
+                reinterpret_cast<const float*>(this->d_X) + 2, P, slab.n_local, slab.z_lo, slab.z_hi, guard_band_width(),
+                slab.d_pred_partial);
+        else
+            slab.n_moved_partials = Ops::max_abs_diff(reinterpret_cast<const float*>(this->d_X) + 2, P,
+                slab.d_z_selected, sizeof(float), slab.n_local, slab.z_lo, slab.z_hi, guard_band_width(),
+                slab.d_moved_partial);
         } else {
-        // Without generic forces both updates are one launch each: the predictor of own and
-        // mirrored cells inside the cube-sorted copy (d_X1 is never written, d_dX stays raw),
-        // then the corrector that subtracts both fixed velocities itself -- the kernels of the
-        // undivided sorted-space step.  With generic forces (they read d_X1) the plain pair:
-        // euler_step over all local cells, the mirrored cells' d_X1 copied into the sorted copy.
-        // The two kernels take the all-reduced totals as they are and work the fixed velocity out
-        // themselves (the predictor leaves stage 1's in slab.d_fix for the corrector); they also
-        // leave the drift guard's per-workgroup maxima, and the corrector hands the all-reduced votes
-        // to the host.
-        typename Ops::Guard_band band;
-        band.lo_face = slab.z_lo;
-        band.hi_face = slab.z_hi;
-        band.width = guard_band_width();
-        if (stage == 1) {
-            slab.raw_corrector = !has_gen && this->stage1_update_in_sorted_copy(slab.n_local, dt, d_total, slab.d_fix,
-                                                 slab.n_own, mode, guard ? slab.d_pred_partial : nullptr, band);
-            if (slab.raw_corrector) {
-                slab.n_pred_partials = guard ? Ops::guard_slots : 0;
-            } else {
-                Ops::mean_from_total(d_total, sizeof(Pt) / sizeof(float), fix, mode);
-                this->stage_update(1, slab.n_local, dt, fix, slab.n_own);
-                guard_plain();
-            }
-        } else if (slab.raw_corrector) {
-            this->stage2_update_raw(slab.n_local, dt, slab.d_fix, d_total, mode, guard ? slab.d_z_selected : nullptr,
-                guard ? slab.d_moved_partial : nullptr, band, slab.world > 1 ? Ops::votes_target(slab.votes) : nullptr);
-            slab.n_moved_partials = guard ? Ops::guard_slots : 0;
-            slab.votes_by_kernel = slab.world > 1;
-        } else {
-            Ops::mean_from_total(d_total, sizeof(Pt) / sizeof(float), fix, mode);
-            this->stage_update(2, slab.n_local, dt, fix, slab.n_own);
-            guard_plain();
+        // The update kernels of the undivided step with the totals source: they take the all-reduced totals as
+        // they are and work the fixed velocity out themselves, the predictor moves own and mirrored cells in the
+        // cube-sorted copy (and in d_X1 for generic forces), and they leave the drift guard's per-workgroup
+        // maxima; the corrector hands the all-reduced votes to the host.
+        using Solver = Heun_solver<Pt, Grid_computer>;
+        typename Solver::Slab_outputs out;
+        out.band.lo_face = slab.z_lo;
+        out.band.hi_face = slab.z_hi;
+        out.band.width = guard_band_width();
+        if (guard && stage == 1) out.pred_partial = slab.d_pred_partial;
+        if (guard && stage == 2) {
+            out.z_selected = slab.d_z_selected;
+            out.moved_partial = slab.d_moved_partial;
         }
+        if (stage == 2 && slab.world > 1) out.votes_out = Ops::votes_target(slab.votes);
+        this->template stage_update<Solver::Fix::totals>(stage, slab.n_local, dt, {d_total, mode}, has_gen, slab.n_own, out);
+        (stage == 1 ? slab.n_pred_partials : slab.n_moved_partials) = guard ? Ops::guard_slots : 0;
         }
         return 0;
     }
@@ -896,9 +872,9 @@ public:
             if (stage == 1) guard_between_stages();
             if (slab.world > 1 && stage == 2) {
                 // the second all-reduce carried the drift guard's votes: they reach the host behind the
-                // stream (stored by the corrector kernel itself, or copied) and are collected when the
-                // next step begins
-                if (slab.votes_by_kernel)
+                // stream (stored by the corrector kernel itself on the device, copied on the host backend) and
+                // are collected when the next step begins
+                if constexpr (Ops::device)
                     Ops::votes_mark(slab.votes);
                 else
                     Ops::votes_begin(slab.votes, slab.d_sum + NW + 2);

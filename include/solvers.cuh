@@ -1796,88 +1796,12 @@ __global__ void make_fix(int mode, const float* __restrict__ d_mean,
     }
 }
 
-}  // namespace ya
-
-
-// 2nd order solver for the equation v = F + <v(t - dt)> for x, y, and z, where
-// <v> is the mean velocity of the neighbours weighted by the friction
-// coefficients; other variables in Pt follow dw/dt = F_w (solvers.cuh:109-144).
-// The fixed velocity is read from device memory instead of a kernel argument.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step(const int n, const float dt,
-    const Pt* __restrict__ d_X0, const float* __restrict__ d_fix, Pt* __restrict__ d_dX,
-    Pt* __restrict__ d_X)
-{
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i >= n) return;
-
-    Pt dX = d_dX[i];
-    dX.x -= d_fix[0];
-    dX.y -= d_fix[1];
-    dX.z -= d_fix[2];
-    d_dX[i] = dX;
-    d_X[i] = d_X0[i] + dX * dt;
-}
-
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step(const int n, const float dt,
-    const Pt* __restrict__ d_dX, const float* __restrict__ d_fix1, Pt* __restrict__ d_dX1,
-    Pt* __restrict__ d_X, float3* __restrict__ d_old_v)
-{
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i >= n) return;
-
-    Pt dX1 = d_dX1[i];
-    dX1.x -= d_fix1[0];
-    dX1.y -= d_fix1[1];
-    dX1.z -= d_fix1[2];
-    d_dX1[i] = dX1;
-    const Pt dX = d_dX[i];
-    Pt X = d_X[i];
-    X += (dX + dX1) * 0.5 * dt;
-    d_X[i] = X;
-    d_old_v[i] = float3{
-        (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
-}
-
-
-// The same two updates for the sorted-space pipeline of Grid_solver (no generic
-// forces): the predictor X1 = X0 + (dX - fix) dt is applied in place to the
-// cube-sorted copy of the cells, which then feeds the second grid build without
-// any gather; d_dX keeps the raw right-hand side and the corrector subtracts both
-// fixed velocities itself.  Statement for statement the arithmetic of
-// euler_step / heun_step above.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step_sorted(const int n, const float dt,
-    const float* __restrict__ d_fix, const Pt* __restrict__ d_dX_sorted,
-    ya::Entry<Pt>* __restrict__ d_sorted, const int n_active)
-{
-    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (s >= n) return;
-    if (d_sorted[s].id >= n_active) return;  // a ghost cell: moved by its owner
-
-    Pt dX = d_dX_sorted[s];
-    dX.x -= d_fix[0];
-    dX.y -= d_fix[1];
-    dX.z -= d_fix[2];
-    ya::Entry<Pt> e = d_sorted[s];
-    e.X = e.X + dX * dt;
-    d_sorted[s] = e;
-}
-
-// z-slab decomposition, no generic forces: own AND mirrored cells moved inside the sorted copy
-// in one pass.  A mirrored cell (id >= n_active) has no right-hand side in sorted order -- it
-// arrived by message as row id of d_dX -- and the sorted copy holds its X[id] bit for bit, so
-// X[id] + (dX[id] - fix) dt is computed here exactly as euler_step computes it.  d_dX stays raw
-// (heun_step_raw subtracts both fixed velocities), d_X1 is not written at all.
-// The fixed velocity is taken from the stage's ALL-REDUCED totals (ya_slab_pack on every rank,
-// summed): {sum[n_floats], count in two pieces, two votes, the fixed point's right-hand side}.
+// The fixed velocity from a z-slab stage's ALL-REDUCED totals (ya_slab_pack on every rank, summed):
+// {sum[n_floats], count in two pieces, two votes, the fixed point's right-hand side}.
 // fix_mode 0 (set_fixed()): fix = sum * float(1. / n), the reference's Pt / n arithmetic
 // (dtypes.cuh:202-217; n through binary32 as there); 1 (set_fixed(i)): the fixed point's value,
 // which only its owner put into the sum; 2 (set_fixed_xy(i), first stage): its x and y, the mean's z
-// (solvers.cuh:241-253).  Computed by every thread alike; thread 0 leaves it in d_fix_out for the
-// corrector.
-namespace ya {
+// (solvers.cuh:241-253).
 __device__ __forceinline__ float3 fix_from_total(const float* __restrict__ total, const int n_floats, const int fix_mode = 0)
 {
     const double n = (double)total[n_floats] + 4096. * (double)total[n_floats + 1];
@@ -1917,60 +1841,13 @@ __device__ __forceinline__ void block_max_to(float v, float* __restrict__ partia
         if (v > 0.f) atomicMax(reinterpret_cast<unsigned*>(partial) + (blockIdx.x % GUARD_SLOTS), __float_as_uint(v));
     }
 }
-}  // namespace ya
 
-// (pred_partial, may be NULL: per workgroup the largest |z moved by this predictor| -- the drift
-// guard of the decomposition, include/slab_logic.inc)
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step_sorted_mirrored(const int n, const float dt,
-    const float* __restrict__ d_total, float* __restrict__ d_fix_out, const Pt* __restrict__ d_dX_sorted,
-    const Pt* __restrict__ d_dX, ya::Entry<Pt>* __restrict__ d_sorted, const int n_active, const int fix_mode,
-    float* __restrict__ pred_partial, const ya::Guard_band band)
-{
-    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    const float3 fix = ya::fix_from_total(d_total, sizeof(Pt) / sizeof(float), fix_mode);
-    if (s == 0) {
-        d_fix_out[0] = fix.x;
-        d_fix_out[1] = fix.y;
-        d_fix_out[2] = fix.z;
-    }
-    float moved = 0.f;
-    if (s < n) {
-        ya::Entry<Pt> e = d_sorted[s];
-        Pt dX = e.id >= n_active ? d_dX[e.id] : d_dX_sorted[s];
-        dX.x -= fix.x;
-        dX.y -= fix.y;
-        dX.z -= fix.z;
-        const float z0 = e.X.z;
-        e.X = e.X + dX * dt;
-        moved = fabsf(e.X.z - z0) * band.weight(z0);
-        d_sorted[s] = e;
-    }
-    if (pred_partial) ya::block_max_to(moved, pred_partial);
-}
-
-// z-slab decomposition: the ghost cells' predictor positions arrive from the slab
-// neighbours in original order (d_X1[id], id >= n_active) and are put into the sorted
-// copy here; the own cells were moved by euler_step_sorted.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void ghosts_into_sorted(const int n,
-    const int n_active, const Pt* __restrict__ d_X1, ya::Entry<Pt>* __restrict__ d_sorted)
-{
-    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (s >= n) return;
-    const int id = d_sorted[s].id;
-    if (id >= n_active) d_sorted[s].X = d_X1[id];
-}
-
-// Round 5: the update kernels of the sorted-space step fold the reduction's partial sums THEMSELVES.
-// ya_reduce_mean was two launches -- B per-block partial sums, then one workgroup that folds them
-// and scales by 1 / n -- and the second one is a whole launch (4-5 us, four times per step at any
-// system size) for a few hundred additions.  Every workgroup of the kernel that needs the mean now
-// repeats that fold from the partials (<= 1024 x 3 floats, L2 hits): the same additions in the same
-// tree (lane t takes partials t, t + 256, ...; lanes folded by halving), the same `sum * float(1. / n)`
+// The mean of a stage's right-hand sides folded by the update kernel itself from the reduction's partial sums:
+// ya_reduce_mean's second launch (4-5 us, four times per step at any system size) for a few hundred additions.
+// Every workgroup repeats that fold from the partials (<= 1024 x 3 floats, L2 hits): the same additions in the
+// same tree (lane t takes partials t, t + 256, ...; lanes folded by halving), the same `sum * float(1. / n)`
 // (dtypes.cuh:202-217), hence the same bits as ya_reduce_mean leaves in d_mean -- only x, y, z, all the
 // update kernels subtract (solvers.cuh:113-144).
-namespace ya {
 template<int NF>
 __device__ __forceinline__ float3 fixed_velocity_from_partials(const float* __restrict__ partials, const int n_partials,
     const int n)
@@ -2009,183 +1886,127 @@ __device__ __forceinline__ float3 fixed_velocity_from_partials(const float* __re
     const float inv = (float)(1. / (double)(float)n);  // Pt / n == Pt * float(1. / float(n))
     return float3{sh[0] * inv, sh[UPDATE_BLOCK] * inv, sh[2 * UPDATE_BLOCK] * inv};
 }
+
+// Where an update kernel takes a stage's fixed velocity from (solvers.cuh:241-253,265-272).  A template
+// parameter: each kernel instance holds the code of its own source only.
+//   memory    src[0..2], left by ya_reduce_mean (+ make_fix)
+//   partials  src = ya_reduce_partials' `arg` partial sums, folded here (fixed_velocity_from_partials)
+//   totals    src = a z-slab stage's all-reduced totals, arg = fix_mode (fix_from_total)
+enum class Fix_src { memory, partials, totals };
+struct Fix_args {
+    const float* src = nullptr;
+    int arg = 0;
+    float* out = nullptr;  // predictor, may be NULL: its thread 0 leaves the velocity here for the corrector
+};
+// Every thread of the workgroup calls it, before any early return: the partials fold has barriers.
+template<Fix_src S, typename Pt>
+__device__ __forceinline__ float3 resolve_fix(const Fix_args& f, const int n)
+{
+    if constexpr (S == Fix_src::memory)
+        return float3{f.src[0], f.src[1], f.src[2]};
+    else if constexpr (S == Fix_src::partials)
+        return fixed_velocity_from_partials<N_floats<Pt>::value>(f.src, f.arg, n);
+    else
+        return fix_from_total(f.src, N_floats<Pt>::value, f.arg);
+}
+template<typename Pt>
+__device__ __forceinline__ Pt minus_fix(Pt dX, const float3 fix)
+{
+    dX.x -= fix.x;
+    dX.y -= fix.y;
+    dX.z -= fix.z;
+    return dX;
+}
 }  // namespace ya
 
-// euler_step_sorted with the fixed velocity = the mean of the stage's right-hand sides, folded here from
-// the reduction's partial sums; workgroup 0 leaves it in d_fix_out for the corrector.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step_sorted_folding(const int n, const float dt,
-    const float* __restrict__ partials, const int n_partials, float* __restrict__ d_fix_out,
-    const Pt* __restrict__ d_dX_sorted, ya::Entry<Pt>* __restrict__ d_sorted)
-{
-    const float3 fix = ya::fixed_velocity_from_partials<ya::N_floats<Pt>::value>(partials, n_partials, n);
-    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (s == 0) {
-        d_fix_out[0] = fix.x;
-        d_fix_out[1] = fix.y;
-        d_fix_out[2] = fix.z;
-    }
-    if (s >= n) return;
-    Pt dX = d_dX_sorted[s];
-    dX.x -= fix.x;
-    dX.y -= fix.y;
-    dX.z -= fix.z;
-    ya::Entry<Pt> e = d_sorted[s];
-    e.X = e.X + dX * dt;
-    d_sorted[s] = e;
-}
 
-// euler_step / heun_step (the pipeline through d_X / d_X1: generic forces, Tile_solver, Gabriel_solver) with the
-// fixed velocity folded here; euler_step_folding leaves it in d_fix_out.
-// (d_sorted, may be NULL: the cube-sorted copy's predictor in the same launch, euler_step_sorted's statements for
-// slot i; d_zero, may be NULL: the NEXT stage's right-hand side array, whose row i is dead by now and is left
-// zeroed for the generic forces that will add to it -- a memset launch less)
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step_folding(const int n, const float dt,
-    const Pt* __restrict__ d_X0, const float* __restrict__ partials, const int n_partials, float* __restrict__ d_fix_out,
-    Pt* __restrict__ d_dX, Pt* __restrict__ d_X, const Pt* __restrict__ d_dX_sorted, ya::Entry<Pt>* __restrict__ d_sorted,
-    Pt* __restrict__ d_zero)
+// 2nd order solver for the equation v = F + <v(t - dt)> for x, y, and z, where
+// <v> is the mean velocity of the neighbours weighted by the friction
+// coefficients; other variables in Pt follow dw/dt = F_w (solvers.cuh:109-144).
+// The right-hand sides stay raw: the corrector subtracts both stages' fixed velocities.
+//
+// The predictor X1 = X0 + (dX - fix) dt (solvers.cuh:113-125) on every copy of the cells that is given, in one
+// launch.  All pointers but d_dX may be NULL:
+//   d_X0 -> d_X1  the cells in id order (what the generic forces are handed, and stage 2's input without a
+//                 sorted copy)
+//   d_sorted      the cube-sorted copy of Grid_solver, moved in place, from which stage 2's grid build starts:
+//                 a cell's right-hand side is d_dX_sorted[slot], or (totals source) d_dX[id] for a z-slab's
+//                 mirrored cell (id >= n_active), which arrived by message in id order; the copy holds X[id] bit
+//                 for bit, so both give the bits of d_X1[id]
+//   d_zero        the next stage's right-hand side array, whose row i is dead by now: left zeroed for the
+//                 generic forces that will add to it (a memset launch less)
+//   pred_partial  (totals source) the largest |z moved| weighted by band, the drift guard of a z-slab
+//                 (ya::block_max_to)
+template<typename Pt, ya::Fix_src S>
+__global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step(const int n, const float dt, const ya::Fix_args fix_args,
+    const Pt* __restrict__ d_dX, const Pt* __restrict__ d_X0, Pt* __restrict__ d_X1, const Pt* __restrict__ d_dX_sorted,
+    ya::Entry<Pt>* __restrict__ d_sorted, const int n_active, Pt* __restrict__ d_zero, float* __restrict__ pred_partial,
+    const ya::Guard_band band)
 {
-    const float3 fix = ya::fixed_velocity_from_partials<ya::N_floats<Pt>::value>(partials, n_partials, n);
+    const float3 fix = ya::resolve_fix<S, Pt>(fix_args, n);
     const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i == 0) {
-        d_fix_out[0] = fix.x;
-        d_fix_out[1] = fix.y;
-        d_fix_out[2] = fix.z;
-    }
-    if (i >= n) return;
-
-    if (d_sorted) {
-        Pt dXs = d_dX_sorted[i];
-        dXs.x -= fix.x;
-        dXs.y -= fix.y;
-        dXs.z -= fix.z;
-        ya::Entry<Pt> e = d_sorted[i];
-        e.X = e.X + dXs * dt;
-        d_sorted[i] = e;
-    }
-    Pt dX = d_dX[i];
-    dX.x -= fix.x;
-    dX.y -= fix.y;
-    dX.z -= fix.z;
-    d_dX[i] = dX;
-    d_X[i] = d_X0[i] + dX * dt;
-    if (d_zero) d_zero[i] = ya::zero<Pt>();
-}
-
-// (zero_dX: row i of d_dX, dead after this, is left zeroed for the next step's generic forces)
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_folding(const int n, const float dt,
-    Pt* __restrict__ d_dX, const float* __restrict__ partials1, const int n_partials1, Pt* __restrict__ d_dX1,
-    Pt* __restrict__ d_X, float3* __restrict__ d_old_v, const bool zero_dX)
-{
-    const float3 fix1 = ya::fixed_velocity_from_partials<ya::N_floats<Pt>::value>(partials1, n_partials1, n);
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i >= n) return;
-
-    Pt dX1 = d_dX1[i];
-    dX1.x -= fix1.x;
-    dX1.y -= fix1.y;
-    dX1.z -= fix1.z;
-    d_dX1[i] = dX1;
-    const Pt dX = d_dX[i];
-    Pt X = d_X[i];
-    X += (dX + dX1) * 0.5 * dt;
-    d_X[i] = X;
-    d_old_v[i] = float3{
-        (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
-    if (zero_dX) d_dX[i] = ya::zero<Pt>();
-}
-
-// heun_step_raw with the second stage's fixed velocity folded from its partial sums.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_raw_folding(const int n, const float dt,
-    const Pt* __restrict__ d_dX, const float* __restrict__ d_fix, const Pt* __restrict__ d_dX1,
-    const float* __restrict__ partials1, const int n_partials1, Pt* __restrict__ d_X, float3* __restrict__ d_old_v)
-{
-    const float3 fix1 = ya::fixed_velocity_from_partials<ya::N_floats<Pt>::value>(partials1, n_partials1, n);
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i >= n) return;
-
-    Pt dX = d_dX[i];
-    dX.x -= d_fix[0];
-    dX.y -= d_fix[1];
-    dX.z -= d_fix[2];
-    Pt dX1 = d_dX1[i];
-    dX1.x -= fix1.x;
-    dX1.y -= fix1.y;
-    dX1.z -= fix1.z;
-    Pt X = d_X[i];
-    X += (dX + dX1) * 0.5 * dt;
-    d_X[i] = X;
-    d_old_v[i] = float3{
-        (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
-}
-
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_raw(const int n, const float dt,
-    const Pt* __restrict__ d_dX, const float* __restrict__ d_fix, const Pt* __restrict__ d_dX1,
-    const float* __restrict__ d_fix1, Pt* __restrict__ d_X, float3* __restrict__ d_old_v)
-{
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i >= n) return;
-
-    Pt dX = d_dX[i];
-    dX.x -= d_fix[0];
-    dX.y -= d_fix[1];
-    dX.z -= d_fix[2];
-    Pt dX1 = d_dX1[i];
-    dX1.x -= d_fix1[0];
-    dX1.y -= d_fix1[1];
-    dX1.z -= d_fix1[2];
-    Pt X = d_X[i];
-    X += (dX + dX1) * 0.5 * dt;
-    d_X[i] = X;
-    d_old_v[i] = float3{
-        (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
-}
-
-
-// heun_step_raw with the second stage's fixed velocity taken from the stage's all-reduced totals
-// (z-slab decomposition; see euler_step_sorted_mirrored).  z_selected / moved_partial (may be NULL):
-// per workgroup the largest |z - z when the mirrored cells were chosen| after this update, weighted
-// by the band.  votes_out (may be NULL; host memory the device can write): the all-reduced votes of
-// this stage, d_total1[n_floats + 2 .. + 3], for the host to collect when the next step begins.
-template<typename Pt>
-__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_raw_total(const int n, const float dt,
-    const Pt* __restrict__ d_dX, const float* __restrict__ d_fix, const Pt* __restrict__ d_dX1,
-    const float* __restrict__ d_total1, Pt* __restrict__ d_X, float3* __restrict__ d_old_v, const int fix_mode,
-    const float* __restrict__ z_selected, float* __restrict__ moved_partial, const ya::Guard_band band,
-    float* __restrict__ votes_out)
-{
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (votes_out && i == 0) {
-        votes_out[0] = d_total1[sizeof(Pt) / sizeof(float) + 2];
-        votes_out[1] = d_total1[sizeof(Pt) / sizeof(float) + 3];
+    if (i == 0 && fix_args.out) {
+        fix_args.out[0] = fix.x;
+        fix_args.out[1] = fix.y;
+        fix_args.out[2] = fix.z;
     }
     float moved = 0.f;
     if (i < n) {
-        const float3 fix1 = ya::fix_from_total(d_total1, sizeof(Pt) / sizeof(float), fix_mode);
+        if (d_X1) {
+            const Pt X0 = d_X0[i];
+            const Pt X1 = X0 + ya::minus_fix(d_dX[i], fix) * dt;
+            d_X1[i] = X1;
+            moved = fabsf(X1.z - X0.z) * band.weight(X0.z);
+        }
+        if (d_sorted) {
+            ya::Entry<Pt> e = d_sorted[i];
+            Pt dX = d_dX_sorted[i];
+            if constexpr (S == ya::Fix_src::totals)
+                if (e.id >= n_active) dX = d_dX[e.id];
+            const float z0 = e.X.z;
+            e.X = e.X + ya::minus_fix(dX, fix) * dt;
+            d_sorted[i] = e;
+            moved = fabsf(e.X.z - z0) * band.weight(z0);
+        }
+        if (d_zero) d_zero[i] = ya::zero<Pt>();
+    }
+    if constexpr (S == ya::Fix_src::totals)
+        if (pred_partial) ya::block_max_to(moved, pred_partial);
+}
 
-        Pt dX = d_dX[i];
-        dX.x -= d_fix[0];
-        dX.y -= d_fix[1];
-        dX.z -= d_fix[2];
-        Pt dX1 = d_dX1[i];
-        dX1.x -= fix1.x;
-        dX1.y -= fix1.y;
-        dX1.z -= fix1.z;
+// The corrector X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v (solvers.cuh:127-144): fix is the first stage's
+// velocity as the predictor left it (d_fix), fix1 comes from S.  (zero_dX: row i of d_dX, dead after this, is left
+// zeroed for the next step's generic forces.  Totals source: z_selected / moved_partial, may be NULL: the largest
+// |z - z when the mirrored cells were chosen| weighted by band, the drift guard; votes_out, may be NULL (host memory
+// the device can write): the all-reduced votes of this stage, totals[n_floats + 2 .. + 3].)
+template<typename Pt, ya::Fix_src S>
+__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step(const int n, const float dt, const float* __restrict__ d_fix,
+    const ya::Fix_args fix1_args, Pt* __restrict__ d_dX, const Pt* __restrict__ d_dX1, Pt* __restrict__ d_X,
+    float3* __restrict__ d_old_v, const bool zero_dX, const float* __restrict__ z_selected,
+    float* __restrict__ moved_partial, const ya::Guard_band band, float* __restrict__ votes_out)
+{
+    const float3 fix1 = ya::resolve_fix<S, Pt>(fix1_args, n);
+    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
+    float moved = 0.f;
+    if (i < n) {
+        const Pt dX_raw = d_dX[i];
+        if (zero_dX) d_dX[i] = ya::zero<Pt>();  // (straight after the load: no address kept live)
+        const Pt dX = ya::minus_fix(dX_raw, float3{d_fix[0], d_fix[1], d_fix[2]});
+        const Pt dX1 = ya::minus_fix(d_dX1[i], fix1);
         Pt X = d_X[i];
         X += (dX + dX1) * 0.5 * dt;
         d_X[i] = X;
         d_old_v[i] = float3{
             (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
-        if (z_selected) {
-            const float z0 = z_selected[i];
-            moved = fabsf(X.z - z0) * band.weight(z0);
-        }
+        if (z_selected) moved = fabsf(X.z - z_selected[i]) * band.weight(z_selected[i]);
     }
-    if (moved_partial) ya::block_max_to(moved, moved_partial);
+    if constexpr (S == ya::Fix_src::totals) {
+        if (votes_out && i == 0) {
+            votes_out[0] = fix1_args.src[ya::N_floats<Pt>::value + 2];
+            votes_out[1] = fix1_args.src[ya::N_floats<Pt>::value + 3];
+        }
+        if (moved_partial) ya::block_max_to(moved, moved_partial);
+    }
 }
 
 
@@ -2476,17 +2297,17 @@ protected:
     int* d_n;
     float *d_mean, *d_fix, *d_mean_first, *d_fix_first, *d_workspace;
     ya_n_reader* n_reader = nullptr;
-    int sorted_stage_cells = -1;  // stage API: cells in the sorted copy stage 2 may start from
-    bool mirrored_in_sorted_copy = false;  // ... and the mirrored cells' predictor is in it already
-    // rows of d_dX / d_dX1 an update kernel left zeroed (stage_update_folding).  INVARIANT: every writer of those two
-    // arrays goes through stage_rhs / sorted_step (which reset the promise) -- the arrays are protected members and
-    // no accessor hands them out; a new path that writes them must reset rhs_zeroed as well.
+    int sorted_stage_cells = -1;  // cells in the sorted copy stage 1 kept: stage_update(1) moves it, stage 2 starts from it
+    const float* stage1_fix = nullptr;  // where stage_update(1) left the first stage's fixed velocity for the corrector
+    // rows of d_dX / d_dX1 an update kernel left zeroed (stage_update).  INVARIANT: every writer of those two arrays
+    // goes through stage_rhs (which resets the promise) -- the arrays are protected members and no accessor hands
+    // them out; a new path that writes them must reset rhs_zeroed as well.
     int rhs_zeroed[2] = {0, 0};
     std::function<void()> keep_order;  // keep_in_cube_order: renumber(the registered arrays)
     int keep_order_every = 0, keep_order_wait = 0;
     bool fix_com = true;
     bool fix_com_z = false;
-    // sorted-space step with set_fixed(): the update kernels fold the reductions' partial sums themselves
+    // set_fixed(): the update kernels fold the reductions' partial sums themselves
     // (ya::fixed_velocity_from_partials; false = ya_reduce_mean's second launch, A/B)
     bool fold_in_update = true;
     int fix_point = 0;
@@ -2538,7 +2359,8 @@ protected:
             n_ids, links.d_n, n, new_id, reinterpret_cast<int*>(links.d_link));
     }
 
-    // The velocity subtracted from dX.xyz for this stage, left in device memory.
+    // The velocity subtracted from dX.xyz for this stage, left in device memory (first: stage 1's, which the
+    // corrector reads after the second stage's reduction).
     const float* fix_velocity(int n, Pt* d_rhs, bool mean, bool point_xy, bool first = false)
     {
         float* mean_out = first ? d_mean_first : d_mean;
@@ -2553,10 +2375,10 @@ protected:
         return fix_out;
     }
 
-    // The three pieces of a stage (stage 1 works on d_X -> d_dX, stage 2 on
-    // d_X1 -> d_dX1).  take_step composes them; a z-slab decomposition calls
-    // them one by one with a ghost exchange and an all-reduce in between
-    // (n = own + ghost cells, n_active = own cells).
+    // The pieces of a stage -- forces, then the source of the fixed velocity, then the update (stage 1 works on
+    // d_X -> d_dX, stage 2 on d_X1 -> d_dX1).  take_step composes them (heun_stages); a z-slab decomposition
+    // calls them one by one with a ghost exchange and an all-reduce in between (n = own + ghost cells,
+    // n_active = own cells).
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void stage_rhs(int stage, int n, int n_active, Generic_forces<Pt>& gen_forces)
     {
@@ -2564,28 +2386,21 @@ protected:
         Pt* d_rhs = stage == 1 ? d_dX : d_dX1;
         const bool has_gen = !ya::is_no_gen_forces<Pt>(gen_forces);
         if (has_gen) {
-            // (the update kernel before this stage may have left the rows zeroed already: stage_update_folding)
+            // (the update kernel before this stage may have left the rows zeroed already: stage_update)
             if (rhs_zeroed[stage - 1] < n) YA_CHECK(ya_memset_async(d_rhs, 0, (size_t)n * sizeof(Pt), nullptr));
             gen_forces(n, d_in, d_rhs);
         }
         rhs_zeroed[stage - 1] = 0;  // the force kernel writes it next
         if (stage == 2 && sorted_stage_cells == n) {
-            // sorted-space second stage (see take_step): the own cells were moved by
-            // stage_update(1), the ghost cells' new positions are in d_X1 (which the
-            // generic forces above were given, as the reference does)
+            // the second stage starts from the sorted copy stage_update(1) moved, mirrored cells included (the
+            // generic forces above were given d_X1, as the reference does)
             sorted_stage_cells = -1;
-            if (!mirrored_in_sorted_copy) Computer<Pt>::ghosts_in_sorted_space(n, n_active, d_X1);
-            mirrored_in_sorted_copy = false;
-            Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(
-                n, d_dX1, n_active, has_gen);
+            Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(n, d_dX1, n_active, has_gen);
             return;
         }
-        sorted_stage_cells = -1;
-        mirrored_in_sorted_copy = false;
         const bool keep_sorted = stage == 1 && Computer<Pt>::use_sorted_pipeline();
-        Computer<Pt>::template pwints<pw_int, pw_friction>(
-            n, d_in, d_old_v, d_rhs, has_gen, n_active, keep_sorted);
-        if (keep_sorted) sorted_stage_cells = n;
+        Computer<Pt>::template pwints<pw_int, pw_friction>(n, d_in, d_old_v, d_rhs, has_gen, n_active, keep_sorted);
+        sorted_stage_cells = keep_sorted ? n : -1;
     }
     // sum and mean of the stage's right-hand side over the first n points, left on
     // the device as {mean[n_floats], sum[n_floats]}
@@ -2595,71 +2410,42 @@ protected:
             stage == 1 ? d_dX : d_dX1, n_floats, n, d_mean, d_workspace, nullptr));
         return d_mean;
     }
-    // n_sorted_active: the cells moved inside the cube-sorted copy by their sorted right-hand
-    // sides (a z-slab moves its own cells there; mirrored cells enter the copy from d_X1)
-    void stage_update(int stage, int n, float dt, const float* d_fix_velocity, int n_sorted_active = -1)
+    // What the update kernels leave for a z-slab (totals source; each may be NULL): the drift guard's maxima,
+    // ya::GUARD_SLOTS floats each (zeroed by the reduction that reads them), and the all-reduced votes
+    // (see heun_step)
+    struct Slab_outputs {
+        float* pred_partial = nullptr;      // stage 1
+        const float* z_selected = nullptr;  // stage 2
+        float* moved_partial = nullptr;
+        float* votes_out = nullptr;
+        ya::Guard_band band;
+    };
+    using Fix = ya::Fix_src;
+    // The update of a stage, one launch, with the fixed velocity from S.  The right-hand sides stay raw; stage 1
+    // leaves its velocity for the corrector.  Stage 1 moves the sorted copy that stage_rhs kept, and writes d_X1
+    // only where it is read: by the generic forces, or by stage 2 without a sorted copy.  With generic forces
+    // the kernels leave the right-hand side array of the NEXT stage zeroed -- d_dX1 after the predictor, d_dX
+    // after the corrector: both dead by then -- so that the memset in front of the generic forces
+    // (solvers.cuh:232,258 `thrust::fill`) need not be launched (rhs_zeroed: rows known to be zero).
+    template<ya::Fix_src S>
+    void stage_update(int stage, int n, float dt, ya::Fix_args fix, bool has_gen, int n_active,
+        const Slab_outputs& slab_out = Slab_outputs{})
     {
         const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
         if (stage == 1) {
-            // before euler_step: it replaces d_dX by d_dX - fix, the sorted copy is raw
-            if (sorted_stage_cells >= 0)
-                Computer<Pt>::predictor_in_sorted_space(
-                    sorted_stage_cells, dt, d_fix_velocity, n_sorted_active >= 0 ? n_sorted_active : n);
-            euler_step<<<blocks, ya::UPDATE_BLOCK>>>(n, dt, d_X, d_fix_velocity, d_dX, d_X1);
-        } else
-            heun_step<<<blocks, ya::UPDATE_BLOCK>>>(
-                n, dt, d_dX, d_fix_velocity, d_dX1, d_X, d_old_v);
-    }
-
-    // stage_update for set_fixed() (the default) with the fixed velocity folded by the update kernels themselves
-    // from the stage's partial sums (two launches fewer per step, the same bits: see
-    // ya::fixed_velocity_from_partials).  The sorted copy's predictor runs first and leaves the velocity for
-    // euler_step; without a sorted copy (Tile_solver, Gabriel_solver) euler_step_folding does both.
-    // With generic forces (`zeroing`) the same kernels leave the right-hand side array of the NEXT stage zeroed --
-    // d_dX1 after the predictor, d_dX after the corrector: both dead by then -- so that the memset in front of the
-    // generic forces (solvers.cuh:232,258 `thrust::fill`) need not be launched (rhs_zeroed: rows known to be zero).
-    void stage_update_folding(int stage, int n, float dt, bool zeroing)
-    {
-        const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
-        int n_partials = 0;
-        YA_CHECK(ya_reduce_partials(stage == 1 ? d_dX : d_dX1, n_floats, n, d_workspace, &n_partials, nullptr));
-        if (stage == 1) {
-            const bool with_sorted = sorted_stage_cells == n;
-            if (!with_sorted) sorted_stage_cells = -1;
-            euler_step_folding<<<blocks, ya::UPDATE_BLOCK>>>(n, dt, d_X, d_workspace, n_partials, d_mean_first, d_dX, d_X1,
-                with_sorted ? Computer<Pt>::sorted_rhs() : nullptr, with_sorted ? Computer<Pt>::sorted_cells() : nullptr,
-                zeroing ? d_dX1 : nullptr);
-            rhs_zeroed[1] = zeroing ? n : 0;
+            const bool in_sorted = sorted_stage_cells == n;
+            fix.out = S == Fix::memory ? nullptr : d_mean_first;
+            stage1_fix = S == Fix::memory ? fix.src : d_mean_first;
+            euler_step<Pt, S><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, fix, d_dX, d_X,
+                has_gen || !in_sorted ? d_X1 : nullptr, Computer<Pt>::sorted_rhs(),
+                in_sorted ? Computer<Pt>::sorted_cells() : nullptr, n_active, has_gen ? d_dX1 : nullptr,
+                slab_out.pred_partial, slab_out.band);
+            rhs_zeroed[1] = has_gen ? n : 0;
         } else {
-            heun_step_folding<<<blocks, ya::UPDATE_BLOCK>>>(n, dt, d_dX, d_workspace, n_partials, d_dX1, d_X, d_old_v, zeroing);
-            rhs_zeroed[0] = zeroing ? n : 0;
+            heun_step<Pt, S><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, stage1_fix, fix, d_dX, d_dX1, d_X,
+                d_old_v, has_gen, slab_out.z_selected, slab_out.moved_partial, slab_out.band, slab_out.votes_out);
+            rhs_zeroed[0] = has_gen ? n : 0;
         }
-    }
-
-    // The two updates of a z-slab's step without generic forces: stage 1 entirely inside the
-    // sorted copy (own and mirrored cells, one launch; d_dX stays raw, d_X1 is not written), stage 2
-    // with both fixed velocities subtracted in the corrector.  Returns false if stage 1 left no
-    // sorted copy to work in (a solver without the sorted pipeline): the caller then uses
-    // stage_update.
-    // (d_total: the stage's all-reduced {sum, count pieces}; stage 1 leaves its fixed velocity in
-    // d_fix_out, stage 2 reads it from there)
-    // (fix_mode: ya::fix_from_total; pred_partial / z_selected + moved_partial: the drift guard's
-    // maxima, ya::GUARD_SLOTS floats each (zeroed by the reduction that reads them), or NULL;
-    // votes_out: see heun_step_raw_total)
-    bool stage1_update_in_sorted_copy(int n, float dt, const float* d_total, float* d_fix_out, int n_active,
-        int fix_mode = 0, float* pred_partial = nullptr, const ya::Guard_band band = ya::Guard_band{})
-    {
-        if (sorted_stage_cells != n) return false;
-        Computer<Pt>::predictor_in_sorted_space_mirrored(n, dt, d_total, d_fix_out, n_active, d_dX, fix_mode, pred_partial, band);
-        mirrored_in_sorted_copy = true;
-        return true;
-    }
-    void stage2_update_raw(int n, float dt, const float* d_fix_stage1, const float* d_total_stage2, int fix_mode = 0,
-        const float* z_selected = nullptr, float* moved_partial = nullptr, const ya::Guard_band band = ya::Guard_band{},
-        float* votes_out = nullptr)
-    {
-        heun_step_raw_total<<<(n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK, ya::UPDATE_BLOCK>>>(
-            n, dt, d_dX, d_fix_stage1, d_dX1, d_total_stage2, d_X, d_old_v, fix_mode, z_selected, moved_partial, band, votes_out);
     }
     // what a rank puts into a stage's all-reduce (ya_slab_pack): the sum over its first n points and
     // their count, its two votes (the drift guard brought up to date in the same kernel if
@@ -2680,34 +2466,28 @@ protected:
             d_fix_index, nullptr));
     }
 
-    // Sorted-space pipeline (Grid_solver without generic forces): the predictor lives in
-    // the cube-sorted copy of the cells, so the second grid build gathers nothing and
-    // d_X1 is never materialised.  Same arithmetic, same results.
+    // One step of n cells: per stage the forces, the fixed velocity, the update.  Without generic forces on
+    // Grid_solver (the headline path, and the step a graph captures) the predictor lives in the cube-sorted copy
+    // of the cells, so the second grid build gathers nothing and d_X1 is never materialised.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void sorted_step(const int n, const float dt)
+    void heun_stages(const int n, const float dt, Generic_forces<Pt>& gen_forces)
     {
-        const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
-        rhs_zeroed[0] = rhs_zeroed[1] = 0;  // both right-hand side arrays are written here
-        Computer<Pt>::template pwints<pw_int, pw_friction>(n, d_X, d_old_v, d_dX, false, n, true);
-        if (fix_com and !fix_com_z and fold_in_update) {
-            // set_fixed() (the default): both fixed velocities are means, folded by the update kernels
-            // themselves from the reductions' partial sums (two launches fewer; same bits)
-            int n_partials = 0;
-            YA_CHECK(ya_reduce_partials(d_dX, n_floats, n, d_workspace, &n_partials, this->stream));
-            Computer<Pt>::predictor_in_sorted_space_folding(n, dt, d_workspace, n_partials, d_mean_first);
-            Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(n, d_dX1, n, false);
-            YA_CHECK(ya_reduce_partials(d_dX1, n_floats, n, d_workspace, &n_partials, this->stream));
-            heun_step_raw_folding<<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(
-                n, dt, d_dX, d_mean_first, d_dX1, d_workspace, n_partials, d_X, d_old_v);
-            return;
+        const bool has_gen = !ya::is_no_gen_forces<Pt>(gen_forces);
+        for (int stage = 1; stage <= 2; stage++) {
+            stage_rhs<pw_int, pw_friction>(stage, n, n, gen_forces);
+            Pt* d_rhs = stage == 1 ? d_dX : d_dX1;
+            if (fix_com and !fix_com_z and fold_in_update) {
+                // set_fixed() (the default): the mean, folded by the update kernel from the reduction's partial
+                // sums (ya::fixed_velocity_from_partials: a launch fewer per stage, the same bits)
+                int n_partials = 0;
+                YA_CHECK(ya_reduce_partials(d_rhs, n_floats, n, d_workspace, &n_partials, this->stream));
+                stage_update<Fix::partials>(stage, n, dt, {d_workspace, n_partials}, has_gen, n);
+            } else {
+                // set_fixed_xy(i) holds x and y in the first stage only (solvers.cuh:241-253, 265-272)
+                const bool xy = stage == 1 && fix_com_z;
+                stage_update<Fix::memory>(stage, n, dt, {fix_velocity(n, d_rhs, fix_com or xy, xy, stage == 1)}, has_gen, n);
+            }
         }
-        // this stage's fixed velocity has to outlive the next reduction
-        const float* fix = fix_velocity(n, d_dX, fix_com or fix_com_z, fix_com_z, true);
-        Computer<Pt>::predictor_in_sorted_space(n, dt, fix, n);
-        Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(n, d_dX1, n, false);
-        const float* fix1 = fix_velocity(n, d_dX1, fix_com, false);
-        heun_step_raw<<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(
-            n, dt, d_dX, fix, d_dX1, fix1, d_X, d_old_v);
     }
 
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
@@ -2753,7 +2533,7 @@ protected:
                     YA_CHECK((int)hipStreamCreateWithFlags(&capture_stream, hipStreamNonBlocking));
                 YA_CHECK((int)hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal));
                 this->stream = capture_stream;
-                sorted_step<pw_int, pw_friction>(n, dt);
+                heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
                 this->stream = nullptr;
                 hipGraph_t graph = nullptr;
                 YA_CHECK((int)hipStreamEndCapture(capture_stream, &graph));
@@ -2764,7 +2544,7 @@ protected:
                 return;
             }
             last_key = key;
-            sorted_step<pw_int, pw_friction>(n, dt);
+            heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
             return;
         }
         if (Computer<Pt>::use_sorted_pipeline()) {
@@ -2788,28 +2568,8 @@ protected:
             return;
         }
 
-        if (sorted_path) {
-            last_key = key_of<pw_int, pw_friction>(n, dt);
-            sorted_step<pw_int, pw_friction>(n, dt);
-            return;
-        }
-        last_key = Step_key{};
-
-        const bool folding = fix_com and !fix_com_z and fold_in_update;
-        // 1st stage
-        stage_rhs<pw_int, pw_friction>(1, n, n, gen_forces);
-        const bool zeroing = !ya::is_no_gen_forces<Pt>(gen_forces);
-        if (folding)
-            stage_update_folding(1, n, dt, zeroing);
-        else
-            stage_update(1, n, dt, fix_velocity(n, d_dX, fix_com or fix_com_z, fix_com_z));
-
-        // 2nd stage
-        stage_rhs<pw_int, pw_friction>(2, n, n, gen_forces);
-        if (folding)
-            stage_update_folding(2, n, dt, zeroing);
-        else
-            stage_update(2, n, dt, fix_velocity(n, d_dX1, fix_com, false));
+        last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};
+        heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
     }
 };
 
@@ -2840,12 +2600,8 @@ protected:
     void cancel_build() {}
     const int* cube_order(int, const Pt*) { return nullptr; }  // no grid: renumber() is a no-op
     void ids_changed() {}
-    void predictor_in_sorted_space(int, float, const float*, int) {}
-    void predictor_in_sorted_space_folding(int, float, const float*, int, float*) {}
     const Pt* sorted_rhs() const { return nullptr; }
     ya::Entry<Pt>* sorted_cells() { return nullptr; }
-    void predictor_in_sorted_space_mirrored(int, float, const float*, float*, int, const Pt*, int, float*, ya::Guard_band) {}
-    void ghosts_in_sorted_space(int, int, const Pt*) {}
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints_from_sorted(int, Pt*, int, bool) {}
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
@@ -3308,34 +3064,9 @@ protected:
         forces<pw_int, pw_friction>(n, d_sorted, d_sorted_v, d_dX, has_gen, n_active,
             keep_sorted ? d_dX_sorted : nullptr);
     }
-    // The two halves of the second Heun stage when the first one kept its
-    // right-hand side in cell order (Heun_solver::take_step).
-    void predictor_in_sorted_space(
-        const int n, const float dt, const float* d_fix, const int n_active)
-    {
-        euler_step_sorted<<<(n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK, ya::UPDATE_BLOCK, 0, stream>>>(
-            n, dt, d_fix, d_dX_sorted, d_sorted, n_active);
-    }
+    // the cube-sorted copy stage 1 kept and its right-hand side in sorted order (Heun_solver::stage_update moves it)
     const Pt* sorted_rhs() const { return d_dX_sorted; }
     ya::Entry<Pt>* sorted_cells() { return d_sorted; }
-    void predictor_in_sorted_space_folding(const int n, const float dt, const float* d_partials, const int n_partials,
-        float* d_fix_out)
-    {
-        euler_step_sorted_folding<<<(n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK, ya::UPDATE_BLOCK, 0, stream>>>(
-            n, dt, d_partials, n_partials, d_fix_out, d_dX_sorted, d_sorted);
-    }
-    void predictor_in_sorted_space_mirrored(const int n, const float dt, const float* d_total, float* d_fix_out,
-        const int n_active, const Pt* d_dX, const int fix_mode, float* pred_partial, const ya::Guard_band band)
-    {
-        euler_step_sorted_mirrored<<<(n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK, ya::UPDATE_BLOCK, 0, stream>>>(
-            n, dt, d_total, d_fix_out, d_dX_sorted, d_dX, d_sorted, n_active, fix_mode, pred_partial, band);
-    }
-    void ghosts_in_sorted_space(const int n, const int n_active, const Pt* d_X1)
-    {
-        if (n_active >= n) return;
-        ghosts_into_sorted<<<(n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK, ya::UPDATE_BLOCK, 0, stream>>>(
-            n, n_active, d_X1, d_sorted);
-    }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints_from_sorted(const int n, Pt* d_dX, const int n_active, const bool has_gen)
     {

@@ -103,8 +103,8 @@ void compare(const char* name, float dt, bool callbacks)
 
     for (int s = 0; s < 5; s++) {
         if (with_generic_forces) {
-            // (the decomposed step with generic forces goes through d_X1 and the plain update
-            // kernels instead of the sorted-copy predictor and the raw corrector)
+            // (with generic forces the predictor also writes d_X1, which they read, and both update
+            // kernels leave the next stage's right-hand side rows zeroed)
             whole.template take_step<force>(dt, origin_forces);
             slab.template take_step<force>(dt, origin_forces);
         } else {

@@ -269,6 +269,27 @@ def test_fixed_point_modes(oracle, device):
         assert np.array_equal(Xo.view(np.uint32), Xd.view(np.uint32)), mode
 
 
+@pytest.mark.parametrize("fixed", ["com", "point", "xy"])
+@pytest.mark.parametrize("model,n,pipelines", [
+    ("clipped_grid", 3000, (0, 1, 2)), ("clipped_push_grid", 3000, (0, 1, 2)),
+    ("clipped_tile", 1000, (None,)), ("push_tile", 1000, (None,)), ("clipped_gabriel", 3000, (None,))])
+def test_update_paths_bit_exact(oracle, device, model, n, pipelines, fixed):
+    """Every source of the fixed velocity -- set_fixed(), set_fixed(i), set_fixed_xy(i) -- on every update path:
+    Grid_solver's sorted copy (sorted_pipeline 1), d_X1 (0) and unfolded (2) pipelines, Tile_solver and
+    Gabriel_solver, with and without a generic force."""
+    for pipeline in pipelines:
+        def setup(s, pipeline=pipeline):
+            if fixed == "point":
+                s.set_fixed(17)
+            elif fixed == "xy":
+                s.set_fixed_xy(17)
+            if pipeline is not None and s.lib is device:
+                assert s.set_param("sorted_pipeline", pipeline) == 0
+        (Xo, vo, _), (Xd, vd, _) = run_both(oracle, device, model, n, 50, 1.0, 0.6, 9, 0.05, 3, setup=setup)
+        assert np.array_equal(Xo.view(np.uint32), Xd.view(np.uint32)), pipeline
+        assert np.array_equal(vo.view(np.uint32), vd.view(np.uint32)), pipeline
+
+
 def test_links_parity(oracle, device):
     """Atomic accumulation order is unspecified on the device: tolerance."""
     n = 2000

@@ -578,9 +578,9 @@ def test_eight_slabs_of_a_million_cells_native_sequencing(device):
 
 @pytest.mark.gpu
 def test_slabs_with_a_generic_force(device):
-    """The decomposed step WITH generic forces (they read d_X1, so the step goes through the plain
-    predictor over all local cells, the mirrored cells' d_X1 copied into the sorted copy, and the
-    plain corrector -- not the sorted-copy predictor and raw corrector of the benchmarked path):
+    """The decomposed step WITH generic forces (they read d_X1, so the predictor writes it for all
+    local cells besides moving the sorted copy, and leaves the next stage's rows zeroed -- not the
+    benchmarked path, where d_X1 is not written):
     400 000 cells in four slabs, every cell also pulled towards the origin by a generic force
     (tools/slab_rehearsal.cu, YALLA_REHEARSAL_GENERIC=1), against the undivided system."""
     import json

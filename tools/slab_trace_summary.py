@@ -33,9 +33,9 @@ def main(path, steps, skip=0):
     rows.sort()
     first_marker = next(i for i, r in enumerate(rows) if "slab_takes_the_gpu" in r[2])
     whole = rows[:first_marker]
-    last_raw = max(i for i, r in enumerate(whole) if "heun_step_raw" in r[2])
+    last_raw = max(i for i, r in enumerate(whole) if "heun_step" in r[2])
     whole = whole[: last_raw + 1]
-    n_whole_steps = sum("heun_step_raw" in r[2] for r in whole)
+    n_whole_steps = sum("heun_step" in r[2] for r in whole)
     per_rank = collections.defaultdict(list)
     rank = None
     for a, b, name in rows[first_marker:]:
@@ -63,7 +63,7 @@ def main(path, steps, skip=0):
         copies = sum(b - a for a, b, n in ks if "copyBuffer" in n or "fillBuffer" in n) / steps / 1e6
         by_kernel = collections.defaultdict(lambda: [0, 0])
         for a, b, n in ks:
-            short = re.sub(r"^.*?(k_\w+|grid_force_\w+?|\w+_step\w*|ghosts_into_sorted|copyBuffer|fillBuffer\w*)\b.*$", r"\1",
+            short = re.sub(r"^.*?(k_\w+|grid_force_\w+?|\w+_step\w*|copyBuffer|fillBuffer\w*)\b.*$", r"\1",
                            re.sub(r"I.*$", "", n.replace("_ZN2ya15", "").replace("void ", "")) if n.startswith("_ZN2ya15")
                            else n)
             by_kernel[short][0] += b - a

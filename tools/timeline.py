@@ -7,7 +7,7 @@ def short(n):
     m = re.search(r'(k_\w+|grid_force\w*|tile_force|heun_step\w*|euler_step\w*|copyBuffer|fillBuffer|make_fix|link\w*)', n)
     return m.group(1) if m else n[:24]
 seq = [(short(r['Kernel_Name']), int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in rows]
-last = sys.argv[2] if len(sys.argv) > 2 else 'heun_step_raw'
+last = sys.argv[2] if len(sys.argv) > 2 else 'heun_step'
 idx = [i for i, s in enumerate(seq) if s[0] == last]
 a, b = idx[len(idx) // 2], idx[len(idx) // 2 + 1]
 t0 = seq[a][2]; prev = seq[a][1]
