@@ -2258,14 +2258,22 @@ public:
 
     // Replaying the step as one hipGraph (Grid_solver without generic forces), opt-in:
     // 1 = whenever possible, -1 = for systems below YA_GRAPH_MAX_CELLS cells, 0 (default) =
-    // never.  The graph is captured the second time the same step (functors, n, dt, fixed
-    // point, cube size, force kernel) is asked for and replayed while that stays so; a
-    // changing n (proliferation) simply keeps the plain launches.  Results are identical: the
-    // same kernels with the same arguments.  Measured on MI355X it buys nothing when the
+    // never.  The graph is captured the second time in a row the same step is asked for and
+    // replayed while that stays so.  "The same step" is everything a captured launch bakes in
+    // (Step_key): functors, n, dt, fixed mode and point, fold_in_update, cube size, and the
+    // computer's own settings (Grid_computer::step_variant: force_variant, sum_order, coop_lanes,
+    // stage_v_max, force_tail_tiles, d_global_id, the tail exchange areas).  These are public
+    // members a model may assign at any time, so they are compared at every step, not watched
+    // by setters.  The step after ANY change is a plain one (it may allocate, and it leaves the
+    // grid's remembered visit order as a replay expects it); a graph whose key comes back is
+    // replayed again from the step after that.  A changing n (proliferation) simply keeps the
+    // plain launches.  Results are identical: the same kernels with the same arguments.
+    // graph_launches counts the hipGraphLaunch calls.  Measured on MI355X it buys nothing when the
     // host queues launches from a C++ loop (a step of a 10^4-cell system is bound by the
     // ~18 dependent kernels' own latencies, 0.19 ms either way); it is for hosts that
     // cannot keep ~10^5 launches per second up.
     int graph_steps = 0;
+    long graph_launches = 0;  // read-only: steps that ran as a hipGraphLaunch (tests: replay really happened)
 
 protected:
 #ifndef YA_GRAPH_MAX_CELLS
@@ -2275,11 +2283,13 @@ protected:
         const void* functors = nullptr;
         int n = -1;
         float dt = 0, cube_size = 0;
-        int variant = 0, fix_mode = 0, fix_point = 0;
+        typename Computer<Pt>::Step_variant variant{};
+        int fix_mode = 0, fix_point = 0;
+        bool fold = true;
         bool operator==(const Step_key& o) const
         {
             return functors == o.functors && n == o.n && dt == o.dt && cube_size == o.cube_size &&
-                   variant == o.variant && fix_mode == o.fix_mode && fix_point == o.fix_point;
+                   variant == o.variant && fix_mode == o.fix_mode && fix_point == o.fix_point && fold == o.fold;
         }
     };
     Step_key graph_key, last_key;
@@ -2502,6 +2512,7 @@ protected:
         k.variant = Computer<Pt>::step_variant();
         k.fix_mode = (fix_com ? 1 : 0) | (fix_com_z ? 2 : 0);
         k.fix_point = fix_point;
+        k.fold = fold_in_update;
         return k;
     }
 
@@ -2521,11 +2532,24 @@ protected:
             n = get_d_n();
             if (n <= 0) return;
             const Step_key key = key_of<pw_int, pw_friction>(n, dt);
-            if (graph_exec && key == graph_key) {
+            // Replay only what the step before was too (key == last_key: every plain step leaves its key
+            // there).  The graph also bakes in what the grid remembered when it was captured -- the visit
+            // order of a build of these n cells (n_prev, d_prev_pid) -- and that holds only straight after
+            // such a step: a graph whose key comes back after other steps (n down and up again) waits one
+            // plain step.
+            if (graph_exec && key == graph_key && key == last_key) {
                 YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
+                graph_launches++;
                 return;
             }
-            if (key == last_key && (graph_steps > 0 || n < YA_GRAPH_MAX_CELLS)) {
+            // NOTHING between hipStreamBeginCapture and hipStreamEndCapture may synchronise, allocate, free or
+            // use the null stream (ya_device_synchronize, ya_malloc / ya_free, hipMemcpy, a memset or launch
+            // without this->stream): the runtime fails such a call and YA_CHECK ends the process.  The step
+            // before ran the same launches plainly, so everything lazily sized exists (the grid's stash, the
+            // tail exchange area); a computer that would still have to allocate says so (ready_to_capture)
+            // and the step stays a plain one.
+            if (key == last_key && (graph_steps > 0 || n < YA_GRAPH_MAX_CELLS) &&
+                Computer<Pt>::template ready_to_capture<pw_int, pw_friction>(n)) {
                 // the same step as last time: capture it (thread-local mode: other host
                 // threads of the model, e.g. one writing output, may keep using HIP)
                 drop_graph();
@@ -2541,10 +2565,11 @@ protected:
                 YA_CHECK((int)hipGraphDestroy(graph));
                 graph_key = key;
                 YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
+                graph_launches++;
                 return;
             }
-            last_key = key;
             heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
+            last_key = key_of<pw_int, pw_friction>(n, dt);  // (after the launches: they may have allocated)
             return;
         }
         if (Computer<Pt>::use_sorted_pipeline()) {
@@ -2568,8 +2593,8 @@ protected:
             return;
         }
 
-        last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};
         heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
+        last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};  // (after the launches, as above)
     }
 };
 
@@ -2594,7 +2619,10 @@ public:
 protected:
     hipStream_t stream = nullptr;  // every launch of a step goes here (null = the default stream)
     float step_cube_size() const { return 0; }
-    int step_variant() const { return 0; }
+    using Step_variant = int;  // (no captured step: Heun_solver::Step_key)
+    Step_variant step_variant() const { return 0; }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    bool ready_to_capture(int) const { return false; }
     void check_status() {}
     void begin_build(const Pt*, const int*, int, ya_n_reader*) {}
     void cancel_build() {}
@@ -2841,7 +2869,25 @@ public:
 protected:
     hipStream_t stream = nullptr;  // every launch of a step goes here (null = the default stream)
     float step_cube_size() const { return cube_size; }
-    int step_variant() const { return force_variant; }
+    // Everything of this class that a captured step bakes into its launches (Heun_solver::Step_key compares it
+    // at every step: the members are public and assigned directly).  A member added to forces() that picks a
+    // kernel, a launch size or a kernel argument belongs here too.
+    struct Step_variant {
+        int force_variant = -1, sum_order = 0, coop_lanes = 0, stage_v_max = 0, tail_tiles = 0;
+        int tail_areas = 0;  // allocations of tail exchange areas so far: a graph made before one holds freed pointers
+        const int* global_id = nullptr;
+        bool operator==(const Step_variant& o) const
+        {
+            return force_variant == o.force_variant && sum_order == o.sum_order && coop_lanes == o.coop_lanes &&
+                   stage_v_max == o.stage_v_max && tail_tiles == o.tail_tiles && tail_areas == o.tail_areas &&
+                   global_id == o.global_id;
+        }
+    };
+    Step_variant step_variant() const
+    {
+        return {force_variant, (int)sum_order, coop_lanes, stage_v_max, force_tail_tiles, tail_areas, d_global_id};
+    }
+    int tail_areas = 0;
     Grid grid;
     ya::Entry<Pt>*d_sorted, *d_resorted;
     float4 *d_sorted_v, *d_resorted_v;
@@ -2903,16 +2949,15 @@ protected:
     else                                                                                      \
         hipLaunchKernelGGL((kernel_), dim3(grid_), dim3(block_), 0, stream, __VA_ARGS__)
         // the kernel this launch goes to: an explicit choice, or by what the model said about its functors
-        const int force_variant = this->force_variant >= 0 ? this->force_variant
-                                  : (ya::stateless_pair<Pt, pw_int, pw_friction>() ? 3 : 2);
-        const int lanes = force_variant == 3 ? (coop_lanes ? coop_lanes : ya::coop::lanes_for(n, by_plane)) : 1;
+        const Kernel_choice choice = kernel_choice<pw_int, pw_friction>(n);
+        const int force_variant = choice.variant, lanes = choice.lanes;
         if (force_variant < 0 || force_variant > 3) {
             fprintf(stderr, "yalla-hip: Grid_computer::force_variant %d is not a kernel (-1, 0, 1, 2, 3)\n", force_variant);
             abort();
         }
         // two launches per stage (force_part) are what grid_force_bits offers; the other kernels
         // compute every tile in the first call
-        const bool bits_kernel = lanes == 1 && force_variant >= 2;
+        const bool bits_kernel = choice.bits_kernel();
         int part = 0;
         hipStream_t stream = this->stream;
         if (force_part == 1) {
@@ -2970,23 +3015,22 @@ protected:
             // 10^7 cells, profiles/r05_tail_ab.txt).  Two wavefronts then call the functor for the same cell i
             // at once: only for functors declared stateless (YA_STATELESS; relu_w_epithelium's
             // `d_mes_nbs[i] += 1` would lose counts).
-            int tail = 0;
-            if (by_plane && ya::stateless_pair<Pt, pw_int, pw_friction>()) {
-                if (force_tail_tiles >= 0) {
-                    tail = force_tail_tiles >= tiles ? -1 : force_tail_tiles;
-                } else {
-                    const int resident = resident_workgroups<ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>>();
-                    if (part != 0)  // a slab stage's two launches, side by side: all halves only if both fit at once;
-                        tail = 2 * tiles <= resident ? -1 : 768;  // the kernel leaves a list of < 4 tails' tiles whole
-                    else
-                        tail = 2 * tiles <= resident ? -1 : (tiles <= resident ? resident - tiles : 768);
-                }
-            }
+            const int tail = tail_of<pw_int, pw_friction>(tiles, part);
             const int room = tail < 0 ? tiles : tail;
             if (room > 0 && (!d_tail_exchange[part] || tail_room[part] < room)) {
                 // (a solver's launches are stream-ordered except parts 1 and 2 of a slab stage, which have
                 // exchange areas of their own)
                 constexpr int NC = ya::N_floats<Pt>::value + 4;
+                // Never inside a stream capture: Heun_solver::take_step captures a step only after the same step
+                // ran plainly (which came through here) and after ready_to_capture() said nothing is missing.
+                // Should a new path get here all the same, say what happened instead of a bare HIP error code.
+                hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+                if (this->stream) YA_CHECK((int)hipStreamIsCapturing(this->stream, &capturing));
+                if (capturing != hipStreamCaptureStatusNone) {
+                    fprintf(stderr, "yalla-hip: grid_force_bits' tail exchange area would have to be allocated inside a "
+                                    "stream capture (Grid_computer::ready_to_capture missed a case)\n");
+                    abort();
+                }
                 YA_CHECK(ya_device_synchronize());
                 if (d_tail_exchange[part]) ya_free(d_tail_exchange[part]), ya_free(d_tail_tickets[part]);
                 // once per solver, not once per size: a system that grows (proliferation) asks for a tile more
@@ -2999,6 +3043,7 @@ protected:
                 YA_CHECK(ya_memset_async(d_tail_tickets[part], 0, slots * sizeof(int), nullptr));
                 YA_CHECK(ya_device_synchronize());
                 tail_room[part] = (int)slots - 8;
+                tail_areas++;  // (graphs captured so far hold the freed areas' addresses: Step_variant)
             }
             // (old_v in LDS costs a launch of halves the residency it lives on: 13 KB per workgroup are 12 per CU)
             const bool stage_v = n <= stage_v_max && tail >= 0;
@@ -3034,6 +3079,42 @@ protected:
 #endif
 #undef YA_COOP_LAUNCH
 #undef YA_FORCE_LAUNCH
+    }
+    // The kernel a launch of n cells goes to (forces(), and ready_to_capture() which must agree with it): an
+    // explicit choice, or by what the model said about its functors; lanes per cell (1: not grid_force_coop)
+    struct Kernel_choice {
+        int variant, lanes;
+        bool bits_kernel() const { return lanes == 1 && variant >= 2; }  // grid_force_bits: tails, two launches per stage
+    };
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    Kernel_choice kernel_choice(const int n) const
+    {
+        const int variant = force_variant >= 0 ? force_variant : (ya::stateless_pair<Pt, pw_int, pw_friction>() ? 3 : 2);
+        const int lanes =
+            variant == 3 ? (coop_lanes ? coop_lanes : ya::coop::lanes_for(n, sum_order == YA_SUM_BY_PLANE)) : 1;
+        return {variant, lanes};
+    }
+    // grid_force_bits' tail for a launch of `tiles` tiles: > 0 the last so many as half tiles, < 0 all, 0 none
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    int tail_of(const int tiles, const int part)
+    {
+        if (sum_order != YA_SUM_BY_PLANE || !ya::stateless_pair<Pt, pw_int, pw_friction>()) return 0;
+        if (force_tail_tiles >= 0) return force_tail_tiles >= tiles ? -1 : force_tail_tiles;
+        const int resident = resident_workgroups<ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>>();
+        if (part != 0)  // a slab stage's two launches, side by side: all halves only if both fit at once;
+            return 2 * tiles <= resident ? -1 : 768;  // the kernel leaves a list of < 4 tails' tiles whole
+        return 2 * tiles <= resident ? -1 : (tiles <= resident ? resident - tiles : 768);
+    }
+    // Heun_solver::take_step before it captures a step of n cells: would forces() have to allocate?  (The captured
+    // step is an undivided one: part 0.)
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    bool ready_to_capture(const int n)
+    {
+        if (!kernel_choice<pw_int, pw_friction>(n).bits_kernel()) return true;
+        const int tiles = (n + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
+        const int tail = tail_of<pw_int, pw_friction>(tiles, 0);
+        const int room = tail < 0 ? tiles : tail;
+        return room <= 0 || (d_tail_exchange[0] && tail_room[0] >= room);
     }
     // Heun_solver::renumber: the cells' ids in (cube, id) order = the point ids of a fresh build
     const int* cube_order(const int n, const Pt* d_X)

@@ -170,6 +170,11 @@ int ya_sim_set_reduce_order(ya_sim* sim, int order);
 int ya_sim_profile(ya_sim* sim, int enable);
 int ya_sim_profile_read(ya_sim* sim, double* total_ms, int* launches);
 
+/* Device only, read-only (test hook): the steps of this system so far that ran as a hipGraphLaunch
+ * (Heun_solver::graph_launches; set_param "graph").  -1 on the oracle, -2 for solvers without
+ * captured steps (Tile_solver, Gabriel_solver). */
+long ya_sim_graph_launches(ya_sim* sim);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -63,6 +63,7 @@ MODELS_ABI = {
     "ya_check_reciprocal": (C.c_long, [C.c_uint, C.c_uint]),
     "ya_sim_profile": (C.c_int, [_sim, C.c_int]),
     "ya_sim_profile_read": (C.c_int, [_sim, C.POINTER(C.c_double), _pi]),
+    "ya_sim_graph_launches": (C.c_long, [_sim]),
 }
 
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).

@@ -50,6 +50,7 @@ struct Sim_base {
     virtual int set_reduce_order(int) { return -1; }
     virtual int profile(int) { return -1; }
     virtual int profile_read(double*, int*) { return -1; }
+    virtual long graph_launches() { return -1; }
     // z-slab decomposition (Grid_solver models only)
     virtual int slab_init(float, float, float, const int*) { return -2; }
     virtual int slab_decompose(const float*, int, int, int, float) { return -2; }
@@ -97,6 +98,7 @@ struct Cells<Pt, TILE> : public Solution<Pt, Tile_solver> {
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
     int set_graph(int) { return -2; }
+    long graph_launches_so_far() { return -2; }
     int set_slab_global_ids(int) { return -2; }
     // Tile_solver stays single-GPU (all pairs): no slab decomposition.
     int slab_init(float, float, float, const int*, int) { return -2; }
@@ -217,6 +219,7 @@ struct Cells<Pt, GRID> : public Solution<Pt, Harness_slab_solver> {
         return 0;
 #endif
     }
+    long graph_launches_so_far() { return this->graph_launches; }  // (device build only: Sim::graph_launches)
 
 };
 
@@ -254,6 +257,7 @@ struct Cells<Pt, GABRIEL> : public Solution<Pt, Gabriel_solver> {
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
     int set_graph(int) { return -2; }
+    long graph_launches_so_far() { return -2; }
     int set_slab_global_ids(int) { return -2; }
     int slab_init(float, float, float, const int*, int) { return -2; }
     int get_own(float*, int*) { return -2; }
@@ -664,6 +668,14 @@ struct Sim : public Sim_base {
         if (rc == 0) *cells.h_n = cells.slab.n_own;  // (the drift guard may have made the step migrate)
         return rc;
     }
+    long graph_launches() override
+    {
+#ifdef YA_ORACLE
+        return -1;
+#else
+        return cells.graph_launches_so_far();
+#endif
+    }
 #ifdef YA_ORACLE
     int set_reduce_order(int order) override
     {
@@ -918,5 +930,6 @@ long ya_check_reciprocal(unsigned first_bits, unsigned last_bits)
 }
 int ya_sim_profile(ya_sim* s, int enable) { return s->p->profile(enable); }
 int ya_sim_profile_read(ya_sim* s, double* ms, int* launches) { return s->p->profile_read(ms, launches); }
+long ya_sim_graph_launches(ya_sim* s) { return s->p->graph_launches(); }
 
 }  // extern "C"

@@ -166,6 +166,10 @@ class Solution:
     def set_reduce_order(self, order):
         return self.lib.ya_sim_set_reduce_order(self._h, int(order))
 
+    def graph_launches(self):
+        """Steps so far that ran as a hipGraphLaunch (-1 oracle, -2 solvers without captured steps)."""
+        return self.lib.ya_sim_graph_launches(self._h)
+
     def profile(self, enable, every=1):
         """Time every `every`-th launch of the force kernel with HIP events."""
         return self.lib.ya_sim_profile(self._h, int(every) if enable else 0)
