@@ -1,0 +1,593 @@
+// Ensemble<Pt, Tile_solver>: M independent all-pairs systems of one point type and one functor,
+// advanced together -- the same six launches per take_step whatever M is, and nothing read by the
+// host: every kernel takes its replica's cell count from d_n[r] on the device.
+//
+// One Tile_solver step of a few hundred cells is launch and host latency, not work (DESIGN.md
+// section 9: 49 us for 800 cells), and a sweep over M such systems as M Solutions pays that M times
+// per step, one system after the other.  Here the latency is paid once per step.
+//
+//     Ensemble<float3> cells{n_replicas, n_max};        // n_max = capacity of EACH replica
+//     cells.h_n[r] = ...; *cells.row(r, i) = ...;       // fill replica r's rows 0 .. h_n[r] - 1
+//     cells.copy_to_device();
+//     cells.take_step<my_force>(dt);                    // all replicas, bit for bit what a lone
+//                                                       // Solution<float3, Tile_solver> of each gives
+//
+// LAYOUT  One flat allocation per array, replica-major: replica r owns rows
+// [r * n_max, r * n_max + n[r]) of h_X, d_X, d_old_v (and of the private right-hand sides);
+// h_n[r] / d_n[r] are the counts.  Counts may differ and may be 0 (such a replica is left alone, as
+// take_step leaves an empty Solution); model kernels may change d_n[r] between steps.
+//
+// IDS  Pairwise functors are called with ensemble-global ids i = r * n_max + local, j likewise: a
+// model's per-cell arrays are sized n_replicas * n_max and indexed by i as always, `i == j` keeps its
+// meaning, and a functor finds its replica as i / n_max (a sweep reads its per-replica parameter
+// from the model's own device array that way).  Generic forces are called once per stage on the
+// flat arrays, gen_forces(n_replicas * n_max, d_in, d_rhs), with the WHOLE right-hand side zeroed
+// beforehand, unused rows included: Links and Property objects sized for the flat id space work
+// unchanged.
+//
+// RESULTS  Every per-cell sum is accumulated in tile_force's order (j ascending over the replica's
+// own rows), the centre of mass in ya_reduce_partials' order (B_r = clamp(ceil(n_r / 256), 1, 1024)
+// blocks of the replica's rows, fold256, then the update kernels' fold of the B_r partials), the
+// updates are Heun_solver's statements: each replica holds the bits a Solution<Pt, Tile_solver>
+// run of the same rows holds (tests/test_ensemble_gpu.py, tests/native_ensemble).
+//
+// Not here ("Ensembles"): Grid_solver / Gabriel_solver ensembles (the Solver
+// template parameter is their door), the fast-arithmetic tier, graph capture, a per-replica dt, slabs.
+#pragma once
+
+#include "solvers.cuh"
+
+namespace ya {
+namespace ens {
+
+// A workgroup's replica and its block within the replica, from the flat x index (the replica count is
+// not bounded by gridDim.y that way).
+struct Where {
+    int replica, block;
+};
+__device__ __forceinline__ Where where(const int blocks_per_replica)
+{
+    return Where{(int)(blockIdx.x / (unsigned)blocks_per_replica), (int)(blockIdx.x % (unsigned)blocks_per_replica)};
+}
+// the replica's count as the device holds it now (never beyond the replica's rows)
+__device__ __forceinline__ int count_of(const int* __restrict__ d_n, const int replica, const int n_max)
+{
+    return min(d_n[replica], n_max);
+}
+
+// ya::tile_force for every replica at once: a workgroup serves 64 cells of ONE replica, tiles of
+// TILE_POINTS partners come from that replica's rows only, j ascending, the functor is called for every
+// (i, j) including i == j, ids are ensemble-global.  The loop is tile_force's, restated (the existing
+// kernels stay untouched, and so do their registers: profiles/ensemble_resource_usage.txt).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(TILE_BLOCK) void tile_force_batched(const int n_max, const int blocks_per_replica,
+    const int* __restrict__ d_n, const Pt* __restrict__ d_X_all, const float3* __restrict__ d_old_v_all,
+    Pt* __restrict__ d_dX_all, const bool has_gen)
+{
+    __shared__ Pt sh_X[TILE_POINTS];
+    __shared__ float3 sh_v[TILE_POINTS];
+
+    const Where w = where(blocks_per_replica);
+    const int n = count_of(d_n, w.replica, n_max);
+    if (w.block * TILE_BLOCK >= n) return;  // (the whole workgroup: blocks past n[r] return at once)
+    const size_t base = (size_t)w.replica * n_max;
+    const Pt* __restrict__ d_X = d_X_all + base;
+    const float3* __restrict__ d_old_v = d_old_v_all + base;
+    Pt* __restrict__ d_dX = d_dX_all + base;
+    const int id_base = (int)base;
+
+    const int local = w.block * TILE_BLOCK + threadIdx.x;
+    const int i = id_base + local;
+    Pt Xi = ya::zero<Pt>();
+    if (local < n) Xi = d_X[local];
+    Pt F = ya::zero<Pt>();
+    float3 sum_v{0.f, 0.f, 0.f};
+    float sum_friction = 0;
+    for (int tile_start = 0; tile_start < n; tile_start += TILE_POINTS) {
+        const int n_tile = min(TILE_POINTS, n - tile_start);
+        __syncthreads();
+        for (int k = threadIdx.x; k < n_tile; k += TILE_BLOCK) {
+            sh_X[k] = d_X[tile_start + k];
+            sh_v[k] = d_old_v[tile_start + k];
+        }
+        __syncthreads();
+        if (local < n) {
+#pragma unroll YA_TILE_UNROLL
+            for (int k = 0; k < n_tile; k++) {
+                const int j = id_base + tile_start + k;
+                Pt r = Xi - sh_X[k];
+                float dist = dist3(r.x, r.y, r.z);
+                F += pw_int(Xi, r, dist, i, j);
+                float friction = pw_friction(Xi, r, dist, i, j);
+                sum_friction += friction;
+                if (friction != 0) {
+                    float3 v = sh_v[k];
+                    sum_v.x += friction * v.x;
+                    sum_v.y += friction * v.y;
+                    sum_v.z += friction * v.z;
+                }
+            }
+        }
+    }
+    if (local < n) store_rhs(d_dX, local, has_gen, F, sum_v, sum_friction);
+}
+
+// ya::tile_force_coop for every replica at once: a 256-thread workgroup owns 16 or 4 cells of ONE replica.
+// tile_force_coop's two phases, restated: the lanes of a cell leave a tile's pair terms in LDS, one lane per
+// component adds them in ascending j -- the sums of tile_force_batched, bit for bit.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+__global__ __launch_bounds__(256) void tile_force_coop_batched(const int n_max, const int blocks_per_replica,
+    const int* __restrict__ d_n, const Pt* __restrict__ d_X_all, const float3* __restrict__ d_old_v_all,
+    Pt* __restrict__ d_dX_all, const bool has_gen)
+{
+    constexpr int COOP_CELLS = 256 / COOP_LANES;
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int NC = NF + 4;  // components summed per cell: F (NF), friction, friction * old_v (3)
+    // partners per tile: a multiple of 64 whose terms fill at most 56 KiB of LDS
+    constexpr int TILE = (57344 / (COOP_CELLS * NC * 4)) / 64 * 64 > 512 ? 512 : (57344 / (COOP_CELLS * NC * 4)) / 64 * 64;
+    static_assert(TILE >= 64, "point type too large for tile_force_coop_batched");
+    constexpr int THREADS = COOP_CELLS * COOP_LANES;
+    constexpr int LOADS = (TILE + THREADS - 1) / THREADS;  // partners a thread carries per tile
+    constexpr int SLOTS = (NC + COOP_LANES - 1) / COOP_LANES;
+    __shared__ __attribute__((aligned(16))) float sh_part[COOP_CELLS][NC][TILE];  // one tile's terms, [cell][component][j]
+    __shared__ Pt sh_X[TILE];                        // the tile's partners
+    __shared__ float3 sh_v[TILE];
+    __shared__ float sh_sum[COOP_CELLS][NC];
+
+    const Where w = where(blocks_per_replica);
+    const int n = count_of(d_n, w.replica, n_max);
+    if (w.block * COOP_CELLS >= n) return;  // (the whole workgroup)
+    const size_t base = (size_t)w.replica * n_max;
+    const Pt* __restrict__ d_X = d_X_all + base;
+    const float3* __restrict__ d_old_v = d_old_v_all + base;
+    Pt* __restrict__ d_dX = d_dX_all + base;
+    const int id_base = (int)base;
+
+    const int cell = threadIdx.x / COOP_LANES, lane = threadIdx.x % COOP_LANES;
+    const int local = w.block * COOP_CELLS + cell;
+    const int i = id_base + local;
+    const bool active = local < n;
+    Pt Xi = ya::zero<Pt>();
+    if (active) Xi = d_X[local];
+    float acc[SLOTS];  // this lane's component sums (components lane, lane + COOP_LANES, ...)
+#pragma unroll
+    for (int a = 0; a < SLOTS; a++) acc[a] = 0.f;
+
+    // the next tile's partners travel from global memory while the current tile is worked on
+    Pt x_next[LOADS];
+    float3 v_next[LOADS];
+#pragma unroll
+    for (int k = 0; k < LOADS; k++) {
+        const int j = threadIdx.x + k * THREADS;
+        x_next[k] = ya::zero<Pt>();
+        v_next[k] = float3{0.f, 0.f, 0.f};
+        if (j < TILE && j < n) {
+            x_next[k] = d_X[j];
+            v_next[k] = d_old_v[j];
+        }
+    }
+    for (int tile_start = 0; tile_start < n; tile_start += TILE) {
+        const int n_tile = min(TILE, n - tile_start);
+#pragma unroll
+        for (int k = 0; k < LOADS; k++) {
+            const int t = threadIdx.x + k * THREADS;
+            if (t < TILE) {
+                sh_X[t] = x_next[k];
+                sh_v[t] = v_next[k];
+                const int j_next = tile_start + TILE + t;
+                if (j_next < n) {
+                    x_next[k] = d_X[j_next];
+                    v_next[k] = d_old_v[j_next];
+                }
+            }
+        }
+        __syncthreads();
+        // (a) the tile's pair terms: lane l takes partners l, l + COOP_LANES, ...
+        if (active) {
+#pragma unroll 4
+            for (int jj = lane; jj < n_tile; jj += COOP_LANES) {
+                const int j = id_base + tile_start + jj;
+                Pt r = Xi - sh_X[jj];
+                float dist = dist3(r.x, r.y, r.z);
+                const Pt f = pw_int(Xi, r, dist, i, j);
+                const float friction = pw_friction(Xi, r, dist, i, j);
+#pragma unroll
+                for (int c = 0; c < NF; c++) sh_part[cell][c][jj] = field(f, c);
+                sh_part[cell][NF][jj] = friction;
+                // the old_v term only where the friction is not zero: a +0 term instead changes no bit of a
+                // sum that started at +0 (ya::tile_force_coop)
+                const float3 v = sh_v[jj];
+                sh_part[cell][NF + 1][jj] = friction != 0 ? friction * v.x : 0.f;
+                sh_part[cell][NF + 2][jj] = friction != 0 ? friction * v.y : 0.f;
+                sh_part[cell][NF + 3][jj] = friction != 0 ? friction * v.z : 0.f;
+            }
+        }
+        __syncthreads();
+        // (b) one lane per component adds the tile's terms in ascending j
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) {
+            const int c = lane + COOP_LANES * a;
+            if (c < NC && active) {
+                float sum = acc[a];
+                const float4* terms = reinterpret_cast<const float4*>(&sh_part[cell][c][0]);
+                int jj = 0;
+                for (; jj + 16 <= n_tile; jj += 16) {
+                    float4 p[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) p[u] = terms[jj / 4 + u];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        sum += p[u].x;
+                        sum += p[u].y;
+                        sum += p[u].z;
+                        sum += p[u].w;
+                    }
+                }
+                for (; jj < n_tile; jj++) sum += sh_part[cell][c][jj];
+                acc[a] = sum;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < SLOTS; a++) {
+        const int c = lane + COOP_LANES * a;
+        if (c < NC) sh_sum[cell][c] = acc[a];
+    }
+    __syncthreads();
+    if (active && lane == 0) {
+        Pt F;
+#pragma unroll
+        for (int c = 0; c < NF; c++) field(F, c) = sh_sum[cell][c];
+        store_rhs(d_dX, local, has_gen, F,
+            float3{sh_sum[cell][NF + 1], sh_sum[cell][NF + 2], sh_sum[cell][NF + 3]}, sh_sum[cell][NF]);
+    }
+}
+
+// Partial sums of every replica's right-hand sides in one launch, in exactly the order of
+// libyalla_hip.so's k_reduce_partial (restated: that library's ABI is not extended for this): replica r
+// uses B_r = clamp(ceil(n_r / 256), 1, 1024) of its `max_blocks` workgroups, lane (b, t) sums the
+// replica's rows 256 b + t, += 256 B_r, the 256 lanes are folded by halving (fold256).  The partials of
+// replica r are rows [r * max_blocks, r * max_blocks + B_r) of the workspace.
+constexpr int REDUCE_MAX_BLOCKS = 1024;
+__host__ __device__ __forceinline__ int reduce_blocks(const int n)
+{
+    const int b = (n + UPDATE_BLOCK - 1) / UPDATE_BLOCK;
+    return b < 1 ? 1 : (b > REDUCE_MAX_BLOCKS ? REDUCE_MAX_BLOCKS : b);
+}
+template<int NW>
+__global__ __launch_bounds__(UPDATE_BLOCK) void reduce_partials_batched(const int n_max, const int max_blocks,
+    const int* __restrict__ d_n, const float* __restrict__ v_all, float* __restrict__ partials)
+{
+    static_assert(UPDATE_BLOCK == 256, "the fold is libyalla_hip.so's fold256");
+    __shared__ float sh[NW * UPDATE_BLOCK];
+    const Where w = where(max_blocks);
+    const int n = count_of(d_n, w.replica, n_max);
+    if (n <= 0) return;
+    const int B = reduce_blocks(n);
+    if (w.block >= B) return;
+    const float* __restrict__ v = v_all + (size_t)w.replica * n_max * NW;
+    float acc[NW];
+#pragma unroll
+    for (int k = 0; k < NW; k++) acc[k] = 0.f;
+    for (long i = (long)w.block * UPDATE_BLOCK + threadIdx.x; i < n; i += (long)B * UPDATE_BLOCK) {
+        const float* p = v + (size_t)i * NW;
+#pragma unroll
+        for (int k = 0; k < NW; k++) acc[k] = acc[k] + p[k];
+    }
+    // fold256: lane[t] += lane[t + s] for s = 128 ... 1, from s = 32 down by shuffle
+#pragma unroll
+    for (int k = 0; k < NW; k++) sh[k * UPDATE_BLOCK + threadIdx.x] = acc[k];
+    __syncthreads();
+    if ((int)threadIdx.x < 128) {
+#pragma unroll
+        for (int k = 0; k < NW; k++)
+            sh[k * UPDATE_BLOCK + threadIdx.x] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 128];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 64) {
+        float s64[NW];
+#pragma unroll
+        for (int k = 0; k < NW; k++) s64[k] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 64];
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+            for (int k = 0; k < NW; k++) s64[k] = s64[k] + __shfl_down(s64[k], s, 64);
+        }
+        if (threadIdx.x == 0) {
+            float* out = partials + ((size_t)w.replica * max_blocks + w.block) * NW;
+#pragma unroll
+            for (int k = 0; k < NW; k++) out[k] = s64[k];
+        }
+    }
+}
+
+// What a stage subtracts from dX.xyz (Heun_solver::heun_stages / fix_velocity): the mean of the replica's
+// right-hand sides, the fixed point's right-hand side, or the point's x and y with the mean's z.
+enum Fix_kind { FIX_MEAN = 0, FIX_POINT = 1, FIX_POINT_XY = 2 };
+
+// The replica's fixed velocity of this stage: the mean folded from the replica's partial sums
+// (ya::fixed_velocity_from_partials on its slice, with n_r), the point's row read directly (no make_fix
+// launch).  Every thread of the workgroup calls it (the fold has barriers).
+template<typename Pt>
+__device__ __forceinline__ float3 resolve_fix(const int kind, const float* __restrict__ partials, const int max_blocks,
+    const int replica, const int n, const Pt* __restrict__ d_rhs, const int fix_point)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    float3 fix{0.f, 0.f, 0.f};
+    if (kind != FIX_POINT)
+        fix = fixed_velocity_from_partials<NF>(partials + (size_t)replica * max_blocks * NF, reduce_blocks(n), n);
+    if (kind != FIX_MEAN) {
+        const Pt p = d_rhs[fix_point];
+        fix.x = p.x;
+        fix.y = p.y;
+        if (kind == FIX_POINT) fix.z = p.z;
+    }
+    return fix;
+}
+
+// euler_step for every replica: X1 = X0 + (dX - fix) dt on the replica's n_r rows; the replica's first
+// workgroup leaves the stage's velocity in d_fix_first[4 r ..] for the corrector.  d_zero (may be NULL): the
+// next stage's right-hand side, left zeroed for the generic forces -- ALL of the replica's rows, used or not.
+template<typename Pt>
+__global__ __launch_bounds__(UPDATE_BLOCK) void euler_step_batched(const int n_max, const int blocks_per_replica,
+    const int* __restrict__ d_n, const float dt, const int kind, const int fix_point, const float* __restrict__ partials,
+    const int max_blocks, float* __restrict__ d_fix_first, const Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_X0_all,
+    Pt* __restrict__ d_X1_all, Pt* __restrict__ d_zero_all)
+{
+    const Where w = where(blocks_per_replica);
+    const int n = count_of(d_n, w.replica, n_max);
+    const size_t base = (size_t)w.replica * n_max;
+    const int local = w.block * UPDATE_BLOCK + threadIdx.x;
+    if (d_zero_all && local < n_max) d_zero_all[base + local] = ya::zero<Pt>();
+    if (w.block * UPDATE_BLOCK >= n) return;  // (the whole workgroup; an empty replica is left alone)
+    const Pt* __restrict__ d_dX = d_dX_all + base;
+    const float3 fix = resolve_fix<Pt>(kind, partials, max_blocks, w.replica, n, d_dX, fix_point);
+    if (local == 0) {
+        d_fix_first[4 * (size_t)w.replica + 0] = fix.x;
+        d_fix_first[4 * (size_t)w.replica + 1] = fix.y;
+        d_fix_first[4 * (size_t)w.replica + 2] = fix.z;
+    }
+    if (local < n) d_X1_all[base + local] = d_X0_all[base + local] + ya::minus_fix(d_dX[local], fix) * dt;
+}
+
+// heun_step for every replica: X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v, fix as the predictor left
+// it, fix1 from this stage.  zero_dX: the replica's rows of d_dX, dead after this, are left zeroed -- all of
+// them -- for the next step's generic forces; the fixed point's stage-1 row is therefore never read here.
+template<typename Pt>
+__global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_max, const int blocks_per_replica,
+    const int* __restrict__ d_n, const float dt, const int kind, const int fix_point, const float* __restrict__ partials,
+    const int max_blocks, const float* __restrict__ d_fix_first, Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_dX1_all,
+    Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const bool zero_dX)
+{
+    const Where w = where(blocks_per_replica);
+    const int n = count_of(d_n, w.replica, n_max);
+    const size_t base = (size_t)w.replica * n_max;
+    const int local = w.block * UPDATE_BLOCK + threadIdx.x;
+    if (w.block * UPDATE_BLOCK >= n) {  // (the whole workgroup)
+        if (zero_dX && local < n_max) d_dX_all[base + local] = ya::zero<Pt>();
+        return;
+    }
+    const float3 fix1 = resolve_fix<Pt>(kind, partials, max_blocks, w.replica, n, d_dX1_all + base, fix_point);
+    const float* fix_first = d_fix_first + 4 * (size_t)w.replica;
+    const float3 fix{fix_first[0], fix_first[1], fix_first[2]};
+    if (local < n) {
+        const size_t row = base + local;
+        const Pt dX_raw = d_dX_all[row];
+        if (zero_dX) d_dX_all[row] = ya::zero<Pt>();
+        const Pt dX = ya::minus_fix(dX_raw, fix);
+        const Pt dX1 = ya::minus_fix(d_dX1_all[row], fix1);
+        Pt X = d_X_all[row];
+        X += (dX + dX1) * 0.5 * dt;
+        d_X_all[row] = X;
+        d_old_v_all[row] = float3{(dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
+    } else if (zero_dX && local < n_max) {
+        d_dX_all[base + local] = ya::zero<Pt>();
+    }
+}
+
+// Lanes per cell of the force launch when the model leaves the choice to the engine and its functors are
+// stateless.  The coop kernels exist because ONE small system cannot fill the chip with one lane per
+// cell; an ensemble can, and the one-lane kernel does less work per pair.  So the rule looks at the whole
+// launch: `waves` = the wavefronts a one-lane launch would have, n_replicas * ceil(n_max / 64).
+// THE THRESHOLDS BELOW ARE PLACEHOLDERS until measured (profiles/ensemble_bench.json).
+inline int lanes_for(const int n_replicas, const int n_max)
+{
+    const size_t waves = (size_t)n_replicas * (size_t)((n_max + TILE_BLOCK - 1) / TILE_BLOCK);
+    if (waves >= 2048) return 1;
+    if (waves >= 256) return 16;
+    return n_max <= 4096 ? 64 : 16;
+}
+
+}  // namespace ens
+}  // namespace ya
+
+
+template<typename Pt, template<typename> class Solver = Tile_solver>
+class Ensemble {
+    static_assert(std::is_same<Solver<Pt>, Tile_solver<Pt>>::value,
+        "Ensemble steps all-pairs systems only: Ensemble<Pt, Tile_solver>");
+    static constexpr int n_floats = ya::N_floats<Pt>::value;
+
+public:
+    Pt* h_X;          // host mirror, n_replicas * n_max rows, replica-major (page-locked if the runtime grants it)
+    Pt* d_X;          // the same on the device
+    float3* d_old_v;  // velocities of the previous step, the same rows
+    int* const h_n;   // [n_replicas] cells of each replica
+    int* d_n;         // the same on the device: what the step reads
+    const int n_replicas;
+    const int n_max;  // capacity of EACH replica
+    // As Tile_computer::lanes_per_cell: 0 (default) = the engine's choice -- one lane per cell unless the
+    // functors are declared stateless (YA_STATELESS), then by the size of the whole launch
+    // (ya::ens::lanes_for); 1, 16 or 64 = that many lanes per cell whatever the functor says.  Any
+    // choice gives the same bits.
+    int lanes_per_cell = 0;
+
+    Ensemble(int n_replicas, int n_max) : h_n{(int*)malloc(sizeof(int) * (n_replicas > 0 ? n_replicas : 1))},
+        n_replicas{n_replicas}, n_max{n_max}
+    {
+        assert(n_replicas > 0 && n_max > 0);
+        // ids are ints (the functors' signature, gen_forces' n), and so is a launch's x dimension
+        const size_t total = rows();
+        assert(total <= (size_t)0x7fffffff);
+        assert((size_t)n_replicas * (size_t)((n_max + 3) / 4) <= (size_t)0x7fffffff);
+        for (int r = 0; r < n_replicas; r++) h_n[r] = n_max;
+        const size_t pts = total * sizeof(Pt);
+        h_X_locked = ya_host_alloc((void**)&h_X, pts) == 0;
+        if (h_X_locked)
+            memset((void*)h_X, 0, pts);
+        else
+            h_X = (Pt*)calloc(total, sizeof(Pt));
+        YA_CHECK(ya_malloc((void**)&d_X, pts));
+        YA_CHECK(ya_malloc((void**)&d_dX, pts));
+        YA_CHECK(ya_malloc((void**)&d_X1, pts));
+        YA_CHECK(ya_malloc((void**)&d_dX1, pts));
+        YA_CHECK(ya_malloc((void**)&d_old_v, total * sizeof(float3)));
+        YA_CHECK(ya_memset_async(d_old_v, 0, total * sizeof(float3), nullptr));
+        YA_CHECK(ya_malloc((void**)&d_n, (size_t)n_replicas * sizeof(int)));
+        YA_CHECK(ya_memset_async(d_n, 0, (size_t)n_replicas * sizeof(int), nullptr));
+        YA_CHECK(ya_malloc((void**)&d_fix_first, (size_t)n_replicas * 4 * sizeof(float)));
+        YA_CHECK(ya_malloc((void**)&d_partials, (size_t)n_replicas * max_blocks() * n_floats * sizeof(float)));
+    }
+    ~Ensemble()
+    {
+        if (h_X_locked)
+            (void)ya_host_free(h_X);
+        else
+            free(h_X);
+        free(h_n);
+        ya_free(d_X);
+        ya_free(d_dX);
+        ya_free(d_X1);
+        ya_free(d_dX1);
+        ya_free(d_old_v);
+        ya_free(d_n);
+        ya_free(d_fix_first);
+        ya_free(d_partials);
+    }
+    Ensemble(const Ensemble&) = delete;
+
+    size_t rows() const { return (size_t)n_replicas * (size_t)n_max; }
+    // row i of replica r in the host mirror (the same index serves d_X, d_old_v and a model's own arrays)
+    size_t index(int r, int i) const { return (size_t)r * (size_t)n_max + (size_t)i; }
+    Pt* row(int r, int i) { return h_X + index(r, i); }
+
+    void copy_to_device()
+    {
+        for (int r = 0; r < n_replicas; r++) assert(h_n[r] >= 0 && h_n[r] <= n_max);
+        YA_CHECK(ya_memcpy_h2d(d_X, h_X, rows() * sizeof(Pt)));
+        YA_CHECK(ya_memcpy_h2d(d_n, h_n, (size_t)n_replicas * sizeof(int)));
+    }
+    void copy_to_host()
+    {
+        YA_CHECK(ya_memcpy_d2h(h_X, d_X, rows() * sizeof(Pt)));
+        YA_CHECK(ya_memcpy_d2h(h_n, d_n, (size_t)n_replicas * sizeof(int)));
+        for (int r = 0; r < n_replicas; r++) assert(h_n[r] <= n_max);
+    }
+    // Blocking read of replica r's device-side count, for the host's own use: the step never calls it.
+    int get_d_n(int r)
+    {
+        assert(r >= 0 && r < n_replicas);
+        int n;
+        YA_CHECK(ya_get_n(d_n + r, &n));
+        assert(n <= n_max);
+        return n;
+    }
+
+    // Heun_solver's three modes, applied to EVERY replica with a LOCAL point id.  Precondition:
+    // point_id < n[r] for every replica that is not empty (a replica whose point does not exist would hold
+    // an unused row's right-hand side).  Semantics are Heun_solver's, quirks included: set_fixed_xy holds
+    // x and y in the first stage only -- the second stage holds the whole point -- and stays in force
+    // for later set_fixed calls (include/solvers.cuh, heun_stages / fix_velocity).
+    void set_fixed() { fix_com = true; }
+    void set_fixed(int point_id)
+    {
+        assert(point_id >= 0 && point_id < n_max);
+        fix_com = false;
+        fix_point = point_id;
+    }
+    void set_fixed_xy(int point_id)
+    {
+        assert(point_id >= 0 && point_id < n_max);
+        fix_com = false;
+        fix_com_z = true;
+        fix_point = point_id;
+    }
+
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_step(float dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_step<pw_int, friction_w_neighbour<Pt>>(dt, gen_forces);
+    }
+    // One Heun step of every replica.  Six launches (per stage: forces, partial sums, update), stream-ordered
+    // on the null stream; no copy to the host, no synchronisation, no allocation.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_step(float dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        const bool has_gen = !ya::is_no_gen_forces<Pt>(gen_forces);
+        const int update_blocks = (n_max + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
+        for (int stage = 1; stage <= 2; stage++) {
+            const Pt* d_in = stage == 1 ? d_X : d_X1;
+            Pt* d_rhs = stage == 1 ? d_dX : d_dX1;
+            if (has_gen) {
+                // (the update kernel before this stage may have left the rows zeroed already)
+                if (!rhs_zeroed[stage - 1]) YA_CHECK(ya_memset_async(d_rhs, 0, rows() * sizeof(Pt), nullptr));
+                gen_forces((int)rows(), d_in, d_rhs);
+            }
+            rhs_zeroed[stage - 1] = false;  // the force kernel writes it next
+            forces<pw_int, pw_friction>(d_in, d_rhs, has_gen);
+            // Heun_solver::heun_stages: set_fixed_xy(i) holds x and y in the first stage only
+            const bool xy = stage == 1 && fix_com_z;
+            const int kind = (fix_com && !fix_com_z) ? ya::ens::FIX_MEAN
+                             : xy                    ? ya::ens::FIX_POINT_XY
+                             : fix_com               ? ya::ens::FIX_MEAN
+                                                     : ya::ens::FIX_POINT;
+            if (kind != ya::ens::FIX_POINT)
+                ya::ens::reduce_partials_batched<n_floats><<<grid_of(max_blocks()), ya::UPDATE_BLOCK>>>(
+                    n_max, max_blocks(), d_n, reinterpret_cast<const float*>(d_rhs), d_partials);
+            if (stage == 1) {
+                ya::ens::euler_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n, dt,
+                    kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_X, d_X1, has_gen ? d_dX1 : nullptr);
+                rhs_zeroed[1] = has_gen;
+            } else {
+                ya::ens::heun_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n, dt,
+                    kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_dX1, d_X, d_old_v, has_gen);
+                rhs_zeroed[0] = has_gen;
+            }
+        }
+    }
+
+protected:
+    Pt *d_dX, *d_X1, *d_dX1;
+    float* d_fix_first;  // [n_replicas][4] stage 1's fixed velocity, left by the predictor for the corrector
+    float* d_partials;   // [n_replicas][max_blocks()][n_floats] partial sums of a stage's right-hand sides
+    bool h_X_locked = false;
+    bool fix_com = true;
+    bool fix_com_z = false;
+    int fix_point = 0;
+    // every row of d_dX / d_dX1 was left zeroed by an update kernel (take_step is their only writer)
+    bool rhs_zeroed[2] = {false, false};
+
+    int max_blocks() const { return ya::ens::reduce_blocks(n_max); }
+    dim3 grid_of(int blocks_per_replica) const { return dim3((unsigned)((size_t)n_replicas * blocks_per_replica)); }
+
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void forces(const Pt* d_in, Pt* d_rhs, const bool has_gen)
+    {
+        int lanes = lanes_per_cell;
+        if (lanes == 0) lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::lanes_for(n_replicas, n_max) : 1;
+        if (lanes >= 64) {
+            const int blocks = (n_max + 3) / 4;
+            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 64><<<grid_of(blocks), 256>>>(
+                n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
+        } else if (lanes > 1) {
+            const int blocks = (n_max + 15) / 16;
+            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 16><<<grid_of(blocks), 256>>>(
+                n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
+        } else {
+            const int blocks = (n_max + ya::TILE_BLOCK - 1) / ya::TILE_BLOCK;
+            ya::ens::tile_force_batched<Pt, pw_int, pw_friction><<<grid_of(blocks), ya::TILE_BLOCK>>>(
+                n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
+        }
+    }
+};

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""M small all-pairs systems per step: M single Solutions stepped one after the other against one Ensemble.
+
+    python tools/ensemble_bench.py [--out profiles/ensemble_bench.json] [--window 0.3] [--repeats 3]
+    python tools/ensemble_bench.py --trace-shape 64 800 --steps 50     # what a rocprofv3 run wraps
+
+In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
+  A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
+     without the ensemble (each step begins with its blocking 4-byte read of n and queues six launches);
+  B  one Ensemble("relu", M, n): six launches per step for all replicas, nothing read by the host;
+     with tile_lanes 0 (the engine's choice, ya::ens::lanes_for), 1, 16 and 64.
+A timed window is K steps between two synchronisations under a host clock, K calibrated so that a window lasts
+at least --window seconds; --repeats windows per setting, the median reported with the spread
+(max - min) / median.  Cells are a seeded random ball per replica (all-pairs cost does not depend on positions).
+The figure is cell-updates per second: M * n * K / seconds.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from yalla_amd.ensemble import Ensemble  # noqa: E402
+from yalla_amd.solution import Solution  # noqa: E402
+
+SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
+LANES = (0, 1, 16, 64)
+DT = 0.01
+
+
+def ball(n, seed):
+    rng = np.random.default_rng(seed)
+    direction = rng.normal(size=(n, 3))
+    direction /= np.linalg.norm(direction, axis=1)[:, None]
+    radius = 0.75 * (n / 0.64) ** (1 / 3) / 2 * rng.random(n) ** (1 / 3)
+    return (direction * radius[:, None]).astype(np.float32)
+
+
+class Singles:
+    def __init__(self, m, n):
+        self.sims = [Solution("relu_tile", n) for _ in range(m)]
+        for r, s in enumerate(self.sims):
+            s.h_X[:] = ball(n, r)
+            s.copy_to_device()
+
+    def steps(self, k):
+        for _ in range(k):
+            for s in self.sims:
+                s.take_step(DT, 1)
+        self.sims[0].synchronize()
+
+    def close(self):
+        for s in self.sims:
+            s.close()
+
+
+class Together:
+    def __init__(self, m, n):
+        self.ens = Ensemble("relu", m, n)
+        for r in range(m):
+            self.ens.h_X[r] = ball(n, r)
+        self.ens.copy_to_device()
+
+    def lanes(self, lanes):
+        self.ens.set_param("tile_lanes", lanes)
+
+    def steps(self, k):
+        self.ens.take_step(DT, k)
+        self.ens.synchronize()
+
+    def close(self):
+        self.ens.close()
+
+
+def timed(run, k):
+    t0 = time.perf_counter()
+    run.steps(k)
+    return time.perf_counter() - t0
+
+
+def calibrate(run, window):
+    k = 4
+    while True:
+        t = timed(run, k)
+        if t >= window:
+            return k
+        k = max(k + 1, int(k * min(8.0, 1.25 * window / max(t, 1e-6))))
+
+
+def summary(samples, cells_per_step, k):
+    rates = sorted(cells_per_step * k / t for t in samples)
+    median = rates[len(rates) // 2]
+    return {"steps_per_window": k, "seconds": [round(t, 6) for t in samples],
+            "cell_updates_per_s": median, "spread": (rates[-1] - rates[0]) / median,
+            "us_per_step": 1e6 * sorted(samples)[len(samples) // 2] / k}
+
+
+def measure(m, n, window, repeats):
+    a, b = Singles(m, n), Together(m, n)
+    try:
+        a.steps(3)
+        ks = {"A": calibrate(a, window)}
+        for lanes in LANES:
+            b.lanes(lanes)
+            b.steps(3)
+            ks[lanes] = calibrate(b, window)
+        samples = {key: [] for key in ks}
+        for _ in range(repeats):  # A, B0, B1, B16, B64, A, ...
+            samples["A"].append(timed(a, ks["A"]))
+            for lanes in LANES:
+                b.lanes(lanes)
+                samples[lanes].append(timed(b, ks[lanes]))
+    finally:
+        a.close()
+        b.close()
+    row = {"n_replicas": m, "n": n, "singles": summary(samples["A"], m * n, ks["A"])}
+    for lanes in LANES:
+        row[f"ensemble_lanes_{lanes}"] = summary(samples[lanes], m * n, ks[lanes])
+    for lanes in LANES:
+        row[f"ratio_lanes_{lanes}"] = row[f"ensemble_lanes_{lanes}"]["cell_updates_per_s"] / row["singles"]["cell_updates_per_s"]
+    row["ratio"] = row["ratio_lanes_0"]  # the engine's choice against the sequential loop
+    row["spread"] = max(row["singles"]["spread"], row["ensemble_lanes_0"]["spread"])
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--window", type=float, default=0.3)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--shapes", default=None, help="M:n,M:n,... instead of the full sweep")
+    ap.add_argument("--trace-shape", type=int, nargs=2, metavar=("M", "N"), default=None,
+                    help="only step one Ensemble of this shape --steps times (for a kernel trace)")
+    ap.add_argument("--steps", type=int, default=50)
+    args = ap.parse_args()
+
+    if args.trace_shape:
+        b = Together(*args.trace_shape)
+        b.steps(args.steps)
+        b.close()
+        print(json.dumps({"traced": {"n_replicas": args.trace_shape[0], "n": args.trace_shape[1], "steps": args.steps}}))
+        return
+
+    shapes = SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape: code objects loaded, allocator and clocks settled
+        for run in (Singles(m, n), Together(m, n)):
+            run.steps(5)
+            run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure(m, n, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   singles {r['singles']['us_per_step']:10.1f} us/step   ensemble "
+              + "  ".join(f"L{lanes}: {r[f'ensemble_lanes_{lanes}']['us_per_step']:9.1f}" for lanes in LANES)
+              + f"   ratio {r['ratio']:.2f}  spread {r['spread']:.3f}", flush=True)
+    result = {"tool": "tools/ensemble_bench.py", "model": "relu", "dt": DT, "window_s": args.window,
+              "repeats": args.repeats, "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio": min(r["ratio"] for r in rows)}))
+
+
+if __name__ == "__main__":
+    main()

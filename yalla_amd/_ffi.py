@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEVICE_LIB = os.environ.get("YALLA_MODELS_LIB") or os.path.join(_HERE, "libyalla_models.so")
 DEVICE_LIB_FAST = os.path.join(_HERE, "libyalla_models_fast.so")  # the fast-arithmetic tier
 CORE_LIB = os.path.join(_HERE, "libyalla_hip.so")
+ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ensemble.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -66,6 +67,28 @@ MODELS_ABI = {
     "ya_sim_graph_launches": (C.c_long, [_sim]),
 }
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble.h one to one.
+_ens = C.c_void_p
+ENSEMBLE_ABI = {
+    "ya_ens_models_count": (C.c_int, []),
+    "ya_ens_models_name": (C.c_char_p, [C.c_int]),
+    "ya_ens_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_ens)]),
+    "ya_ens_destroy": (None, [_ens]),
+    "ya_ens_n_floats": (C.c_int, [_ens]),
+    "ya_ens_h_X": (_pf, [_ens]),
+    "ya_ens_set_h_n": (C.c_int, [_ens, C.c_int, C.c_int]),
+    "ya_ens_get_h_n": (C.c_int, [_ens, C.c_int]),
+    "ya_ens_get_d_n": (C.c_int, [_ens, C.c_int]),
+    "ya_ens_copy_to_device": (C.c_int, [_ens]),
+    "ya_ens_copy_to_host": (C.c_int, [_ens]),
+    "ya_ens_take_steps": (C.c_int, [_ens, C.c_float, C.c_int]),
+    "ya_ens_synchronize": (C.c_int, [_ens]),
+    "ya_ens_set_fixed": (C.c_int, [_ens, C.c_int, C.c_int]),
+    "ya_ens_get_old_v": (C.c_int, [_ens, _pf]),
+    "ya_ens_set_old_v": (C.c_int, [_ens, _pf]),
+    "ya_ens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
+}
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -114,3 +137,22 @@ def device_lib(arith="exact"):
             raise RuntimeError(f"{path} is not the {arith}-arithmetic HIP build")
         _device[arith] = lib
     return _device[arith]
+
+
+_ensemble = []
+
+
+def ensemble_lib():
+    """The ensemble harness, yalla_amd/libyalla_ensemble.so (include/yalla_ensemble.h), every entry
+    point typed.  Raises if it has not been built: there is no fallback."""
+    if not _ensemble:
+        if not os.path.exists(ENSEMBLE_LIB):
+            raise FileNotFoundError(
+                f"{ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
+        lib = C.CDLL(ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
+        for name, (res, args) in ENSEMBLE_ABI.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
+        _ensemble.append(lib)
+    return _ensemble[0]

@@ -1,0 +1,241 @@
+// libyalla_ensemble.so -- the ensemble harness (include/yalla_ensemble.h): Ensemble<Pt, Tile_solver>
+// (include/ensemble.cuh) instantiated for the functor / friction pairs of the `*_tile` models of the same
+// names in libyalla_models.so (model_functors.h is included read-only for the functors and their
+// YA_STATELESS declarations).  Links against libyalla_hip.so.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <string>
+
+#include "dtypes.cuh"
+#include "inits.cuh"
+#include "links.cuh"
+#include "property.cuh"
+#include "solvers.cuh"
+#include "ensemble.cuh"
+
+#include "model_functors.h"
+
+#include "yalla_ensemble.h"
+
+namespace ens_harness {
+
+struct Base {
+    virtual ~Base() {}
+    virtual int n_floats() = 0;
+    virtual int n_replicas() = 0;
+    virtual int n_max() = 0;
+    virtual float* h_X() = 0;
+    virtual int* h_n() = 0;
+    virtual void copy_to_device() = 0;
+    virtual void copy_to_host() = 0;
+    virtual int get_d_n(int r) = 0;
+    virtual void take_steps(float dt, int n_steps) = 0;
+    virtual void set_fixed(int mode, int point) = 0;
+    virtual float3* d_old_v() = 0;
+    virtual void set_lanes(int lanes) = 0;
+};
+
+template<typename Pt>
+struct No_gen {
+    static Generic_forces<Pt> gen(int, int) { return no_gen_forces<Pt>; }
+    static void before_steps(int) {}
+};
+
+// models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
+// (i = r * n_max + local), so the ensemble's model hands the functor the local ones: the same statements, hence
+// the bits of oscillator_tile in every replica.  n_max travels in a device variable, set when it changes.
+__device__ int oscillator_rows_per_replica = 1;
+__device__ inline float4 oscillator_by_local_id(float4 Xi, float4 r, float dist, int i, int j)
+{
+    return models::oscillator(Xi, r, dist, i % oscillator_rows_per_replica, j % oscillator_rows_per_replica);
+}
+struct Oscillator_ids : public No_gen<float4> {
+    static void before_steps(int n_max)
+    {
+        static int rows_set = 1;
+        if (rows_set == n_max) return;
+        YA_CHECK((int)hipMemcpyToSymbol(HIP_SYMBOL(oscillator_rows_per_replica), &n_max, sizeof(int)));
+        rows_set = n_max;
+    }
+};
+// The generic force of the `push_tile` model (models::push: the right-hand side of cell 1 set to (1, 0, 0)) for
+// an ensemble: ONE call on the flat arrays pushes cell 1 of every replica, global row r * n_max + 1.
+template<typename Pt>
+__global__ void push_cell_1_of_every_replica(const int n_replicas, const int n_max, Pt* d_dX)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_replicas) return;
+    Pt* row = d_dX + (size_t)r * n_max + 1;
+    row->x = 1;
+    row->y = 0;
+    row->z = 0;
+}
+template<typename Pt>
+struct Push_gen {
+    static Generic_forces<Pt> gen(int n_replicas, int n_max)
+    {
+        return [n_replicas, n_max](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
+            if (n_max < 2 || n != n_replicas * n_max) return;
+            push_cell_1_of_every_replica<Pt><<<(n_replicas + 255) / 256, 256>>>(n_replicas, n_max, d_dX);
+        };
+    }
+    static void before_steps(int) {}
+};
+
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
+struct Sim : public Base {
+    Ensemble<Pt> cells;
+    Sim(int n_replicas, int n_max) : cells{n_replicas, n_max} {}
+    int n_floats() override { return sizeof(Pt) / sizeof(float); }
+    int n_replicas() override { return cells.n_replicas; }
+    int n_max() override { return cells.n_max; }
+    float* h_X() override { return reinterpret_cast<float*>(cells.h_X); }
+    int* h_n() override { return cells.h_n; }
+    void copy_to_device() override { cells.copy_to_device(); }
+    void copy_to_host() override { cells.copy_to_host(); }
+    int get_d_n(int r) override { return cells.get_d_n(r); }
+    void take_steps(float dt, int n_steps) override
+    {
+        Policy::before_steps(cells.n_max);
+        Generic_forces<Pt> gen = Policy::gen(cells.n_replicas, cells.n_max);
+        for (int s = 0; s < n_steps; s++) cells.template take_step<pw_int, pw_friction>(dt, gen);
+    }
+    void set_fixed(int mode, int point) override
+    {
+        if (mode == 0) cells.set_fixed();
+        if (mode == 1) cells.set_fixed(point);
+        if (mode == 2) cells.set_fixed_xy(point);
+    }
+    float3* d_old_v() override { return cells.d_old_v; }
+    void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
+};
+
+using Factory = Base* (*)(int, int);
+struct Model {
+    const char* name;
+    Factory make;
+};
+template<typename S>
+Base* make_sim(int n_replicas, int n_max)
+{
+    return new S{n_replicas, n_max};
+}
+#define YA_ENS_MODEL(name, Pt, pw_int, pw_friction, Policy) \
+    Model { name, &make_sim<Sim<Pt, pw_int, pw_friction, Policy>> }
+
+static const Model model_table[] = {
+    YA_ENS_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENS_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENS_MODEL("fading", float3, models::fading_spring, friction_on_background<float3>, No_gen<float3>),
+    YA_ENS_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENS_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
+    YA_ENS_MODEL("oscillator", float4, oscillator_by_local_id, friction_w_neighbour<float4>, Oscillator_ids),
+    YA_ENS_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
+};
+static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
+
+}  // namespace ens_harness
+
+struct ya_ens {
+    std::unique_ptr<ens_harness::Base> p;
+};
+
+extern "C" {
+
+int ya_ens_models_count(void) { return ens_harness::n_models; }
+const char* ya_ens_models_name(int i)
+{
+    return (i >= 0 && i < ens_harness::n_models) ? ens_harness::model_table[i].name : nullptr;
+}
+
+int ya_ens_create(const char* model, int n_replicas, int n_max, ya_ens** out)
+{
+    if (!model || !out || n_replicas <= 0 || n_max <= 0) return -3;
+    // ids and launch sizes are ints (include/ensemble.cuh)
+    if ((size_t)n_replicas * (size_t)n_max > (size_t)0x7fffffff) return -3;
+    if ((size_t)n_replicas * (size_t)((n_max + 3) / 4) > (size_t)0x7fffffff) return -3;
+    for (int i = 0; i < ens_harness::n_models; i++) {
+        if (std::string(model) == ens_harness::model_table[i].name) {
+            ya_ens* e = new ya_ens;
+            e->p.reset(ens_harness::model_table[i].make(n_replicas, n_max));
+            *out = e;
+            return 0;
+        }
+    }
+    return -1;
+}
+void ya_ens_destroy(ya_ens* ens) { delete ens; }
+
+int ya_ens_n_floats(ya_ens* e) { return e->p->n_floats(); }
+float* ya_ens_h_X(ya_ens* e) { return e->p->h_X(); }
+int ya_ens_set_h_n(ya_ens* e, int r, int n)
+{
+    if (r < 0 || r >= e->p->n_replicas() || n < 0 || n > e->p->n_max()) return -3;
+    e->p->h_n()[r] = n;
+    return 0;
+}
+int ya_ens_get_h_n(ya_ens* e, int r)
+{
+    if (r < 0 || r >= e->p->n_replicas()) return -3;
+    return e->p->h_n()[r];
+}
+int ya_ens_get_d_n(ya_ens* e, int r)
+{
+    if (r < 0 || r >= e->p->n_replicas()) return -3;
+    return e->p->get_d_n(r);
+}
+int ya_ens_copy_to_device(ya_ens* e)
+{
+    e->p->copy_to_device();
+    return 0;
+}
+int ya_ens_copy_to_host(ya_ens* e)
+{
+    e->p->copy_to_host();
+    return 0;
+}
+int ya_ens_take_steps(ya_ens* e, float dt, int n_steps)
+{
+    e->p->take_steps(dt, n_steps);
+    return 0;
+}
+int ya_ens_synchronize(ya_ens*)
+{
+    YA_CHECK(ya_device_synchronize());
+    return 0;
+}
+int ya_ens_set_fixed(ya_ens* e, int mode, int local_point)
+{
+    if (mode < 0 || mode > 2) return -3;
+    if (mode != 0 && (local_point < 0 || local_point >= e->p->n_max())) return -3;
+    e->p->set_fixed(mode, local_point);
+    return 0;
+}
+int ya_ens_get_old_v(ya_ens* e, float* out)
+{
+    if (!out) return -3;
+    YA_CHECK(ya_device_synchronize());
+    YA_CHECK(ya_memcpy_d2h(out, e->p->d_old_v(), (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
+    return 0;
+}
+int ya_ens_set_old_v(ya_ens* e, const float* in)
+{
+    if (!in) return -3;
+    YA_CHECK(ya_device_synchronize());
+    YA_CHECK(ya_memcpy_h2d(e->p->d_old_v(), in, (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
+    return 0;
+}
+int ya_ens_set_param(ya_ens* e, const char* name, double v)
+{
+    if (!name) return -3;
+    if (std::string(name) == "tile_lanes") {
+        const int lanes = (int)v;
+        if (lanes != 0 && lanes != 1 && lanes != 16 && lanes != 64) return -3;
+        e->p->set_lanes(lanes);
+        return 0;
+    }
+    return -2;
+}
+
+}  // extern "C"

@@ -1,0 +1,152 @@
+"""Host-side mirror of `Ensemble<Pt, Tile_solver>` (include/ensemble.cuh) over the ensemble C ABI
+(include/yalla_ensemble.h): M independent all-pairs systems of one model in one allocation, advanced
+together by the same six launches per step whatever M is, with nothing read by the host.
+
+It mirrors `Solution`: `h_X` is the host mirror, here an `(n_replicas, n_max, n_floats)` view;
+`h_n[r]` the host-side count of replica r; `copy_to_device()` / `copy_to_host()` move every row and
+every count; `take_step(dt, steps)` advances every replica; `set_fixed*` take an id LOCAL to a
+replica and apply to every replica.  Each replica holds, bit for bit, what a
+`Solution("<model>_tile", n_max)` given the same rows holds.
+
+    with Ensemble("relu", n_replicas=64, n_max=800) as cells:
+        cells.h_X[r, :n, :3] = ...; cells.h_n[r] = n
+        cells.copy_to_device()
+        cells.take_step(0.05, 100)
+        X = cells.positions(r)
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from .solution import YallaError, _check
+
+
+class _Counts:
+    """h_n of an Ensemble: an array-like over the library's own host counts."""
+
+    def __init__(self, ens):
+        self._ens = ens
+
+    def __len__(self):
+        return self._ens.n_replicas
+
+    def _index(self, r):
+        r = int(r)
+        if r < 0:
+            r += len(self)
+        if not 0 <= r < len(self):
+            raise IndexError(r)
+        return r
+
+    def __getitem__(self, r):
+        if isinstance(r, slice):
+            return [self[k] for k in range(*r.indices(len(self)))]
+        return self._ens.lib.ya_ens_get_h_n(self._ens._h, self._index(r))
+
+    def __setitem__(self, r, n):
+        if isinstance(r, slice):
+            ks = range(*r.indices(len(self)))
+            ns = np.broadcast_to(np.asarray(n), (len(ks),))
+            for k, v in zip(ks, ns):
+                self[k] = v
+            return
+        _check(self._ens.lib.ya_ens_set_h_n(self._ens._h, self._index(r), int(n)), "set h_n")
+
+    def __iter__(self):
+        return (self[r] for r in range(len(self)))
+
+    def __array__(self, dtype=None, copy=None):
+        return np.array(list(self), dtype=dtype or np.int32)
+
+
+class Ensemble:
+    def __init__(self, model, n_replicas, n_max, lib=None):
+        self.lib = lib if lib is not None else _ffi.ensemble_lib()
+        self.model = model
+        handle = C.c_void_p()
+        code = self.lib.ya_ens_create(model.encode(), int(n_replicas), int(n_max), C.byref(handle))
+        if code == -1:
+            raise YallaError(f"unknown ensemble model {model!r}; known: {models(self.lib)}")
+        _check(code, "ya_ens_create")
+        self._h = handle
+        self.n_replicas = int(n_replicas)
+        self.n_max = int(n_max)
+        self.n_floats = self.lib.ya_ens_n_floats(self._h)
+        ptr = self.lib.ya_ens_h_X(self._h)
+        self.h_X = np.ctypeslib.as_array(ptr, shape=(self.n_replicas, self.n_max, self.n_floats))
+        self.h_n = _Counts(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.h_X = None
+            self.lib.ya_ens_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def copy_to_device(self):
+        _check(self.lib.ya_ens_copy_to_device(self._h), "copy_to_device")
+
+    def copy_to_host(self):
+        _check(self.lib.ya_ens_copy_to_host(self._h), "copy_to_host")
+
+    def get_d_n(self, r):
+        """Blocking read of replica r's device-side count (the step itself never reads it)."""
+        n = self.lib.ya_ens_get_d_n(self._h, int(r))
+        if n < 0:
+            raise YallaError(f"get_d_n({r}) failed with harness code {n}")
+        return n
+
+    def take_step(self, dt, steps=1):
+        _check(self.lib.ya_ens_take_steps(self._h, float(dt), int(steps)), "take_step")
+
+    def synchronize(self):
+        _check(self.lib.ya_ens_synchronize(self._h), "synchronize")
+
+    def set_fixed(self, local_id=None):
+        """set_fixed() holds every replica's centre of mass, set_fixed(i) cell i of every replica
+        (i must exist in every replica that is not empty)."""
+        if local_id is None:
+            _check(self.lib.ya_ens_set_fixed(self._h, 0, 0), "set_fixed")
+        else:
+            _check(self.lib.ya_ens_set_fixed(self._h, 1, int(local_id)), "set_fixed")
+
+    def set_fixed_xy(self, local_id):
+        _check(self.lib.ya_ens_set_fixed(self._h, 2, int(local_id)), "set_fixed_xy")
+
+    def set_param(self, name, value):
+        _check(self.lib.ya_ens_set_param(self._h, name.encode(), float(value)), "set_param")
+        return 0
+
+    def positions(self, r=None):
+        """copy_to_host() and a copy of replica r's rows h_X[r, :h_n[r]] (every replica's, as a list,
+        without r)."""
+        self.copy_to_host()
+        if r is None:
+            return [self.h_X[k, : self.h_n[k]].copy() for k in range(self.n_replicas)]
+        return self.h_X[r, : self.h_n[r]].copy()
+
+    def old_v(self):
+        out = np.empty((self.n_replicas, self.n_max, 3), dtype=np.float32)
+        _check(self.lib.ya_ens_get_old_v(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "get_old_v")
+        return out
+
+    def set_old_v(self, v):
+        v = np.ascontiguousarray(v, dtype=np.float32).reshape(self.n_replicas, self.n_max, 3)
+        _check(self.lib.ya_ens_set_old_v(self._h, v.ctypes.data_as(C.POINTER(C.c_float))), "set_old_v")
+
+
+def models(lib=None):
+    lib = lib if lib is not None else _ffi.ensemble_lib()
+    return [lib.ya_ens_models_name(i).decode() for i in range(lib.ya_ens_models_count())]
