@@ -29,7 +29,10 @@
 // own rows), the centre of mass in ya_reduce_partials' order (B_r = clamp(ceil(n_r / 256), 1, 1024)
 // blocks of the replica's rows, fold256, then the update kernels' fold of the B_r partials), the
 // updates are Heun_solver's statements: each replica holds the bits a Solution<Pt, Tile_solver>
-// run of the same rows holds (tests/test_ensemble_gpu.py, tests/native_ensemble).
+// run of the same rows holds (tests/test_ensemble_gpu.py, tests/native_ensemble).  The force loops, the
+// fold and the corrector's row are the single-system kernels' own device functions (solvers.cuh:
+// tile_force_rows, tile_force_coop_rows, heun_row; fold256.cuh): the kernels here add only where a
+// workgroup finds its replica's rows, its count and its id offset.
 //
 // Not here ("Ensembles"): Grid_solver / Gabriel_solver ensembles (the Solver
 // template parameter is their door), the fast-arithmetic tier, graph capture, a per-replica dt, slabs.
@@ -57,197 +60,40 @@ __device__ __forceinline__ int count_of(const int* __restrict__ d_n, const int r
 
 // ya::tile_force for every replica at once: a workgroup serves 64 cells of ONE replica, tiles of
 // TILE_POINTS partners come from that replica's rows only, j ascending, the functor is called for every
-// (i, j) including i == j, ids are ensemble-global.  The loop is tile_force's, restated (the existing
-// kernels stay untouched, and so do their registers: profiles/ensemble_resource_usage.txt).
+// (i, j) including i == j, ids are ensemble-global.  The loop is tile_force's own (ya::tile_force_rows).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
 __global__ __launch_bounds__(TILE_BLOCK) void tile_force_batched(const int n_max, const int blocks_per_replica,
     const int* __restrict__ d_n, const Pt* __restrict__ d_X_all, const float3* __restrict__ d_old_v_all,
     Pt* __restrict__ d_dX_all, const bool has_gen)
 {
-    __shared__ Pt sh_X[TILE_POINTS];
-    __shared__ float3 sh_v[TILE_POINTS];
-
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
     if (w.block * TILE_BLOCK >= n) return;  // (the whole workgroup: blocks past n[r] return at once)
     const size_t base = (size_t)w.replica * n_max;
-    const Pt* __restrict__ d_X = d_X_all + base;
-    const float3* __restrict__ d_old_v = d_old_v_all + base;
-    Pt* __restrict__ d_dX = d_dX_all + base;
-    const int id_base = (int)base;
-
-    const int local = w.block * TILE_BLOCK + threadIdx.x;
-    const int i = id_base + local;
-    Pt Xi = ya::zero<Pt>();
-    if (local < n) Xi = d_X[local];
-    Pt F = ya::zero<Pt>();
-    float3 sum_v{0.f, 0.f, 0.f};
-    float sum_friction = 0;
-    for (int tile_start = 0; tile_start < n; tile_start += TILE_POINTS) {
-        const int n_tile = min(TILE_POINTS, n - tile_start);
-        __syncthreads();
-        for (int k = threadIdx.x; k < n_tile; k += TILE_BLOCK) {
-            sh_X[k] = d_X[tile_start + k];
-            sh_v[k] = d_old_v[tile_start + k];
-        }
-        __syncthreads();
-        if (local < n) {
-#pragma unroll YA_TILE_UNROLL
-            for (int k = 0; k < n_tile; k++) {
-                const int j = id_base + tile_start + k;
-                Pt r = Xi - sh_X[k];
-                float dist = dist3(r.x, r.y, r.z);
-                F += pw_int(Xi, r, dist, i, j);
-                float friction = pw_friction(Xi, r, dist, i, j);
-                sum_friction += friction;
-                if (friction != 0) {
-                    float3 v = sh_v[k];
-                    sum_v.x += friction * v.x;
-                    sum_v.y += friction * v.y;
-                    sum_v.z += friction * v.z;
-                }
-            }
-        }
-    }
-    if (local < n) store_rhs(d_dX, local, has_gen, F, sum_v, sum_friction);
+    tile_force_rows<Pt, pw_int, pw_friction>(
+        n, w.block, (int)base, d_X_all + base, d_old_v_all + base, d_dX_all + base, has_gen);
 }
 
 // ya::tile_force_coop for every replica at once: a 256-thread workgroup owns 16 or 4 cells of ONE replica.
-// tile_force_coop's two phases, restated: the lanes of a cell leave a tile's pair terms in LDS, one lane per
-// component adds them in ascending j -- the sums of tile_force_batched, bit for bit.
+// tile_force_coop's own two phases (ya::tile_force_coop_rows): the lanes of a cell leave a tile's pair terms
+// in LDS, one lane per component adds them in ascending j -- the sums of tile_force_batched, bit for bit.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
 __global__ __launch_bounds__(256) void tile_force_coop_batched(const int n_max, const int blocks_per_replica,
     const int* __restrict__ d_n, const Pt* __restrict__ d_X_all, const float3* __restrict__ d_old_v_all,
     Pt* __restrict__ d_dX_all, const bool has_gen)
 {
-    constexpr int COOP_CELLS = 256 / COOP_LANES;
-    constexpr int NF = N_floats<Pt>::value;
-    constexpr int NC = NF + 4;  // components summed per cell: F (NF), friction, friction * old_v (3)
-    // partners per tile: a multiple of 64 whose terms fill at most 56 KiB of LDS
-    constexpr int TILE = (57344 / (COOP_CELLS * NC * 4)) / 64 * 64 > 512 ? 512 : (57344 / (COOP_CELLS * NC * 4)) / 64 * 64;
-    static_assert(TILE >= 64, "point type too large for tile_force_coop_batched");
-    constexpr int THREADS = COOP_CELLS * COOP_LANES;
-    constexpr int LOADS = (TILE + THREADS - 1) / THREADS;  // partners a thread carries per tile
-    constexpr int SLOTS = (NC + COOP_LANES - 1) / COOP_LANES;
-    __shared__ __attribute__((aligned(16))) float sh_part[COOP_CELLS][NC][TILE];  // one tile's terms, [cell][component][j]
-    __shared__ Pt sh_X[TILE];                        // the tile's partners
-    __shared__ float3 sh_v[TILE];
-    __shared__ float sh_sum[COOP_CELLS][NC];
-
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
-    if (w.block * COOP_CELLS >= n) return;  // (the whole workgroup)
+    if (w.block * (256 / COOP_LANES) >= n) return;  // (the whole workgroup)
     const size_t base = (size_t)w.replica * n_max;
-    const Pt* __restrict__ d_X = d_X_all + base;
-    const float3* __restrict__ d_old_v = d_old_v_all + base;
-    Pt* __restrict__ d_dX = d_dX_all + base;
-    const int id_base = (int)base;
-
-    const int cell = threadIdx.x / COOP_LANES, lane = threadIdx.x % COOP_LANES;
-    const int local = w.block * COOP_CELLS + cell;
-    const int i = id_base + local;
-    const bool active = local < n;
-    Pt Xi = ya::zero<Pt>();
-    if (active) Xi = d_X[local];
-    float acc[SLOTS];  // this lane's component sums (components lane, lane + COOP_LANES, ...)
-#pragma unroll
-    for (int a = 0; a < SLOTS; a++) acc[a] = 0.f;
-
-    // the next tile's partners travel from global memory while the current tile is worked on
-    Pt x_next[LOADS];
-    float3 v_next[LOADS];
-#pragma unroll
-    for (int k = 0; k < LOADS; k++) {
-        const int j = threadIdx.x + k * THREADS;
-        x_next[k] = ya::zero<Pt>();
-        v_next[k] = float3{0.f, 0.f, 0.f};
-        if (j < TILE && j < n) {
-            x_next[k] = d_X[j];
-            v_next[k] = d_old_v[j];
-        }
-    }
-    for (int tile_start = 0; tile_start < n; tile_start += TILE) {
-        const int n_tile = min(TILE, n - tile_start);
-#pragma unroll
-        for (int k = 0; k < LOADS; k++) {
-            const int t = threadIdx.x + k * THREADS;
-            if (t < TILE) {
-                sh_X[t] = x_next[k];
-                sh_v[t] = v_next[k];
-                const int j_next = tile_start + TILE + t;
-                if (j_next < n) {
-                    x_next[k] = d_X[j_next];
-                    v_next[k] = d_old_v[j_next];
-                }
-            }
-        }
-        __syncthreads();
-        // (a) the tile's pair terms: lane l takes partners l, l + COOP_LANES, ...
-        if (active) {
-#pragma unroll 4
-            for (int jj = lane; jj < n_tile; jj += COOP_LANES) {
-                const int j = id_base + tile_start + jj;
-                Pt r = Xi - sh_X[jj];
-                float dist = dist3(r.x, r.y, r.z);
-                const Pt f = pw_int(Xi, r, dist, i, j);
-                const float friction = pw_friction(Xi, r, dist, i, j);
-#pragma unroll
-                for (int c = 0; c < NF; c++) sh_part[cell][c][jj] = field(f, c);
-                sh_part[cell][NF][jj] = friction;
-                // the old_v term only where the friction is not zero: a +0 term instead changes no bit of a
-                // sum that started at +0 (ya::tile_force_coop)
-                const float3 v = sh_v[jj];
-                sh_part[cell][NF + 1][jj] = friction != 0 ? friction * v.x : 0.f;
-                sh_part[cell][NF + 2][jj] = friction != 0 ? friction * v.y : 0.f;
-                sh_part[cell][NF + 3][jj] = friction != 0 ? friction * v.z : 0.f;
-            }
-        }
-        __syncthreads();
-        // (b) one lane per component adds the tile's terms in ascending j
-#pragma unroll
-        for (int a = 0; a < SLOTS; a++) {
-            const int c = lane + COOP_LANES * a;
-            if (c < NC && active) {
-                float sum = acc[a];
-                const float4* terms = reinterpret_cast<const float4*>(&sh_part[cell][c][0]);
-                int jj = 0;
-                for (; jj + 16 <= n_tile; jj += 16) {
-                    float4 p[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) p[u] = terms[jj / 4 + u];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        sum += p[u].x;
-                        sum += p[u].y;
-                        sum += p[u].z;
-                        sum += p[u].w;
-                    }
-                }
-                for (; jj < n_tile; jj++) sum += sh_part[cell][c][jj];
-                acc[a] = sum;
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < SLOTS; a++) {
-        const int c = lane + COOP_LANES * a;
-        if (c < NC) sh_sum[cell][c] = acc[a];
-    }
-    __syncthreads();
-    if (active && lane == 0) {
-        Pt F;
-#pragma unroll
-        for (int c = 0; c < NF; c++) field(F, c) = sh_sum[cell][c];
-        store_rhs(d_dX, local, has_gen, F,
-            float3{sh_sum[cell][NF + 1], sh_sum[cell][NF + 2], sh_sum[cell][NF + 3]}, sh_sum[cell][NF]);
-    }
+    tile_force_coop_rows<Pt, pw_int, pw_friction, COOP_LANES>(
+        n, w.block, (int)base, d_X_all + base, d_old_v_all + base, d_dX_all + base, has_gen);
 }
 
 // Partial sums of every replica's right-hand sides in one launch, in exactly the order of
-// libyalla_hip.so's k_reduce_partial (restated: that library's ABI is not extended for this): replica r
-// uses B_r = clamp(ceil(n_r / 256), 1, 1024) of its `max_blocks` workgroups, lane (b, t) sums the
-// replica's rows 256 b + t, += 256 B_r, the 256 lanes are folded by halving (fold256).  The partials of
+// libyalla_hip.so's k_reduce_partial (that library's ABI is not extended for this; the fold is the one both
+// call, ya::fold256): replica r uses B_r = clamp(ceil(n_r / 256), 1, 1024) of its `max_blocks` workgroups, lane
+// (b, t) sums the replica's rows 256 b + t, += 256 B_r, the 256 lanes are folded by halving.  The partials of
 // replica r are rows [r * max_blocks, r * max_blocks + B_r) of the workspace.
 constexpr int REDUCE_MAX_BLOCKS = 1024;
 __host__ __device__ __forceinline__ int reduce_blocks(const int n)
@@ -259,7 +105,6 @@ template<int NW>
 __global__ __launch_bounds__(UPDATE_BLOCK) void reduce_partials_batched(const int n_max, const int max_blocks,
     const int* __restrict__ d_n, const float* __restrict__ v_all, float* __restrict__ partials)
 {
-    static_assert(UPDATE_BLOCK == 256, "the fold is libyalla_hip.so's fold256");
     __shared__ float sh[NW * UPDATE_BLOCK];
     const Where w = where(max_blocks);
     const int n = count_of(d_n, w.replica, n_max);
@@ -275,31 +120,9 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void reduce_partials_batched(const in
 #pragma unroll
         for (int k = 0; k < NW; k++) acc[k] = acc[k] + p[k];
     }
-    // fold256: lane[t] += lane[t + s] for s = 128 ... 1, from s = 32 down by shuffle
-#pragma unroll
-    for (int k = 0; k < NW; k++) sh[k * UPDATE_BLOCK + threadIdx.x] = acc[k];
-    __syncthreads();
-    if ((int)threadIdx.x < 128) {
-#pragma unroll
-        for (int k = 0; k < NW; k++)
-            sh[k * UPDATE_BLOCK + threadIdx.x] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 128];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 64) {
-        float s64[NW];
-#pragma unroll
-        for (int k = 0; k < NW; k++) s64[k] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 64];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-            for (int k = 0; k < NW; k++) s64[k] = s64[k] + __shfl_down(s64[k], s, 64);
-        }
-        if (threadIdx.x == 0) {
-            float* out = partials + ((size_t)w.replica * max_blocks + w.block) * NW;
-#pragma unroll
-            for (int k = 0; k < NW; k++) out[k] = s64[k];
-        }
-    }
+    fold256<NW>(acc, sh);
+    if (threadIdx.x < NW)
+        partials[((size_t)w.replica * max_blocks + w.block) * NW + threadIdx.x] = sh[threadIdx.x * UPDATE_BLOCK];
 }
 
 // What a stage subtracts from dX.xyz (Heun_solver::heun_stages / fix_velocity): the mean of the replica's
@@ -369,18 +192,9 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_ma
         return;
     }
     const float3 fix1 = resolve_fix<Pt>(kind, partials, max_blocks, w.replica, n, d_dX1_all + base, fix_point);
-    const float* fix_first = d_fix_first + 4 * (size_t)w.replica;
-    const float3 fix{fix_first[0], fix_first[1], fix_first[2]};
     if (local < n) {
-        const size_t row = base + local;
-        const Pt dX_raw = d_dX_all[row];
-        if (zero_dX) d_dX_all[row] = ya::zero<Pt>();
-        const Pt dX = ya::minus_fix(dX_raw, fix);
-        const Pt dX1 = ya::minus_fix(d_dX1_all[row], fix1);
-        Pt X = d_X_all[row];
-        X += (dX + dX1) * 0.5 * dt;
-        d_X_all[row] = X;
-        d_old_v_all[row] = float3{(dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
+        ya::heun_row(local, dt, d_fix_first + 4 * (size_t)w.replica, fix1, d_dX_all + base, d_dX1_all + base,
+            d_X_all + base, d_old_v_all + base, zero_dX);
     } else if (zero_dX && local < n_max) {
         d_dX_all[base + local] = ya::zero<Pt>();
     }

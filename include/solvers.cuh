@@ -57,6 +57,7 @@
 
 #include "cudebug.cuh"
 #include "dtypes.cuh"
+#include "fold256.cuh"
 #include "yalla_hip.h"
 
 // Model files use thrust::fill / reduce on their own arrays and rely on the
@@ -158,6 +159,7 @@ constexpr int FORCE_BLOCK = YA_FORCE_BLOCK;  // grid force: cells (threads) per 
 constexpr int TILE_BLOCK = 64;     // tile force: one wavefront per workgroup
 constexpr int TILE_POINTS = 256;   // points staged in LDS per tile
 constexpr int UPDATE_BLOCK = 256;
+static_assert(UPDATE_BLOCK == 256, "the update kernels fold partial sums with ya::fold256, libyalla_hip.so's order");
 
 // One cell in cube-sorted order: the point and its original id.  16-byte
 // entries (float3) load as one dwordx4.
@@ -384,17 +386,20 @@ __device__ __forceinline__ Pt store_rhs(
 
 // All-pairs force (replaces compute_tile, solvers.cuh:284-322): j ascending,
 // functor called for every (i, j) including i == j.
+// The body, for one system's n rows at d_X / d_old_v / d_dX: the workgroup is the system's `block`-th and
+// serves TILE_BLOCK of its rows; the functors are handed the ids id_base + row (an ensemble's replica starts
+// at id_base, include/ensemble.cuh; a lone system's constant 0 folds away).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
-    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX,
-    const bool has_gen)
+__device__ __forceinline__ void tile_force_rows(const int n, const int block, const int id_base,
+    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX, const bool has_gen)
 {
     __shared__ Pt sh_X[TILE_POINTS];
     __shared__ float3 sh_v[TILE_POINTS];
 
-    const int i = blockIdx.x * TILE_BLOCK + threadIdx.x;
+    const int local = block * TILE_BLOCK + threadIdx.x;
+    const int i = id_base + local;
     Pt Xi = ya::zero<Pt>();
-    if (i < n) Xi = d_X[i];
+    if (local < n) Xi = d_X[local];
     Pt F = ya::zero<Pt>();
     float3 sum_v{0.f, 0.f, 0.f};
     float sum_friction = 0;
@@ -406,7 +411,7 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
             sh_v[k] = d_old_v[tile_start + k];
         }
         __syncthreads();
-        if (i < n) {
+        if (local < n) {
             // unrolled: the pairs' distance / functor chains are independent and overlap,
             // the sums stay in j order
 #ifndef YA_TILE_UNROLL
@@ -414,7 +419,7 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
 #endif
 #pragma unroll YA_TILE_UNROLL
             for (int k = 0; k < n_tile; k++) {
-                const int j = tile_start + k;
+                const int j = id_base + tile_start + k;
                 Pt r = Xi - sh_X[k];
                 float dist = dist3(r.x, r.y, r.z);
                 F += pw_int(Xi, r, dist, i, j);
@@ -429,7 +434,14 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
             }
         }
     }
-    if (i < n) store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
+    if (local < n) store_rhs(d_dX, local, has_gen, F, sum_v, sum_friction);
+}
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
+    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX,
+    const bool has_gen)
+{
+    tile_force_rows<Pt, pw_int, pw_friction>(n, blockIdx.x, 0, d_X, d_old_v, d_dX, has_gen);
 }
 
 // The same all-pairs force with 16 or 64 lanes per cell (opt-in: Tile_computer::lanes_per_cell).
@@ -442,11 +454,10 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
 // the functor is called for one i from several lanes at once, so functors that update per-cell
 // state non-atomically (d_mes_nbs[i] += 1, examples/passive_growth.cu:48-51) must keep the
 // default of one lane per cell.
-
+// The body, with tile_force_rows' arguments: the workgroup serves 256 / COOP_LANES of the system's rows.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
-__global__ __launch_bounds__(256) void tile_force_coop(const int n,
-    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX,
-    const bool has_gen)
+__device__ __forceinline__ void tile_force_coop_rows(const int n, const int block, const int id_base,
+    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX, const bool has_gen)
 {
     constexpr int COOP_CELLS = 256 / COOP_LANES;
     constexpr int NF = N_floats<Pt>::value;
@@ -463,10 +474,11 @@ __global__ __launch_bounds__(256) void tile_force_coop(const int n,
     __shared__ float sh_sum[COOP_CELLS][NC];
 
     const int cell = threadIdx.x / COOP_LANES, lane = threadIdx.x % COOP_LANES;
-    const int i = blockIdx.x * COOP_CELLS + cell;
-    const bool active = i < n;
+    const int local = block * COOP_CELLS + cell;
+    const int i = id_base + local;
+    const bool active = local < n;
     Pt Xi = ya::zero<Pt>();
-    if (active) Xi = d_X[i];
+    if (active) Xi = d_X[local];
     float acc[SLOTS];  // this lane's component sums (components lane, lane + COOP_LANES, ...)
 #pragma unroll
     for (int a = 0; a < SLOTS; a++) acc[a] = 0.f;
@@ -504,7 +516,7 @@ __global__ __launch_bounds__(256) void tile_force_coop(const int n,
         if (active) {
 #pragma unroll 4
             for (int jj = lane; jj < n_tile; jj += COOP_LANES) {
-                const int j = tile_start + jj;
+                const int j = id_base + tile_start + jj;
                 Pt r = Xi - sh_X[jj];
                 float dist = dist3(r.x, r.y, r.z);
                 const Pt f = pw_int(Xi, r, dist, i, j);
@@ -558,9 +570,16 @@ __global__ __launch_bounds__(256) void tile_force_coop(const int n,
         Pt F;
 #pragma unroll
         for (int c = 0; c < NF; c++) field(F, c) = sh_sum[cell][c];
-        store_rhs(d_dX, i, has_gen, F,
+        store_rhs(d_dX, local, has_gen, F,
             float3{sh_sum[cell][NF + 1], sh_sum[cell][NF + 2], sh_sum[cell][NF + 3]}, sh_sum[cell][NF]);
     }
+}
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+__global__ __launch_bounds__(256) void tile_force_coop(const int n,
+    const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v, Pt* __restrict__ d_dX,
+    const bool has_gen)
+{
+    tile_force_coop_rows<Pt, pw_int, pw_friction, COOP_LANES>(n, blockIdx.x, 0, d_X, d_old_v, d_dX, has_gen);
 }
 
 // Row r of the 27-cube stencil in the reference's d_nhood order
@@ -1852,37 +1871,13 @@ template<int NF>
 __device__ __forceinline__ float3 fixed_velocity_from_partials(const float* __restrict__ partials, const int n_partials,
     const int n)
 {
-    static_assert(UPDATE_BLOCK == 256, "the fold is libyalla_hip.so's fold256");
     __shared__ float sh[3 * UPDATE_BLOCK];
     float acc[3] = {0.f, 0.f, 0.f};
     for (int p = threadIdx.x; p < n_partials; p += UPDATE_BLOCK) {
 #pragma unroll
         for (int k = 0; k < 3; k++) acc[k] = acc[k] + partials[(size_t)p * NF + k];
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) sh[k * UPDATE_BLOCK + threadIdx.x] = acc[k];
-    __syncthreads();
-    if ((int)threadIdx.x < 128) {
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            sh[k * UPDATE_BLOCK + threadIdx.x] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 128];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 64) {
-        float v[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) v[k] = sh[k * UPDATE_BLOCK + threadIdx.x] + sh[k * UPDATE_BLOCK + threadIdx.x + 64];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) v[k] = v[k] + __shfl_down(v[k], s, 64);
-        }
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) sh[k * UPDATE_BLOCK] = v[k];
-        }
-    }
-    __syncthreads();
+    fold256<3>(acc, sh);
     const float inv = (float)(1. / (double)(float)n);  // Pt / n == Pt * float(1. / float(n))
     return float3{sh[0] * inv, sh[UPDATE_BLOCK] * inv, sh[2 * UPDATE_BLOCK] * inv};
 }
@@ -1916,6 +1911,24 @@ __device__ __forceinline__ Pt minus_fix(Pt dX, const float3 fix)
     dX.y -= fix.y;
     dX.z -= fix.z;
     return dX;
+}
+// Row i of the corrector X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v (solvers.cuh:127-144), fix = d_fix[0..2]
+// as the predictor left it; returns the new X.  zero_dX: the row of d_dX, dead after this, is left zeroed for
+// the next step's generic forces.
+template<typename Pt>
+__device__ __forceinline__ Pt heun_row(const int i, const float dt, const float* __restrict__ d_fix, const float3 fix1,
+    Pt* __restrict__ d_dX, const Pt* __restrict__ d_dX1, Pt* __restrict__ d_X, float3* __restrict__ d_old_v,
+    const bool zero_dX)
+{
+    const Pt dX_raw = d_dX[i];
+    if (zero_dX) d_dX[i] = ya::zero<Pt>();  // (straight after the load: no address kept live)
+    const Pt dX = minus_fix(dX_raw, float3{d_fix[0], d_fix[1], d_fix[2]});
+    const Pt dX1 = minus_fix(d_dX1[i], fix1);
+    Pt X = d_X[i];
+    X += (dX + dX1) * 0.5 * dt;
+    d_X[i] = X;
+    d_old_v[i] = float3{(dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
+    return X;
 }
 }  // namespace ya
 
@@ -1989,15 +2002,7 @@ __global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step(const int n, const
     const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
     float moved = 0.f;
     if (i < n) {
-        const Pt dX_raw = d_dX[i];
-        if (zero_dX) d_dX[i] = ya::zero<Pt>();  // (straight after the load: no address kept live)
-        const Pt dX = ya::minus_fix(dX_raw, float3{d_fix[0], d_fix[1], d_fix[2]});
-        const Pt dX1 = ya::minus_fix(d_dX1[i], fix1);
-        Pt X = d_X[i];
-        X += (dX + dX1) * 0.5 * dt;
-        d_X[i] = X;
-        d_old_v[i] = float3{
-            (dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
+        const Pt X = ya::heun_row(i, dt, d_fix, fix1, d_dX, d_dX1, d_X, d_old_v, zero_dX);
         if (z_selected) moved = fabsf(X.z - z_selected[i]) * band.weight(z_selected[i]);
     }
     if constexpr (S == ya::Fix_src::totals) {

@@ -351,7 +351,7 @@ def test_engine_takes_the_reference_grid_step_bit_for_bit(device, sum_order):
 
 # ---- the golden fixtures themselves, from numpy (set_fixed(): the centre of mass is held) --------------------------
 def fold256(lanes):
-    """lane[t] += lane[t + s] for s = 128 ... 1 (yalla_amd/csrc/core.hip fold256)."""
+    """lane[t] += lane[t + s] for s = 128 ... 1 (ya::fold256, include/fold256.cuh, DESIGN.md section 2)."""
     lanes = lanes.copy()
     s2 = 128
     while s2 >= 1:

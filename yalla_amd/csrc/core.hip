@@ -37,9 +37,11 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "fold256.cuh"
 #include "yalla_hip.h"
 
 namespace {
+using ya::fold256;
 
 constexpr int BLOCK = 256;
 constexpr int SCAN_ITEMS = 8;                   // cubes per thread in the scan
@@ -354,40 +356,9 @@ __global__ __launch_bounds__(BLOCK) void k_order_from(const int* __restrict__ ar
 // --- deterministic reduction -----------------------------------------------
 // B = clamp(ceil(n/256), 1, 1024) blocks; lane (b, t) sums i = b*256 + t,
 // += B*256 ... serially; block folds 256 lanes by halving through LDS; then one
-// block sums the B partials the same way.  The oracle restates this order
-// (oracle/yalla_host.hpp, YA_REDUCE_TREE).
-template<int NW>
-__device__ __forceinline__ void fold256(float (&acc)[NW], float* sh /* [NW][256] */)
-{
-    // lane[t] += lane[t + s] for s = 128 ... 1 (the documented order).  Round 5: from s = 32 down the
-    // operands sit in ONE wavefront and travel by shuffle instead of through LDS and a workgroup
-    // barrier per step -- the same additions of the same operands, so the same bits: a reduction
-    // kernel is 8 barriers shorter (4.9 -> 3.4 us per launch at any size).
-#pragma unroll
-    for (int k = 0; k < NW; k++) sh[k * BLOCK + threadIdx.x] = acc[k];
-    __syncthreads();
-    if ((int)threadIdx.x < 128) {
-#pragma unroll
-        for (int k = 0; k < NW; k++)
-            sh[k * BLOCK + threadIdx.x] = sh[k * BLOCK + threadIdx.x] + sh[k * BLOCK + threadIdx.x + 128];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 64) {
-        float v[NW];
-#pragma unroll
-        for (int k = 0; k < NW; k++) v[k] = sh[k * BLOCK + threadIdx.x] + sh[k * BLOCK + threadIdx.x + 64];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-            for (int k = 0; k < NW; k++) v[k] = v[k] + __shfl_down(v[k], s, 64);
-        }
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < NW; k++) sh[k * BLOCK] = v[k];
-        }
-    }
-    __syncthreads();
-}
+// block sums the B partials the same way (ya::fold256, include/fold256.cuh).  The oracle restates this
+// order (oracle/yalla_host.hpp, YA_REDUCE_TREE).
+static_assert(BLOCK == 256, "the reduction kernels fold with ya::fold256");
 
 // (Round 5 tried ONE launch -- the block that draws the last ticket folds the partials, same order --
 // and it is slower, 13.6 us against 9.8 for the two launches at 1024 blocks: partial sums that cross
