@@ -1,6 +1,10 @@
 // Ensemble<Pt, Tile_solver>: M independent all-pairs systems of one point type and one functor,
 // advanced together -- the same six launches per take_step whatever M is, and nothing read by the
 // host: every kernel takes its replica's cell count from d_n[r] on the device.
+// Ensemble<Pt, Grid_solver> (ensemble_grid.cuh, included at the end of this file) is the same for M
+// Grid_solver systems: everything below holds for it too, except that "forces of a stage" are a batched grid
+// build and a batched grid force.  The step -- stages, partial sums, the two update kernels -- exists once,
+// in ya::ens::Stepper, which both forms derive from.
 //
 // One Tile_solver step of a few hundred cells is launch and host latency, not work (DESIGN.md
 // section 9: 49 us for 800 cells), and a sweep over M such systems as M Solutions pays that M times
@@ -34,8 +38,8 @@
 // tile_force_rows, tile_force_coop_rows, heun_row; fold256.cuh): the kernels here add only where a
 // workgroup finds its replica's rows, its count and its id offset.
 //
-// Not here ("Ensembles"): Grid_solver / Gabriel_solver ensembles (the Solver
-// template parameter is their door), the fast-arithmetic tier, graph capture, a per-replica dt, slabs.
+// Not here ("Ensembles"): Gabriel_solver ensembles (the Solver template parameter is
+// their door, as it was Grid_solver's), the fast-arithmetic tier, graph capture, a per-replica dt, slabs.
 #pragma once
 
 #include "solvers.cuh"
@@ -217,10 +221,17 @@ inline int lanes_for(const int n_replicas, const int n_max)
 }  // namespace ya
 
 
-template<typename Pt, template<typename> class Solver = Tile_solver>
-class Ensemble {
-    static_assert(std::is_same<Solver<Pt>, Tile_solver<Pt>>::value,
-        "Ensemble steps all-pairs systems only: Ensemble<Pt, Tile_solver>");
+namespace ya {
+namespace ens {
+
+// What both forms of Ensemble are: the flat replica-major arrays, the counts, the fixed modes and THE STEP.
+// Form (CRTP) supplies the forces of a stage,
+//     template<pw_int, pw_friction> void forces(const Pt* d_in, Pt* d_rhs, bool has_gen)
+// which leaves every replica's right-hand sides of the cells d_in[r * n_max + 0 .. n_r) in d_rhs, added to what
+// the generic forces left there if has_gen.
+template<typename Pt, typename Form>
+class Stepper {
+protected:
     static constexpr int n_floats = ya::N_floats<Pt>::value;
 
 public:
@@ -231,20 +242,14 @@ public:
     int* d_n;         // the same on the device: what the step reads
     const int n_replicas;
     const int n_max;  // capacity of EACH replica
-    // As Tile_computer::lanes_per_cell: 0 (default) = the engine's choice -- one lane per cell unless the
-    // functors are declared stateless (YA_STATELESS), then by the size of the whole launch
-    // (ya::ens::lanes_for); 1, 16 or 64 = that many lanes per cell whatever the functor says.  Any
-    // choice gives the same bits.
-    int lanes_per_cell = 0;
 
-    Ensemble(int n_replicas, int n_max) : h_n{(int*)malloc(sizeof(int) * (n_replicas > 0 ? n_replicas : 1))},
+    Stepper(int n_replicas, int n_max) : h_n{(int*)malloc(sizeof(int) * (n_replicas > 0 ? n_replicas : 1))},
         n_replicas{n_replicas}, n_max{n_max}
     {
         assert(n_replicas > 0 && n_max > 0);
         // ids are ints (the functors' signature, gen_forces' n), and so is a launch's x dimension
         const size_t total = rows();
         assert(total <= (size_t)0x7fffffff);
-        assert((size_t)n_replicas * (size_t)((n_max + 3) / 4) <= (size_t)0x7fffffff);
         for (int r = 0; r < n_replicas; r++) h_n[r] = n_max;
         const size_t pts = total * sizeof(Pt);
         h_X_locked = ya_host_alloc((void**)&h_X, pts) == 0;
@@ -263,7 +268,7 @@ public:
         YA_CHECK(ya_malloc((void**)&d_fix_first, (size_t)n_replicas * 4 * sizeof(float)));
         YA_CHECK(ya_malloc((void**)&d_partials, (size_t)n_replicas * max_blocks() * n_floats * sizeof(float)));
     }
-    ~Ensemble()
+    ~Stepper()
     {
         if (h_X_locked)
             (void)ya_host_free(h_X);
@@ -279,7 +284,7 @@ public:
         ya_free(d_fix_first);
         ya_free(d_partials);
     }
-    Ensemble(const Ensemble&) = delete;
+    Stepper(const Stepper&) = delete;
 
     size_t rows() const { return (size_t)n_replicas * (size_t)n_max; }
     // row i of replica r in the host mirror (the same index serves d_X, d_old_v and a model's own arrays)
@@ -333,8 +338,8 @@ public:
     {
         take_step<pw_int, friction_w_neighbour<Pt>>(dt, gen_forces);
     }
-    // One Heun step of every replica.  Six launches (per stage: forces, partial sums, update), stream-ordered
-    // on the null stream; no copy to the host, no synchronisation, no allocation.
+    // One Heun step of every replica.  Per stage: the form's forces, partial sums, update; stream-ordered on the
+    // null stream; no copy to the host, no synchronisation, no allocation.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_step(float dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
@@ -349,7 +354,7 @@ public:
                 gen_forces((int)rows(), d_in, d_rhs);
             }
             rhs_zeroed[stage - 1] = false;  // the force kernel writes it next
-            forces<pw_int, pw_friction>(d_in, d_rhs, has_gen);
+            static_cast<Form*>(this)->template forces<pw_int, pw_friction>(d_in, d_rhs, has_gen);
             // Heun_solver::heun_stages: set_fixed_xy(i) holds x and y in the first stage only
             const bool xy = stage == 1 && fix_com_z;
             const int kind = (fix_com && !fix_com_z) ? ya::ens::FIX_MEAN
@@ -384,24 +389,62 @@ protected:
 
     int max_blocks() const { return ya::ens::reduce_blocks(n_max); }
     dim3 grid_of(int blocks_per_replica) const { return dim3((unsigned)((size_t)n_replicas * blocks_per_replica)); }
+};
 
+}  // namespace ens
+}  // namespace ya
+
+
+// Ensemble<Pt> / Ensemble<Pt, Tile_solver>{n_replicas, n_max} and Ensemble<Pt, Grid_solver>{n_replicas, n_max,
+// grid_size, cube_size} (ensemble_grid.cuh); no other solver has an ensemble.
+template<typename Pt, template<typename> class Solver = Tile_solver, typename Which = void>
+class Ensemble {
+    static_assert(!std::is_same<Which, void>::value,
+        "Ensemble steps all-pairs or grid systems: Ensemble<Pt, Tile_solver> or Ensemble<Pt, Grid_solver>");
+};
+
+template<typename Pt, template<typename> class Solver>
+class Ensemble<Pt, Solver, std::enable_if_t<std::is_same<Solver<Pt>, Tile_solver<Pt>>::value>>
+    : public ya::ens::Stepper<Pt, Ensemble<Pt, Solver>> {
+    using Base = ya::ens::Stepper<Pt, Ensemble<Pt, Solver>>;
+    friend Base;
+
+public:
+    // As Tile_computer::lanes_per_cell: 0 (default) = the engine's choice -- one lane per cell unless the
+    // functors are declared stateless (YA_STATELESS), then by the size of the whole launch
+    // (ya::ens::lanes_for); 1, 16 or 64 = that many lanes per cell whatever the functor says.  Any
+    // choice gives the same bits.
+    int lanes_per_cell = 0;
+
+    // Six launches per take_step (per stage: forces, partial sums, update).
+    Ensemble(int n_replicas, int n_max) : Base{n_replicas, n_max}
+    {
+        assert((size_t)n_replicas * (size_t)((n_max + 3) / 4) <= (size_t)0x7fffffff);  // (a launch's x dimension)
+    }
+
+protected:
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void forces(const Pt* d_in, Pt* d_rhs, const bool has_gen)
     {
+        const int n_max = this->n_max, n_replicas = this->n_replicas;
+        const int* d_n = this->d_n;
+        const float3* d_old_v = this->d_old_v;
         int lanes = lanes_per_cell;
         if (lanes == 0) lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::lanes_for(n_replicas, n_max) : 1;
         if (lanes >= 64) {
             const int blocks = (n_max + 3) / 4;
-            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 64><<<grid_of(blocks), 256>>>(
+            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 64><<<this->grid_of(blocks), 256>>>(
                 n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
         } else if (lanes > 1) {
             const int blocks = (n_max + 15) / 16;
-            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 16><<<grid_of(blocks), 256>>>(
+            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 16><<<this->grid_of(blocks), 256>>>(
                 n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
         } else {
             const int blocks = (n_max + ya::TILE_BLOCK - 1) / ya::TILE_BLOCK;
-            ya::ens::tile_force_batched<Pt, pw_int, pw_friction><<<grid_of(blocks), ya::TILE_BLOCK>>>(
+            ya::ens::tile_force_batched<Pt, pw_int, pw_friction><<<this->grid_of(blocks), ya::TILE_BLOCK>>>(
                 n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
         }
     }
 };
+
+#include "ensemble_grid.cuh"

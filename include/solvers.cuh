@@ -804,7 +804,7 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
     const int b0, const int e0, const int b1, const int e1, const int b2, const int e2,
     const int shift0, const int shift1, const int shift2, const float4* __restrict__ sorted_v,
     const Pt& Xi, const int i, const float cut2, Pt& F, float3& sum_v, float& sum_friction,
-    const int* __restrict__ global_id)
+    const int* __restrict__ global_id, const int id_base = 0)
 {
     constexpr int POPS = Pops<Pt>::value;
     // ---- phase 1 ----
@@ -865,7 +865,7 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
     {                                                                                  \
         Pt r = Xi - other_.X;                                                          \
         float dist = dist3(r.x, r.y, r.z);                                             \
-        const int j = GLOBAL_IDS ? global_id[other_.id] : other_.id;                   \
+        const int j = (GLOBAL_IDS ? global_id[other_.id] : other_.id) + id_base;       \
         YA_CALL_INLINED F += pw_int(Xi, r, dist, i, j);                                \
         pair_friction<Pt, pw_friction>(Xi, r, dist, i, j, v_, sum_v, sum_friction);    \
     }
@@ -906,6 +906,13 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
 
 // GLOBAL_IDS (z-slab decomposition): functors get global_id[local index]; a template parameter
 // rather than a null test so that the single-GPU kernel carries neither the test nor the gather.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS>
+__device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile, const int id_base, const int half,
+    const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
+    const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
+    Pt* d_dX, const bool has_gen, const int n_active, Pt* d_dX_sorted,
+    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane);
+
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V = false,
     bool GLOBAL_IDS = false>
 __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_force_bits(const int n,
@@ -918,16 +925,6 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     const int own_cube_hi = 0x7fffffff)
 {
     constexpr int FB = bits::BLOCK;
-    constexpr int CAP = bits::Stage<Pt>::value;
-    constexpr int NF = N_floats<Pt>::value;
-    constexpr int NC = NF + 4;  // sums kept per cell: F (NF), friction * old_v (3), friction
-    __shared__ __attribute__((aligned(16))) Entry<Pt> sh_e[CAP + 8];  // slack: whole groups are read
-    __shared__ unsigned sh_m[(bits::WORDS + 1) * FB];                // [word][thread], one spare row
-    // STAGE_V (small systems, Grid_computer::forces): old_v of the staged cells in LDS as well.
-    // A launch that cannot fill the chip is one wavefront per SIMD and nothing hides the round
-    // trip to L2 that every interacting pair's old_v otherwise costs.
-    __shared__ float4 sh_v[STAGE_V ? CAP + 8 : 1];
-    bits::Lds_word* const words = (bits::Lds_word*)sh_m + threadIdx.x;
 
     // z-slab decomposition: a stage's forces in two launches, so that the right-hand sides the
     // slab neighbours wait for are computed and sent first.  part 1 = the tiles that hold the
@@ -994,6 +991,35 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
         else
             tile = t_lo + t;
     }
+    // which tile is mine ends here; the tile itself is the body an ensemble's kernel shares (include/ensemble_grid.cuh)
+    grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(n, tile, 0, half, compact - whole, sorted,
+        sorted_v, cube_id, offs, gs, n_cubes, cut2, d_dX, has_gen, n_active, d_dX_sorted, global_id, tail_exchange,
+        tail_tickets, by_plane);
+}
+
+// One tile of grid_force_bits -- 64 consecutive sorted slots of ONE system's arrays -- as the workgroup that was
+// given it: half < 0 a whole tile, 0 / 1 one half of exchange slot `slot` ("the tail", above).  The functors are
+// handed the ids id_base + id (an ensemble's replica starts at id_base and its cube ids and offs[] are its own, so
+// the clamps of YA_ROW_BOUNDS keep every stencil row inside the replica's segment; a lone system's constant 0
+// folds away).  (No __restrict__ here: what may alias is said once, by the kernels' own parameters.)
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS>
+__device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile, const int id_base, const int half,
+    const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
+    const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
+    Pt* d_dX, const bool has_gen, const int n_active, Pt* d_dX_sorted,
+    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane)
+{
+    constexpr int FB = bits::BLOCK;
+    constexpr int CAP = bits::Stage<Pt>::value;
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int NC = NF + 4;  // sums kept per cell: F (NF), friction * old_v (3), friction
+    __shared__ __attribute__((aligned(16))) Entry<Pt> sh_e[CAP + 8];  // slack: whole groups are read
+    __shared__ unsigned sh_m[(bits::WORDS + 1) * FB];                // [word][thread], one spare row
+    // STAGE_V (small systems, Grid_computer::forces): old_v of the staged cells in LDS as well.
+    // A launch that cannot fill the chip is one wavefront per SIMD and nothing hides the round
+    // trip to L2 that every interacting pair's old_v otherwise costs.
+    __shared__ float4 sh_v[STAGE_V ? CAP + 8 : 1];
+    bits::Lds_word* const words = (bits::Lds_word*)sh_m + threadIdx.x;
     const int s0 = tile * FB;
     const int s = s0 + threadIdx.x;
     bool active = s < n;
@@ -1012,7 +1038,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     }
     if (!__syncthreads_or(active)) return;  // a workgroup of ghosts only
     // functors see GLOBAL ids in a slab decomposition (they index per-cell model arrays)
-    const int gi = GLOBAL_IDS && active ? global_id[i] : i;
+    const int gi = (GLOBAL_IDS && active ? global_id[i] : i) + id_base;
     Pt F = ya::zero<Pt>();
     float3 sum_v{0.f, 0.f, 0.f};
     float sum_friction = 0;
@@ -1081,7 +1107,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
             if (!__any(bits_needed > bits::PASS_BITS)) {
                 bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(sh_e, sh_v, words, sb[0], se[0], sb[1], se[1], sb[2],
                     se[2], shift[0], shift[1], shift[2], sorted_v, Xi, gi, cut2, F, sum_v, sum_friction,
-                    global_id);
+                    global_id, id_base);
             } else {
                 // dense rows: one pass per stretch of PASS_BITS candidates, rows in order
 #pragma unroll 1
@@ -1092,7 +1118,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
 #pragma unroll 1
                     for (int b = rb; __any(b < re); b += bits::PASS_BITS)
                         bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(sh_e, sh_v, words, b, min(re, b + bits::PASS_BITS),
-                            0, 0, 0, 0, rs, 0, 0, sorted_v, Xi, gi, cut2, F, sum_v, sum_friction, global_id);
+                            0, 0, 0, 0, rs, 0, 0, sorted_v, Xi, gi, cut2, F, sum_v, sum_friction, global_id, id_base);
                 }
             }
         }
@@ -1120,7 +1146,6 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
         // acknowledged at device scope (a workgroup-scope fence and the barrier compile to nothing in a
         // one-wavefront workgroup, and the stores and the atomic travel to different channels).
         __shared__ int sh_second;
-        const int slot = compact - whole;
         float* const mine_out = tail_exchange + ((size_t)slot * 2 + half) * NC * FB + threadIdx.x;
 #pragma unroll
         for (int k = 0; k < NC; k++)
@@ -1211,12 +1236,14 @@ __device__ __forceinline__ void wave_sync()
 }
 }  // namespace coop
 
+// The body, for ONE system's arrays: the workgroup is the system's `block`-th of `n_blocks` and owns 256 / LANES of
+// its sorted slots; the functors are handed the ids id_base + id (grid_force_bits_tile's comment).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
-__global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
-    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
-    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
-    const int n_cubes, const float cut2, Pt* __restrict__ d_dX, const bool has_gen,
-    const int n_active, Pt* __restrict__ d_dX_sorted, const int* __restrict__ global_id, const bool by_plane)
+__device__ __forceinline__ void grid_force_coop_cells(const int n, const int block, const int n_blocks,
+    const int id_base, const Entry<Pt>* sorted, const float4* sorted_v,
+    const int* cube_id, const int* offs, const int gs,
+    const int n_cubes, const float cut2, Pt* d_dX, const bool has_gen,
+    const int n_active, Pt* d_dX_sorted, const int* global_id, const bool by_plane)
 {
     static_assert(LANES == 4 || LANES == 8 || LANES == 16, "lanes per cell");
     constexpr int CELLS = coop::BLOCK / LANES, MAX_HITS = coop::MAX_HITS;
@@ -1236,7 +1263,7 @@ __global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
     __shared__ int sh_lo[9], sh_len[9], sh_shift[9], sh_kb[CELLS][9], sh_ke[CELLS][9];
 
     const int cell = threadIdx.x / LANES, lane = threadIdx.x % LANES;
-    const int s0 = xcd_contiguous_tile(blockIdx.x, gridDim.x) * CELLS;
+    const int s0 = xcd_contiguous_tile(block, n_blocks) * CELLS;
     const int s = s0 + cell;
     bool active = s < n;
 
@@ -1250,7 +1277,7 @@ __global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
         active = i < n_active;  // ghost cells of a slab decomposition get no force
     }
     if (!__syncthreads_or(active)) return;  // a workgroup of ghosts only
-    const int gi = global_id && active ? global_id[i] : i;
+    const int gi = (global_id && active ? global_id[i] : i) + id_base;
     // The reference indexes cube_start/end without bounds checks (solvers.cuh:444);
     // out-of-grid cubes are treated as empty here.
     for (int r = lane; r < 9; r += LANES) {
@@ -1410,7 +1437,7 @@ __global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
                             v = sorted_v[(unsigned)(t + base + sh_shift[e >> 12])];
                         Pt rr = Xi - other.X;
                         float dist = dist3(rr.x, rr.y, rr.z);
-                        const int j = global_id ? global_id[other.id] : other.id;
+                        const int j = (global_id ? global_id[other.id] : other.id) + id_base;
                         YA_CALL_INLINED f = pw_int(Xi, rr, dist, gi, j);
                         friction = pw_friction(Xi, rr, dist, gi, j);
                     }
@@ -1462,6 +1489,17 @@ __global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
             float3{sh_sum[cell][NF + 1], sh_sum[cell][NF + 2], sh_sum[cell][NF + 3]}, sh_sum[cell][NF]);
         if (d_dX_sorted) d_dX_sorted[s] = dX;  // for the sorted-space Euler stage
     }
+}
+
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+__global__ __launch_bounds__(coop::BLOCK) void grid_force_coop(const int n,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cut2, Pt* __restrict__ d_dX, const bool has_gen,
+    const int n_active, Pt* __restrict__ d_dX_sorted, const int* __restrict__ global_id, const bool by_plane)
+{
+    grid_force_coop_cells<Pt, pw_int, pw_friction, LANES>(n, blockIdx.x, gridDim.x, 0, sorted, sorted_v, cube_id, offs,
+        gs, n_cubes, cut2, d_dX, has_gen, n_active, d_dX_sorted, global_id, by_plane);
 }
 
 #undef YA_ROW_BOUNDS

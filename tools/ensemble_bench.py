@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""M small all-pairs systems per step: M single Solutions stepped one after the other against one Ensemble.
+"""M small systems per step: M single Solutions stepped one after the other against one Ensemble.
 
     python tools/ensemble_bench.py [--out profiles/ensemble_bench.json] [--window 0.3] [--repeats 3]
     python tools/ensemble_bench.py --trace-shape 64 800 --steps 50     # what a rocprofv3 run wraps
+    python tools/ensemble_bench.py --solver grid [--out profiles/ensemble_grid_bench.json]
+    python tools/ensemble_bench.py --solver grid --trace-shape 64 2000 --steps 50
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -13,6 +15,12 @@ A timed window is K steps between two synchronisations under a host clock, K cal
 at least --window seconds; --repeats windows per setting, the median reported with the spread
 (max - min) / median.  Cells are a seeded random ball per replica (all-pairs cost does not depend on positions).
 The figure is cell-updates per second: M * n * K / seconds.
+
+--solver grid: the same protocol for Grid_solver systems -- Solution("relu_grid", n, grid_size) round-robin (below
+YA_GRAPH_MAX_CELLS each of them replays a captured graph of its step) against one GridEnsemble("relu", M, n,
+grid_size) with lanes 0 (ya::ens::grid_lanes_for), 1, 4, 8, 16; M in {1, 8, 64, 512} x n in {500, 2000, 10^4,
+5 * 10^4} with M * n <= 5 * 10^6; grid_size fitted to the ball (the ensemble scans M * grid_size^3 counters per
+stage).  The row's spread is that of the worse side.
 """
 import argparse
 import json
@@ -25,12 +33,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from yalla_amd.ensemble import Ensemble  # noqa: E402
+from yalla_amd.ensemble import Ensemble, GridEnsemble  # noqa: E402
 from yalla_amd.solution import Solution  # noqa: E402
 
 SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
 LANES = (0, 1, 16, 64)
+GRID_SHAPES = [(m, n) for n in (500, 2000, 10000, 50000) for m in (1, 8, 64, 512) if m * n <= 5000000]
+GRID_LANES = (0, 1, 4, 8, 16)
 DT = 0.01
+GRID = False  # --solver grid
+
+
+def grid_size_for(n):
+    """The ball's diameter at the density of random_sphere(0.75), half as much again for relu's expansion, even."""
+    radius = 0.75 * (n / 0.64) ** (1 / 3) / 2
+    return 2 * int(np.ceil(1.5 * radius)) + 4
 
 
 def ball(n, seed):
@@ -43,7 +60,8 @@ def ball(n, seed):
 
 class Singles:
     def __init__(self, m, n):
-        self.sims = [Solution("relu_tile", n) for _ in range(m)]
+        self.sims = [Solution("relu_grid", n, grid_size_for(n), 1.0) if GRID else Solution("relu_tile", n)
+                     for _ in range(m)]
         for r, s in enumerate(self.sims):
             s.h_X[:] = ball(n, r)
             s.copy_to_device()
@@ -61,13 +79,13 @@ class Singles:
 
 class Together:
     def __init__(self, m, n):
-        self.ens = Ensemble("relu", m, n)
+        self.ens = GridEnsemble("relu", m, n, grid_size_for(n), 1.0) if GRID else Ensemble("relu", m, n)
         for r in range(m):
             self.ens.h_X[r] = ball(n, r)
         self.ens.copy_to_device()
 
     def lanes(self, lanes):
-        self.ens.set_param("tile_lanes", lanes)
+        self.ens.set_param("lanes" if GRID else "tile_lanes", lanes)
 
     def steps(self, k):
         self.ens.take_step(DT, k)
@@ -119,12 +137,14 @@ def measure(m, n, window, repeats):
         a.close()
         b.close()
     row = {"n_replicas": m, "n": n, "singles": summary(samples["A"], m * n, ks["A"])}
+    if GRID:
+        row["grid_size"] = grid_size_for(n)
     for lanes in LANES:
         row[f"ensemble_lanes_{lanes}"] = summary(samples[lanes], m * n, ks[lanes])
     for lanes in LANES:
         row[f"ratio_lanes_{lanes}"] = row[f"ensemble_lanes_{lanes}"]["cell_updates_per_s"] / row["singles"]["cell_updates_per_s"]
     row["ratio"] = row["ratio_lanes_0"]  # the engine's choice against the sequential loop
-    row["spread"] = max(row["singles"]["spread"], row["ensemble_lanes_0"]["spread"])
+    row["spread"] = max(row["singles"]["spread"], row["ensemble_lanes_0"]["spread"])  # of the worse side
     return row
 
 
@@ -137,7 +157,11 @@ def main():
     ap.add_argument("--trace-shape", type=int, nargs=2, metavar=("M", "N"), default=None,
                     help="only step one Ensemble of this shape --steps times (for a kernel trace)")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--solver", choices=("tile", "grid"), default="tile")
     args = ap.parse_args()
+    global GRID, LANES, SHAPES
+    if args.solver == "grid":
+        GRID, LANES, SHAPES = True, GRID_LANES, GRID_SHAPES
 
     if args.trace_shape:
         b = Together(*args.trace_shape)
@@ -158,13 +182,13 @@ def main():
         print(f"M {m:5d}  n {n:5d}   singles {r['singles']['us_per_step']:10.1f} us/step   ensemble "
               + "  ".join(f"L{lanes}: {r[f'ensemble_lanes_{lanes}']['us_per_step']:9.1f}" for lanes in LANES)
               + f"   ratio {r['ratio']:.2f}  spread {r['spread']:.3f}", flush=True)
-    result = {"tool": "tools/ensemble_bench.py", "model": "relu", "dt": DT, "window_s": args.window,
-              "repeats": args.repeats, "rows": rows}
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(result, f, indent=1)
-            f.write("\n")
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py", "solver": args.solver, "model": "relu", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
     print(json.dumps({"shapes": len(rows), "min_ratio": min(r["ratio"] for r in rows)}))
 
 

@@ -14,6 +14,7 @@ DEVICE_LIB = os.environ.get("YALLA_MODELS_LIB") or os.path.join(_HERE, "libyalla
 DEVICE_LIB_FAST = os.path.join(_HERE, "libyalla_models_fast.so")  # the fast-arithmetic tier
 CORE_LIB = os.path.join(_HERE, "libyalla_hip.so")
 ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ensemble.h
+GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid.so")  # include/yalla_ensemble_grid.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -89,6 +90,30 @@ ENSEMBLE_ABI = {
     "ya_ens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
 }
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_grid.h one to one.
+GRID_ENSEMBLE_ABI = {
+    "ya_gens_models_count": (C.c_int, []),
+    "ya_gens_models_name": (C.c_char_p, [C.c_int]),
+    "ya_gens_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_ens)]),
+    "ya_gens_destroy": (None, [_ens]),
+    "ya_gens_n_floats": (C.c_int, [_ens]),
+    "ya_gens_h_X": (_pf, [_ens]),
+    "ya_gens_set_h_n": (C.c_int, [_ens, C.c_int, C.c_int]),
+    "ya_gens_get_h_n": (C.c_int, [_ens, C.c_int]),
+    "ya_gens_get_d_n": (C.c_int, [_ens, C.c_int]),
+    "ya_gens_copy_to_device": (C.c_int, [_ens]),
+    "ya_gens_copy_to_host": (C.c_int, [_ens]),
+    "ya_gens_take_steps": (C.c_int, [_ens, C.c_float, C.c_int]),
+    "ya_gens_synchronize": (C.c_int, [_ens]),
+    "ya_gens_set_fixed": (C.c_int, [_ens, C.c_int, C.c_int]),
+    "ya_gens_set_cube_size": (C.c_int, [_ens, C.c_float]),
+    "ya_gens_get_old_v": (C.c_int, [_ens, _pf]),
+    "ya_gens_set_old_v": (C.c_int, [_ens, _pf]),
+    "ya_gens_status": (C.c_int, [_ens, C.c_int, C.c_int]),
+    "ya_gens_get_grid": (C.c_int, [_ens, C.c_int, _pi, _pi, _pi, _pi]),
+    "ya_gens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
+}
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -156,3 +181,22 @@ def ensemble_lib():
             fn.argtypes = args
         _ensemble.append(lib)
     return _ensemble[0]
+
+
+_grid_ensemble = []
+
+
+def grid_ensemble_lib():
+    """The grid ensemble harness, yalla_amd/libyalla_ensemble_grid.so (include/yalla_ensemble_grid.h), every
+    entry point typed.  Raises if it has not been built: there is no fallback."""
+    if not _grid_ensemble:
+        if not os.path.exists(GRID_ENSEMBLE_LIB):
+            raise FileNotFoundError(
+                f"{GRID_ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
+        lib = C.CDLL(GRID_ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
+        for name, (res, args) in GRID_ENSEMBLE_ABI.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
+        _grid_ensemble.append(lib)
+    return _grid_ensemble[0]

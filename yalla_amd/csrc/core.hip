@@ -37,10 +37,12 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "cube_id.cuh"
 #include "fold256.cuh"
 #include "yalla_hip.h"
 
 namespace {
+using ya::cube_id_of;
 using ya::fold256;
 
 constexpr int BLOCK = 256;
@@ -51,17 +53,7 @@ constexpr int REDUCE_MAX_BLOCKS = 1024;
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // --- binning ---------------------------------------------------------------
-// solvers.cuh:357-360 evaluated in float, left to right:
-//   (floor(x/cs) + gs/2) + (floor(y/cs) + gs/2)*gs + (floor(z/cs) + gs/2)*gs*gs
-__device__ __forceinline__ int cube_id_of(float x, float y, float z, float cs, int gs)
-{
-    const float half = (float)(gs / 2);
-    const float fgs = (float)gs;
-    float fx = floorf(x / cs) + half;
-    float fy = (floorf(y / cs) + half) * fgs;
-    float fz = ((floorf(z / cs) + half) * fgs) * fgs;
-    return (int)((fx + fy) + fz);
-}
+// (the cube id itself: ya::cube_id_of, include/cube_id.cuh)
 
 // Visit order over max(n, n_prev) positions: position s of the previous build's
 // sorted order, identity for cells added since (ids >= n_prev); -1 where the

@@ -17,6 +17,7 @@
 #include "model_functors.h"
 
 #include "yalla_ensemble.h"
+#include "ensemble_harness.h"  // No_gen, Push_gen
 
 namespace ens_harness {
 
@@ -36,12 +37,6 @@ struct Base {
     virtual void set_lanes(int lanes) = 0;
 };
 
-template<typename Pt>
-struct No_gen {
-    static Generic_forces<Pt> gen(int, int) { return no_gen_forces<Pt>; }
-    static void before_steps(int) {}
-};
-
 // models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
 // (i = r * n_max + local), so the ensemble's model hands the functor the local ones: the same statements, hence
 // the bits of oscillator_tile in every replica.  n_max travels in a device variable, set when it changes.
@@ -59,30 +54,6 @@ struct Oscillator_ids : public No_gen<float4> {
         rows_set = n_max;
     }
 };
-// The generic force of the `push_tile` model (models::push: the right-hand side of cell 1 set to (1, 0, 0)) for
-// an ensemble: ONE call on the flat arrays pushes cell 1 of every replica, global row r * n_max + 1.
-template<typename Pt>
-__global__ void push_cell_1_of_every_replica(const int n_replicas, const int n_max, Pt* d_dX)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_replicas) return;
-    Pt* row = d_dX + (size_t)r * n_max + 1;
-    row->x = 1;
-    row->y = 0;
-    row->z = 0;
-}
-template<typename Pt>
-struct Push_gen {
-    static Generic_forces<Pt> gen(int n_replicas, int n_max)
-    {
-        return [n_replicas, n_max](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
-            if (n_max < 2 || n != n_replicas * n_max) return;
-            push_cell_1_of_every_replica<Pt><<<(n_replicas + 255) / 256, 256>>>(n_replicas, n_max, d_dX);
-        };
-    }
-    static void before_steps(int) {}
-};
-
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
 struct Sim : public Base {
     Ensemble<Pt> cells;

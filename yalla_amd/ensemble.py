@@ -13,6 +13,8 @@ replica and apply to every replica.  Each replica holds, bit for bit, what a
         cells.copy_to_device()
         cells.take_step(0.05, 100)
         X = cells.positions(r)
+
+`GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh).
 """
 import ctypes as C
 
@@ -42,7 +44,7 @@ class _Counts:
     def __getitem__(self, r):
         if isinstance(r, slice):
             return [self[k] for k in range(*r.indices(len(self)))]
-        return self._ens.lib.ya_ens_get_h_n(self._ens._h, self._index(r))
+        return self._ens._f("get_h_n")(self._ens._h, self._index(r))
 
     def __setitem__(self, r, n):
         if isinstance(r, slice):
@@ -51,7 +53,7 @@ class _Counts:
             for k, v in zip(ks, ns):
                 self[k] = v
             return
-        _check(self._ens.lib.ya_ens_set_h_n(self._ens._h, self._index(r), int(n)), "set h_n")
+        _check(self._ens._f("set_h_n")(self._ens._h, self._index(r), int(n)), "set h_n")
 
     def __iter__(self):
         return (self[r] for r in range(len(self)))
@@ -61,26 +63,34 @@ class _Counts:
 
 
 class Ensemble:
+    _PREFIX = "ya_ens_"  # the C ABI this class drives (GridEnsemble: ya_gens_, the same functions and more)
+
+    def _f(self, name):
+        return getattr(self.lib, self._PREFIX + name)
+
     def __init__(self, model, n_replicas, n_max, lib=None):
         self.lib = lib if lib is not None else _ffi.ensemble_lib()
-        self.model = model
         handle = C.c_void_p()
-        code = self.lib.ya_ens_create(model.encode(), int(n_replicas), int(n_max), C.byref(handle))
+        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), C.byref(handle))
         if code == -1:
             raise YallaError(f"unknown ensemble model {model!r}; known: {models(self.lib)}")
         _check(code, "ya_ens_create")
+        self._attach(model, handle, n_replicas, n_max)
+
+    def _attach(self, model, handle, n_replicas, n_max):
+        self.model = model
         self._h = handle
         self.n_replicas = int(n_replicas)
         self.n_max = int(n_max)
-        self.n_floats = self.lib.ya_ens_n_floats(self._h)
-        ptr = self.lib.ya_ens_h_X(self._h)
+        self.n_floats = self._f("n_floats")(self._h)
+        ptr = self._f("h_X")(self._h)
         self.h_X = np.ctypeslib.as_array(ptr, shape=(self.n_replicas, self.n_max, self.n_floats))
         self.h_n = _Counts(self)
 
     def close(self):
         if getattr(self, "_h", None):
             self.h_X = None
-            self.lib.ya_ens_destroy(self._h)
+            self._f("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -96,37 +106,37 @@ class Ensemble:
         self.close()
 
     def copy_to_device(self):
-        _check(self.lib.ya_ens_copy_to_device(self._h), "copy_to_device")
+        _check(self._f("copy_to_device")(self._h), "copy_to_device")
 
     def copy_to_host(self):
-        _check(self.lib.ya_ens_copy_to_host(self._h), "copy_to_host")
+        _check(self._f("copy_to_host")(self._h), "copy_to_host")
 
     def get_d_n(self, r):
         """Blocking read of replica r's device-side count (the step itself never reads it)."""
-        n = self.lib.ya_ens_get_d_n(self._h, int(r))
+        n = self._f("get_d_n")(self._h, int(r))
         if n < 0:
             raise YallaError(f"get_d_n({r}) failed with harness code {n}")
         return n
 
     def take_step(self, dt, steps=1):
-        _check(self.lib.ya_ens_take_steps(self._h, float(dt), int(steps)), "take_step")
+        _check(self._f("take_steps")(self._h, float(dt), int(steps)), "take_step")
 
     def synchronize(self):
-        _check(self.lib.ya_ens_synchronize(self._h), "synchronize")
+        _check(self._f("synchronize")(self._h), "synchronize")
 
     def set_fixed(self, local_id=None):
         """set_fixed() holds every replica's centre of mass, set_fixed(i) cell i of every replica
         (i must exist in every replica that is not empty)."""
         if local_id is None:
-            _check(self.lib.ya_ens_set_fixed(self._h, 0, 0), "set_fixed")
+            _check(self._f("set_fixed")(self._h, 0, 0), "set_fixed")
         else:
-            _check(self.lib.ya_ens_set_fixed(self._h, 1, int(local_id)), "set_fixed")
+            _check(self._f("set_fixed")(self._h, 1, int(local_id)), "set_fixed")
 
     def set_fixed_xy(self, local_id):
-        _check(self.lib.ya_ens_set_fixed(self._h, 2, int(local_id)), "set_fixed_xy")
+        _check(self._f("set_fixed")(self._h, 2, int(local_id)), "set_fixed_xy")
 
     def set_param(self, name, value):
-        _check(self.lib.ya_ens_set_param(self._h, name.encode(), float(value)), "set_param")
+        _check(self._f("set_param")(self._h, name.encode(), float(value)), "set_param")
         return 0
 
     def positions(self, r=None):
@@ -139,14 +149,67 @@ class Ensemble:
 
     def old_v(self):
         out = np.empty((self.n_replicas, self.n_max, 3), dtype=np.float32)
-        _check(self.lib.ya_ens_get_old_v(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "get_old_v")
+        _check(self._f("get_old_v")(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "get_old_v")
         return out
 
     def set_old_v(self, v):
         v = np.ascontiguousarray(v, dtype=np.float32).reshape(self.n_replicas, self.n_max, 3)
-        _check(self.lib.ya_ens_set_old_v(self._h, v.ctypes.data_as(C.POINTER(C.c_float))), "set_old_v")
+        _check(self._f("set_old_v")(self._h, v.ctypes.data_as(C.POINTER(C.c_float))), "set_old_v")
+
+
+class GridEnsemble(Ensemble):
+    """Host-side mirror of `Ensemble<Pt, Grid_solver>` (include/ensemble_grid.cuh) over include/yalla_ensemble_grid.h:
+    M independent Grid_solver systems of one model, every replica bit for bit what a
+    `Solution("<model>_grid", n_max, grid_size, cube_size)` given the same rows holds.  Everything `Ensemble`
+    offers, and: `grid(r)` (the replica's cube_id, point_id, cube_start, cube_end as `Solution.grid()` returns
+    them, ids local to the replica), `status(r)` (1 = a cell of replica r left its grid; copy_to_host() aborts on
+    a replica in that state unless status(r, clear=True) forgave it), a `cube_size` setter, and
+    set_param("lanes", 0 | 1 | 4 | 8 | 16) / set_param("sum_order", 0 | 1).
+
+    Every stage scans n_replicas * grid_size**3 counters: pick grid_size to fit the replicas, not 50.
+    """
+    _PREFIX = "ya_gens_"
+
+    def __init__(self, model, n_replicas, n_max, grid_size=50, cube_size=1.0, lib=None):
+        self.lib = lib if lib is not None else _ffi.grid_ensemble_lib()
+        handle = C.c_void_p()
+        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), int(grid_size), float(cube_size),
+                                 C.byref(handle))
+        if code == -1:
+            raise YallaError(f"unknown grid ensemble model {model!r}; known: {grid_models(self.lib)}")
+        _check(code, "ya_gens_create")
+        self.grid_size = int(grid_size)
+        self._attach(model, handle, n_replicas, n_max)
+
+    @property
+    def cube_size(self):
+        raise AttributeError("cube_size is write-only here")
+
+    @cube_size.setter
+    def cube_size(self, value):
+        _check(self._f("set_cube_size")(self._h, float(value)), "set cube_size")
+
+    def status(self, r, clear=True):
+        bits = self._f("status")(self._h, int(r), int(bool(clear)))
+        if bits < 0:
+            raise YallaError(f"status({r}) failed with harness code {bits}")
+        return bits
+
+    def grid(self, r):
+        """cube_id, point_id (n_max each; ids local to the replica), cube_start, cube_end (grid_size**3 each) of
+        replica r's last build."""
+        a, b = np.empty(self.n_max, np.int32), np.empty(self.n_max, np.int32)
+        c, d = np.empty(self.grid_size ** 3, np.int32), np.empty(self.grid_size ** 3, np.int32)
+        ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int))
+        _check(self._f("get_grid")(self._h, int(r), ip(a), ip(b), ip(c), ip(d)), "get_grid")
+        return a, b, c, d
 
 
 def models(lib=None):
     lib = lib if lib is not None else _ffi.ensemble_lib()
     return [lib.ya_ens_models_name(i).decode() for i in range(lib.ya_ens_models_count())]
+
+
+def grid_models(lib=None):
+    lib = lib if lib is not None else _ffi.grid_ensemble_lib()
+    return [lib.ya_gens_models_name(i).decode() for i in range(lib.ya_gens_models_count())]
