@@ -101,32 +101,73 @@ def friction_on_background(dist, i, j):
     return np.zeros(dist.shape, f32)
 
 
+# relu_plain_gabriel: the same functor, not declared stateless on the device (another kernel body, the same
+# numbers).  The two wide models (Po_cell: x y z theta phi; Cell: + u v): rows are xyz plus extra columns, the
+# geometry is xyz alone and the force on the extra columns is zero (relu_force's `Pt dF{0}`).
 MODELS = {"relu_gabriel": (relu_force, friction_w_neighbour),
+          "relu_plain_gabriel": (relu_force, friction_w_neighbour),
+          "relu_po_gabriel": (relu_force, friction_w_neighbour),
+          "relu_cell_gabriel": (relu_force, friction_w_neighbour),
           "clipped_gabriel": (clipped_spring, friction_w_neighbour),
           "wall_gabriel": (wall_relu_force, friction_on_background)}
+WIDTH = {"relu_po_gabriel": 5, "relu_cell_gabriel": 7}
+
+_memo = {}
+
+
+def _memoised(key, make):
+    """The lists of an input are made once (tests share them; the arrays are read-only)."""
+    if key not in _memo:
+        if len(_memo) >= 24:
+            _memo.pop(next(iter(_memo)))
+        out = make()
+        for a in out:
+            a.setflags(write=False)
+        _memo[key] = out
+    return _memo[key]
+
+
+def _key(X, *rest):
+    X = np.ascontiguousarray(X, f32)
+    return (X.shape, hash(X.tobytes())) + rest
 
 
 def gabriel_lists(X, gs, coefficient):
     """(ids, dist, kept) per cell, in the selection sort's order: kept[i, m] = pair (i, ids[i, m]) interacts."""
+    X = np.ascontiguousarray(X[:, :3], f32)
+    return _memoised(_key(X, gs, float(f32(coefficient))), lambda: _gabriel_lists(X, gs, coefficient))
+
+
+def _gabriel_lists(X, gs, coefficient):
     n = len(X)
-    ids, dist = selection_sort(*candidates(X, gs))
-    K = ids.shape[1]
-    kept = ids >= 0
-    cells = np.arange(n)
-    chunk = max(1, 4_000_000 // (K * K))
+    ids, dist = _memoised(_key(X, gs), lambda: selection_sort(*candidates(X, gs)))
+    kept = ids >= 0                                               # (a new array)
     coef = f32(coefficient)
-    for a in range(0, n, chunk):
-        b = min(n, a + chunk)
-        I, D = ids[a:b], dist[a:b]
-        Xi = X[a:b, None, :]
+    # cells in the order of their candidate counts, so that a chunk is padded to ITS widest list only (the
+    # sorted lists hold their candidates first); the test of candidates m0 .. m1 needs q < m1 only
+    count = kept.sum(axis=1)
+    by_count = np.argsort(count, kind="stable")
+    a = 0
+    while a < n:
+        b = min(n, a + max(1, 3_000_000 // max(int(count[by_count[a]]), 1) ** 2))
+        while b > a + 1 and (b - a) * int(count[by_count[b - 1]]) ** 2 > 6_000_000:
+            b = a + (b - a) // 2
+        rows = by_count[a:b]
+        K = max(int(count[rows[-1]]), 1)
+        I, D = ids[rows, :K], dist[rows, :K]
+        Xi = X[rows, None, :]
         Xj = X[np.maximum(I, 0)]                                  # (c, K, 3)
         mid = (f32(0.5) * (Xi + Xj)).astype(f32)
         radius = ((f32(0.5) * D).astype(f32) * coef).astype(f32)
-        r_mk = (mid[:, :, None, :] - Xj[:, None, :, :]).astype(f32)   # [c, m, q]
-        inside = dist3(r_mk) < radius[:, :, None]
-        earlier = np.tril(np.ones((K, K), bool), -1)[None] & (I >= 0)[:, None, :]
-        dropped = (inside & earlier).any(axis=2) & (I != cells[a:b, None])
-        kept[a:b] &= ~dropped
+        dropped = np.zeros(I.shape, bool)
+        for m0 in range(0, K, 64):
+            m1 = min(K, m0 + 64)
+            r_mk = (mid[:, m0:m1, None, :] - Xj[:, None, :m1, :]).astype(f32)   # [c, m, q]
+            inside = dist3(r_mk) < radius[:, m0:m1, None]
+            earlier = (np.arange(m1)[None, :] < np.arange(m0, m1)[:, None])[None] & (I[:, :m1] >= 0)[:, None, :]
+            dropped[:, m0:m1] = (inside & earlier).any(axis=2)
+        kept[rows, :K] &= ~(dropped & (I != rows[:, None]))
+        a = b
     return ids, dist, kept
 
 
@@ -139,6 +180,11 @@ def rhs(X, gs, coefficient, model, old_v=None, gen=None):
 def _rhs(X, gs, coefficient, model, old_v, gen):
     pw_int, pw_friction = MODELS[model]
     n = len(X)
+    width = X.shape[1]
+    assert width == WIDTH.get(model, 3)
+    X = np.ascontiguousarray(X[:, :3], f32)
+    if gen is not None:
+        assert width == 3
     ids, dist, kept = gabriel_lists(X, gs, coefficient)
     i = np.arange(n)
     F = np.zeros((n, 3), f32)
@@ -156,7 +202,8 @@ def _rhs(X, gs, coefficient, model, old_v, gen):
         if old_v is not None:
             sv = np.where(on[:, None], sv + fr[:, None] * old_v[jj], sv)
     dX = F if gen is None else (gen + F).astype(f32)
-    return np.where((sf > 0)[:, None], dX + sv / sf[:, None], dX).astype(f32)
+    dX = np.where((sf > 0)[:, None], dX + sv / sf[:, None], dX).astype(f32)
+    return np.hstack([dX, np.zeros((n, width - 3), f32)])         # no force on the extra columns
 
 
 def wall_gen(X):
@@ -181,14 +228,14 @@ def wall_gen(X):
 
 def forces(X, gs, coefficient, model):
     """What one dt = 0 step with a fixed lone cell leaves in old_v: the stage's right-hand side with old_v = 0."""
-    return rhs(X, gs, coefficient, model, old_v=np.zeros_like(X),
+    return rhs(X, gs, coefficient, model, old_v=np.zeros_like(X[:, :3]),
                gen=wall_gen(X) if model == "wall_gabriel" else None)
 
 
 def steps(X, steps_, dt, p, gs, coefficient, model):
     """Heun_solver::take_step with set_fixed(p), `steps_` times (as reference_grid_steps of the grid statement)."""
     X = X.copy()
-    old_v = np.zeros_like(X)
+    old_v = np.zeros_like(X[:, :3])
     dt = f32(dt)
     for _ in range(steps_):
         gen = wall_gen(X) if model == "wall_gabriel" else None
@@ -199,7 +246,7 @@ def steps(X, steps_, dt, p, gs, coefficient, model):
         dX1 = rhs(X1, gs, coefficient, model, old_v, gen1)
         dX1 = dX1 - dX1[p]
         X = (X + ((dX + dX1) * f32(0.5)) * dt).astype(f32)
-        old_v = ((dX + dX1) * f32(0.5)).astype(f32)
+        old_v = ((dX + dX1) * f32(0.5)).astype(f32)[:, :3]
     return X, old_v
 
 
@@ -208,6 +255,35 @@ def neighbour_counts(X, gs, coefficient):
     ids, dist, kept = gabriel_lists(X, gs, coefficient)
     i = np.arange(len(X))[:, None]
     return (kept & (ids != i) & ~(dist > f32(1))).sum(axis=1)
+
+
+def decision_cells(X, gs, coefficient, margin=1e-6):
+    """The cells with a decision that arithmetic within `margin` of binary32's could turn, from the positions in
+    binary64: a pair distance within `margin` of cube_size (1), or a (pair, earlier candidate) with
+    |dist_mk - radius| < margin * radius.  (What another rounding of sqrt or of its radicand may flip; the lists'
+    order is the binary32 statement's.)"""
+    X64 = np.ascontiguousarray(X[:, :3]).astype(f64)
+    n = len(X64)
+    mark = np.zeros(n, bool)
+    for a in range(0, n, 400):
+        d = np.sqrt(((X64[a:a + 400, None, :] - X64[None, :, :]) ** 2).sum(axis=2))
+        mark[a:a + 400] |= (np.abs(d - 1.0) < margin).any(axis=1)
+    ids, _, _ = gabriel_lists(X, gs, coefficient)
+    K = ids.shape[1]
+    coef = f64(f32(coefficient))
+    lower = np.tril(np.ones((K, K), bool), -1)[None]
+    chunk = max(1, 2_000_000 // (K * K))
+    for a in range(0, n, chunk):
+        I = ids[a:a + chunk]
+        Xi = X64[a:a + len(I), None, :]
+        Xj = X64[np.maximum(I, 0)]
+        radius = 0.5 * np.sqrt(((Xi - Xj) ** 2).sum(axis=2)) * coef
+        mid = 0.5 * (Xi + Xj)
+        d_mk = np.sqrt(((mid[:, :, None, :] - Xj[:, None, :, :]) ** 2).sum(axis=3))      # [c, m, q]
+        near = np.abs(d_mk - radius[:, :, None]) < margin * radius[:, :, None]
+        pair = (I >= 0) & (I != np.arange(a, a + len(I))[:, None])
+        mark[a:a + len(I)] |= (near & lower & pair[:, :, None] & (I >= 0)[:, None, :]).any(axis=(1, 2))
+    return mark
 
 
 def regular_hexagon(n, d=0.5):

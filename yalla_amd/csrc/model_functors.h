@@ -64,6 +64,42 @@ __device__ inline float3 wall_relu_force(float3 Xi, float3 r, float dist, int i,
     return dF;
 }
 
+// --- relu_force<float3> (include/inits.cuh) once more, statement for statement, as a function of its own that
+// is NOT listed under YA_STATELESS at the end of this file.  The omission is the point: a model that does not
+// know the macro gets the solvers' one-lane-per-cell bodies (under Gabriel_solver: gabriel::test_and_sum), and
+// `relu_plain_gabriel` holds that body bit for bit against `relu_gabriel`, which gets the other one. --------
+__device__ inline float3 relu_plain(float3 Xi, float3 r, float dist, int i, int j)
+{
+    float3 dF{0.f, 0.f, 0.f};
+
+    if (i == j) return dF;
+
+    if (dist > 1.f) return dF;
+
+    auto F = fmaxf(0.8f - dist, 0) * 2.f - fmaxf(dist - 0.8f, 0);
+    dF.x = r.x * F / dist;
+    dF.y = r.y * F / dist;
+    dF.z = r.z * F / dist;
+
+    return dF;
+}
+
+// --- tests/test_solvers.cu:339-352: no force, a per-cell counter of the pairs the solver lets interact,
+// written without atomics (one thread owns cell i).  NOT stateless, and not listed as such. -----------------
+YA_MODEL_VAR int* d_n_nbs;
+
+__device__ inline float3 count_neighbours(float3 Xi, float3 r, float dist, int i, int j)
+{
+    float3 dF{0.f, 0.f, 0.f};
+    if (i == j) return dF;
+
+    if (dist > 1.0f) return dF;
+
+    d_n_nbs[i] += 1;
+
+    return dF;
+}
+
 // A spring whose force fades to zero at the cut-off (NOT a reference model: the z-slab decomposition's
 // tests use it with friction_on_background).  Nothing about such a pair changes by a jump when it crosses
 // the cut-off, so a divided run has no pair "within rounding of the cut-off" to excuse a cell that differs
@@ -439,7 +475,8 @@ inline void proliferate(float rate, double mean_dist, unsigned seed, unsigned st
 
 // What the models say about their functors (include/solvers.cuh, YA_STATELESS; nothing on the
 // oracle): pure functions of their arguments, or counting with atomicAdd (branching.cu:105-107).
-// relu_w_epithelium is NOT listed: it counts with `d_mes_nbs[i] += 1` (passive_growth.cu:48-51).
+// relu_w_epithelium is NOT listed: it counts with `d_mes_nbs[i] += 1` (passive_growth.cu:48-51).  Neither are
+// count_neighbours (`d_n_nbs[i] += 1`) and relu_plain (on purpose: see there).
 #ifdef YA_STATELESS
 YA_STATELESS(float3, models::spring)
 YA_STATELESS(float3, models::clipped_spring)

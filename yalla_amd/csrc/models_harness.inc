@@ -391,6 +391,58 @@ struct Wall_gen : public No_gen<float3> {
     int keep_in_cube_order(C&, int) { return -2; }
 };
 
+// tests/test_solvers.cu:354-381: the counters of models::count_neighbours as a Property, reset_nbs as the
+// generic force (every stage), read with get_prop("n_nbs").  models::d_n_nbs is ONE symbol for every system
+// of this model in a process (as the growth models' symbols below): one live system at a time -- a second
+// one's step points the symbol at its own array, and the first one's next step points it back.
+struct Count_gen : public No_gen<float3> {
+    std::unique_ptr<Property<int>> n_nbs;
+    static const void*& symbol_of()
+    {
+        static const void* owner = nullptr;
+        return owner;
+    }
+    ~Count_gen()
+    {
+        if (symbol_of() == this) symbol_of() = nullptr;
+    }
+    template<typename C>
+    void ensure(C& cells)
+    {
+        if (n_nbs) return;
+        n_nbs.reset(new Property<int>{cells.n_max});
+        n_nbs->copy_to_device();  // zeros
+    }
+    template<typename C>
+    Generic_forces<float3> gen(C& cells)
+    {
+        ensure(cells);
+        if (symbol_of() != this) {
+            YA_SET_VAR(models::d_n_nbs, n_nbs->d_prop);
+            symbol_of() = this;
+        }
+        int* nbs = n_nbs->d_prop;
+        return [nbs](const int n, const float3* __restrict__ d_X, float3* d_dX) {
+            YA_ZERO(nbs, (size_t)n * sizeof(int));
+        };
+    }
+    // (the counters are indexed by id: no renumbering)
+    template<typename C>
+    int renumber_now(C&) { return -2; }
+    template<typename C>
+    int keep_in_cube_order(C&, int) { return -2; }
+    template<typename C>
+    int get_prop(C& cells, const char* name, int* values, int n)
+    {
+        if (std::string(name) != "n_nbs" || n > cells.n_max) return -2;
+        ensure(cells);
+        YA_SYNC();
+        n_nbs->copy_to_host();
+        for (int i = 0; i < n; i++) values[i] = n_nbs->h_prop[i];
+        return 0;
+    }
+};
+
 struct Sorting_params {
     static int set(const char* name, double v)
     {
@@ -766,6 +818,12 @@ static const Model model_table[] = {
     YA_MODEL("relu_gabriel", float3, GABRIEL, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
     YA_MODEL("clipped_gabriel", float3, GABRIEL, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
     YA_MODEL("wall_gabriel", float3, GABRIEL, models::wall_relu_force, friction_on_background<float3>, Wall_gen),
+    // ... a functor that is not declared YA_STATELESS (what a model that does not know the macro gets, as
+    // growth_w_wall.cu's own), tests/test_solvers.cu:339-381's neighbour counter, and the wide point types
+    YA_MODEL("relu_plain_gabriel", float3, GABRIEL, models::relu_plain, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_MODEL("count_gabriel", float3, GABRIEL, models::count_neighbours, friction_w_neighbour<float3>, Count_gen),
+    YA_MODEL("relu_po_gabriel", Po_cell, GABRIEL, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
+    YA_MODEL("relu_cell_gabriel", Cell, GABRIEL, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
     YA_MODEL_EXTRA
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);

@@ -8,7 +8,8 @@ select what is held fixed, `get_d_n()` reads the device-side count.  A model
 name selects the point type, the solver and the pairwise functor (C++ template
 arguments in the reference), e.g. "springs_grid" = Solution<float3,
 Grid_solver> stepping `spring`; "relu_gabriel", "clipped_gabriel" and "wall_gabriel" step
-Gabriel_solver (set_param("gabriel_coefficient", c), default 0.8).
+Gabriel_solver (set_param("gabriel_coefficient", c), default 0.8), as do "relu_plain_gabriel",
+"count_gabriel" (get_prop("n_nbs", n)), "relu_po_gabriel" and "relu_cell_gabriel".
 """
 import ctypes as C
 
