@@ -38,8 +38,14 @@
 // tile_force_rows, tile_force_coop_rows, heun_row; fold256.cuh): the kernels here add only where a
 // workgroup finds its replica's rows, its count and its id offset.
 //
+// WHOLE STEPS  cells.take_steps<my_force>(dt, 100) is 100 calls of take_step, bit for bit; where a replica fits
+// one workgroup's LDS (n_max <= ya::ens::whole_step_capacity<Pt>(), 1024 for the usual point types) and there are
+// no generic forces, it can run as ONE launch per steps_per_launch steps: a workgroup per replica runs the whole
+// steps from LDS (ya::ens::whole_steps, Ensemble::whole_steps).
+//
 // Not here ("Ensembles"): Gabriel_solver ensembles (the Solver template parameter is
-// their door, as it was Grid_solver's), the fast-arithmetic tier, graph capture, a per-replica dt, slabs.
+// their door, as it was Grid_solver's), the fast-arithmetic tier, graph capture, a per-replica dt, slabs, whole
+// steps for grid ensembles, several lanes per cell inside the whole-step kernel.
 #pragma once
 
 #include "solvers.cuh"
@@ -202,6 +208,152 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_ma
     } else if (zero_dX && local < n_max) {
         d_dX_all[base + local] = ya::zero<Pt>();
     }
+}
+
+// ---- whole steps in one launch ---------------------------------------------------------------------------
+// A replica of at most whole_step_capacity<Pt>() rows fits ONE workgroup's LDS with everything a Heun step
+// touches: X, X1, dX, dX1 (sizeof(Pt) per row each), old_v (12 B per row), the fold's scratch and the <= 4
+// partial sums.  ya::ens::whole_steps then runs n_steps whole steps there -- no launch boundary, no global
+// traffic in between -- in the order and the arithmetic of the six launches above, so that every bit agrees.
+// The arrays are laid out for n_max rows (dynamic LDS: small replicas share a CU).
+constexpr int WHOLE_STEP_MAX_ROWS = 1024;  // B_r = ceil(n_r / 256) <= 4: a lane's share of a partial sum is ONE row
+constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;  // gfx950: a workgroup may take the CU's whole LDS
+// ya::fixed_velocity_from_partials' own (static) fold scratch, which comes on top of the dynamic arrays
+constexpr size_t WHOLE_STEP_STATIC_LDS = 3 * UPDATE_BLOCK * sizeof(float);
+template<typename Pt>
+constexpr size_t whole_step_lds_bytes(const int n_max)
+{
+    return (size_t)n_max * (4 * sizeof(Pt) + sizeof(float3))                 // X, X1, dX, dX1, old_v
+           + (size_t)N_floats<Pt>::value * UPDATE_BLOCK * sizeof(float)      // fold256's scratch
+           + (size_t)N_floats<Pt>::value * (WHOLE_STEP_MAX_ROWS / UPDATE_BLOCK) * sizeof(float);  // the partial sums
+}
+// The largest n_max whose arrays fit one workgroup (1024 for every point type up to 8 floats).
+template<typename Pt>
+constexpr int whole_step_capacity()
+{
+    constexpr size_t fixed = whole_step_lds_bytes<Pt>(0) + WHOLE_STEP_STATIC_LDS;
+    static_assert(fixed < LDS_PER_WORKGROUP, "a point type whose fold scratch alone overflows the LDS");
+    constexpr size_t rows = (LDS_PER_WORKGROUP - fixed) / (4 * sizeof(Pt) + sizeof(float3));
+    return rows < (size_t)WHOLE_STEP_MAX_ROWS ? (int)rows : WHOLE_STEP_MAX_ROWS;
+}
+
+// tile_force_batched for the replica in LDS: one thread per cell (thread t owns rows t, t + 256, ...: the contract
+// of functors that keep per-cell state), partners straight from the LDS copy, j ascending over 0 .. n - 1 with
+// i == j included, ensemble-global ids, the pair and the right-hand side by tile_force_rows' own functions.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void whole_stage_force(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
+    Pt* sh_rhs)
+{
+    for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK) {
+        const int i = id_base + local;
+        const Pt Xi = sh_in[local];
+        Pt F = ya::zero<Pt>();
+        float3 sum_v{0.f, 0.f, 0.f};
+        float sum_friction = 0;
+#pragma unroll YA_TILE_UNROLL
+        for (int k = 0; k < n; k++)
+            tile_pair<Pt, pw_int, pw_friction>(Xi, sh_in[k], sh_v[k], i, id_base + k, F, sum_v, sum_friction);
+        store_rhs(sh_rhs, local, false, F, sum_v, sum_friction);
+    }
+}
+
+// The stage's fixed velocity, as reduce_partials_batched and resolve_fix give it: block b's lane t starts from 0,
+// adds row 256 b + t (B_r = reduce_blocks(n) <= 4 blocks cover the replica once), fold256, the B_r partials folded
+// by ya::fixed_velocity_from_partials; the fixed point's raw right-hand side.  Every thread calls it (barriers).
+template<typename Pt>
+__device__ __forceinline__ float3 whole_stage_fix(const int kind, const int n, const Pt* sh_rhs, const int fix_point,
+    float* sh_fold, float* sh_partials)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    float3 fix{0.f, 0.f, 0.f};
+    if (kind != FIX_POINT) {
+        const int B = reduce_blocks(n);
+        for (int b = 0; b < B; b++) {
+            float acc[NF];
+#pragma unroll
+            for (int k = 0; k < NF; k++) acc[k] = 0.f;
+            const int row = b * UPDATE_BLOCK + threadIdx.x;
+            if (row < n) {
+                const float* p = reinterpret_cast<const float*>(sh_rhs) + (size_t)row * NF;
+#pragma unroll
+                for (int k = 0; k < NF; k++) acc[k] = acc[k] + p[k];
+            }
+            fold256<NF>(acc, sh_fold);
+            if (threadIdx.x < NF) sh_partials[b * NF + threadIdx.x] = sh_fold[threadIdx.x * UPDATE_BLOCK];
+            __syncthreads();  // (the next fold writes sh_fold)
+        }
+        fix = fixed_velocity_from_partials<NF>(sh_partials, B, n);
+    }
+    if (kind != FIX_MEAN) {
+        const Pt p = sh_rhs[fix_point];
+        fix.x = p.x;
+        fix.y = p.y;
+        if (kind == FIX_POINT) fix.z = p.z;
+    }
+    return fix;
+}
+
+// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
+// Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
+// end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
+// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, const int* __restrict__ d_n, const float dt,
+    const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char whole_step_lds[];
+    constexpr int NF = N_floats<Pt>::value;
+    const int replica = blockIdx.x;
+    const int n = count_of(d_n, replica, n_max);
+    if (n <= 0) return;  // (the whole workgroup; an empty replica is left alone)
+    Pt* sh_X = reinterpret_cast<Pt*>(whole_step_lds);
+    Pt* sh_X1 = sh_X + n_max;
+    Pt* sh_dX = sh_X1 + n_max;
+    Pt* sh_dX1 = sh_dX + n_max;
+    float3* sh_v = reinterpret_cast<float3*>(sh_dX1 + n_max);
+    float* sh_fold = reinterpret_cast<float*>(sh_v + n_max);
+    float* sh_partials = sh_fold + NF * UPDATE_BLOCK;
+
+    const size_t base = (size_t)replica * n_max;
+    Pt* __restrict__ d_X = d_X_all + base;
+    float3* __restrict__ d_old_v = d_old_v_all + base;
+    for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK) {
+        sh_X[local] = d_X[local];
+        sh_v[local] = d_old_v[local];
+    }
+    __syncthreads();
+
+    for (int step = 0; step < n_steps; step++) {
+        // predictor: X1 = X + (dX - fix) dt (euler_step_batched)
+        whole_stage_force<Pt, pw_int, pw_friction>(n, (int)base, sh_X, sh_v, sh_dX);
+        __syncthreads();
+        const float3 fix = whole_stage_fix<Pt>(kind1, n, sh_dX, fix_point, sh_fold, sh_partials);
+        for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK)
+            sh_X1[local] = sh_X[local] + ya::minus_fix(sh_dX[local], fix) * dt;
+        __syncthreads();
+        // corrector (heun_step_batched): old_v is written only after this barrier, when stage 2's forces have read it
+        whole_stage_force<Pt, pw_int, pw_friction>(n, (int)base, sh_X1, sh_v, sh_dX1);
+        __syncthreads();
+        const float3 fix1 = whole_stage_fix<Pt>(kind2, n, sh_dX1, fix_point, sh_fold, sh_partials);
+        const float fix_first[3] = {fix.x, fix.y, fix.z};  // stage 1's, as the predictor leaves it in d_fix_first
+        for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK)
+            ya::heun_row(local, dt, fix_first, fix1, sh_dX, sh_dX1, sh_X, sh_v, false);
+        __syncthreads();
+    }
+
+    for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK) {
+        d_X[local] = sh_X[local];
+        d_old_v[local] = sh_v[local];
+    }
+}
+
+// Whether whole-step launches beat the six-launch step when the model leaves the choice to the engine
+// (Ensemble::whole_steps == 0).  THIS RULE IS A PLACEHOLDER until measured (profiles/ensemble_whole_step_bench.json):
+// one workgroup per CU; below that the six-launch path spreads a replica over more CUs.
+inline bool whole_steps_pay(const int n_replicas, const int n_max)
+{
+    return n_replicas >= 256;
 }
 
 // Lanes per cell of the force launch when the model leaves the choice to the engine and its functors are
@@ -387,6 +539,15 @@ protected:
     // every row of d_dX / d_dX1 was left zeroed by an update kernel (take_step is their only writer)
     bool rhs_zeroed[2] = {false, false};
 
+    // take_step's expression for what a stage holds fixed (1 = predictor, 2 = corrector)
+    int fix_kind_of(const int stage) const
+    {
+        const bool xy = stage == 1 && fix_com_z;
+        return (fix_com && !fix_com_z) ? ya::ens::FIX_MEAN
+               : xy                    ? ya::ens::FIX_POINT_XY
+               : fix_com               ? ya::ens::FIX_MEAN
+                                       : ya::ens::FIX_POINT;
+    }
     int max_blocks() const { return ya::ens::reduce_blocks(n_max); }
     dim3 grid_of(int blocks_per_replica) const { return dim3((unsigned)((size_t)n_replicas * blocks_per_replica)); }
 };
@@ -416,10 +577,59 @@ public:
     // choice gives the same bits.
     int lanes_per_cell = 0;
 
+    // take_steps as whole-step launches (ya::ens::whole_steps: one workgroup per replica runs the steps from LDS):
+    // -1 = never, 1 = whenever the call is eligible, 0 (default) = the engine's choice, eligible and
+    // ya::ens::whole_steps_pay(n_replicas, n_max).  Eligible: no generic forces and
+    // n_max <= ya::ens::whole_step_capacity<Pt>().  Any choice gives the same bits.
+    int whole_steps = 0;
+    // A whole-step launch runs at most this many steps (no single kernel runs unboundedly long); take_steps
+    // splits longer requests.
+    int steps_per_launch = 256;
+    // whole-step launches made so far (which path ran)
+    long whole_step_launches = 0;
+
     // Six launches per take_step (per stage: forces, partial sums, update).
     Ensemble(int n_replicas, int n_max) : Base{n_replicas, n_max}
     {
         assert((size_t)n_replicas * (size_t)((n_max + 3) / 4) <= (size_t)0x7fffffff);  // (a launch's x dimension)
+    }
+
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
+    }
+    // n_steps Heun steps of every replica, bit for bit n_steps calls of take_step: as whole-step launches of at
+    // most steps_per_launch steps each where the call is eligible and whole_steps allows it, as that loop otherwise.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        const bool eligible = ya::is_no_gen_forces<Pt>(gen_forces) && this->n_max <= ya::ens::whole_step_capacity<Pt>();
+        const bool whole = eligible && (whole_steps > 0 ||
+                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, this->n_max)));
+        if (!whole) {
+            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
+            return;
+        }
+        assert(steps_per_launch >= 1);
+        const auto kernel = &ya::ens::whole_steps<Pt, pw_int, pw_friction>;
+        const size_t lds = ya::ens::whole_step_lds_bytes<Pt>(this->n_max);
+        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
+        static size_t lds_allowed = 64 * 1024;
+        if (lds > lds_allowed) {
+            YA_CHECK((int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_allowed = lds;
+        }
+        for (int done = 0; done < n_steps;) {
+            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
+            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k,
+                this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v);
+            whole_step_launches++;
+            done += k;
+        }
+        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
+        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
     }
 
 protected:

@@ -384,6 +384,26 @@ __device__ __forceinline__ Pt store_rhs(
     return dX;
 }
 
+// One pair (i, j) of the all-pairs force: the functors' terms added to cell i's running sums, in the statements
+// and the order every one-lane all-pairs loop has (tile_force_rows below, ya::ens::whole_steps in
+// include/ensemble.cuh).  vj is read only where the friction is not zero.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void tile_pair(const Pt Xi, const Pt& Xj, const float3& vj, const int i, const int j, Pt& F,
+    float3& sum_v, float& sum_friction)
+{
+    Pt r = Xi - Xj;
+    float dist = dist3(r.x, r.y, r.z);
+    F += pw_int(Xi, r, dist, i, j);
+    float friction = pw_friction(Xi, r, dist, i, j);
+    sum_friction += friction;
+    if (friction != 0) {
+        float3 v = vj;
+        sum_v.x += friction * v.x;
+        sum_v.y += friction * v.y;
+        sum_v.z += friction * v.z;
+    }
+}
+
 // All-pairs force (replaces compute_tile, solvers.cuh:284-322): j ascending,
 // functor called for every (i, j) including i == j.
 // The body, for one system's n rows at d_X / d_old_v / d_dX: the workgroup is the system's `block`-th and
@@ -420,17 +440,7 @@ __device__ __forceinline__ void tile_force_rows(const int n, const int block, co
 #pragma unroll YA_TILE_UNROLL
             for (int k = 0; k < n_tile; k++) {
                 const int j = id_base + tile_start + k;
-                Pt r = Xi - sh_X[k];
-                float dist = dist3(r.x, r.y, r.z);
-                F += pw_int(Xi, r, dist, i, j);
-                float friction = pw_friction(Xi, r, dist, i, j);
-                sum_friction += friction;
-                if (friction != 0) {
-                    float3 v = sh_v[k];
-                    sum_v.x += friction * v.x;
-                    sum_v.y += friction * v.y;
-                    sum_v.z += friction * v.z;
-                }
+                tile_pair<Pt, pw_int, pw_friction>(Xi, sh_X[k], sh_v[k], i, j, F, sum_v, sum_friction);
             }
         }
     }

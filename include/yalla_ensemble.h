@@ -10,7 +10,8 @@
  * "push" (no pairwise force; push_tile's generic force in one call on the flat arrays: the
  * right-hand side of cell 1 of EVERY replica, global row r * n_max + 1, is set to (1, 0, 0)).
  *
- * HIP only: there is no CPU build of this header.  All functions return 0 on success, a negative
+ * HIP only: there is no CPU build of this header.  All functions return 0 on success (ya_ens_take_steps:
+ * 0 or a count, see there), a negative
  * value for a harness error (-1 unknown model, -2 unknown parameter, -3 bad argument), or abort
  * the process on a HIP error.
  */
@@ -41,7 +42,10 @@ int ya_ens_get_d_n(ya_ens* ens, int replica); /* blocking read of the device-sid
 int ya_ens_copy_to_device(ya_ens* ens);       /* every row and every count */
 int ya_ens_copy_to_host(ya_ens* ens);
 
-/* n_steps calls of take_step<pw_int, pw_friction>(dt[, gen_forces]): queued, not waited for. */
+/* take_steps<pw_int, pw_friction>(dt, n_steps[, gen_forces]): the bits of n_steps calls of take_step; queued,
+ * not waited for.  With "whole_steps" at its harness default of -1 it IS that loop of take_step.
+ * Returns the number of whole-step launches the call made, by which Ensemble::whole_step_launches rose (>= 0,
+ * at most n_steps; always 0 with whole_steps = -1): which path ran. */
 int ya_ens_take_steps(ya_ens* ens, float dt, int n_steps);
 int ya_ens_synchronize(ya_ens* ens);
 
@@ -53,7 +57,12 @@ int ya_ens_set_fixed(ya_ens* ens, int mode, int local_point);
 int ya_ens_get_old_v(ya_ens* ens, float* out);
 int ya_ens_set_old_v(ya_ens* ens, const float* in);
 
-/* "tile_lanes": Ensemble::lanes_per_cell (0 = the engine's choice, 1, 16, 64). */
+/* "tile_lanes": Ensemble::lanes_per_cell (0 = the engine's choice, 1, 16, 64).
+ * "whole_steps": Ensemble::whole_steps -- -1 (the harness's default) = six launches per step always, 1 = whole
+ * steps from LDS in one launch (ya::ens::whole_steps) whenever the call is eligible (no generic forces, so never
+ * "push"; n_max within the point type's capacity, 1024 for every model here), 0 = the engine's choice.
+ * "steps_per_launch": Ensemble::steps_per_launch (>= 1), the most steps one such launch runs.
+ * Any setting gives the same bits. */
 int ya_ens_set_param(ya_ens* ens, const char* name, double value);
 
 #pragma GCC visibility pop

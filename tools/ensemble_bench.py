@@ -5,6 +5,7 @@
     python tools/ensemble_bench.py --trace-shape 64 800 --steps 50     # what a rocprofv3 run wraps
     python tools/ensemble_bench.py --solver grid [--out profiles/ensemble_grid_bench.json]
     python tools/ensemble_bench.py --solver grid --trace-shape 64 2000 --steps 50
+    python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -21,6 +22,12 @@ YA_GRAPH_MAX_CELLS each of them replays a captured graph of its step) against on
 grid_size) with lanes 0 (ya::ens::grid_lanes_for), 1, 4, 8, 16; M in {1, 8, 64, 512} x n in {500, 2000, 10^4,
 5 * 10^4} with M * n <= 5 * 10^6; grid_size fitted to the ball (the ensemble scans M * grid_size^3 counters per
 stage).  The row's spread is that of the worse side.
+
+--whole-steps: ONE Ensemble("relu", M, n) per shape, the same protocol, three settings alternating: the six-launch
+step (whole_steps -1, the baseline), whole-step launches of one step each (whole_steps 1, steps_per_launch 1: no
+launches between the stages) and of up to 256 steps each (steps_per_launch at its default: none between the steps
+either).  M in {1, 16, 64, 256, 1024, 4096} x n in {32, 100, 256, 512, 1024} with M * n^2 <= 2^28, so that a window
+stays short.  ratio_* = the setting's rate over the baseline's.
 """
 import argparse
 import json
@@ -40,6 +47,8 @@ SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 1
 LANES = (0, 1, 16, 64)
 GRID_SHAPES = [(m, n) for n in (500, 2000, 10000, 50000) for m in (1, 8, 64, 512) if m * n <= 5000000]
 GRID_LANES = (0, 1, 4, 8, 16)
+WHOLE_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
+WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), "whole_256_steps_per_launch": (1, 256)}
 DT = 0.01
 GRID = False  # --solver grid
 
@@ -86,6 +95,10 @@ class Together:
 
     def lanes(self, lanes):
         self.ens.set_param("lanes" if GRID else "tile_lanes", lanes)
+
+    def whole(self, whole_steps, steps_per_launch):
+        self.ens.set_param("whole_steps", whole_steps)
+        self.ens.set_param("steps_per_launch", steps_per_launch)
 
     def steps(self, k):
         self.ens.take_step(DT, k)
@@ -148,6 +161,57 @@ def measure(m, n, window, repeats):
     return row
 
 
+def measure_whole(m, n, window, repeats):
+    b = Together(m, n)
+    try:
+        ks = {}
+        for key, setting in WHOLE_SETTINGS.items():
+            b.whole(*setting)
+            b.steps(3)
+            ks[key] = calibrate(b, window)
+        samples = {key: [] for key in ks}
+        for _ in range(repeats):  # six, whole 1, whole 256, six, ...
+            for key, setting in WHOLE_SETTINGS.items():
+                b.whole(*setting)
+                samples[key].append(timed(b, ks[key]))
+        launches = b.ens.whole_step_launches
+    finally:
+        b.close()
+    row = {"n_replicas": m, "n": n, "whole_step_launches": launches}
+    for key in WHOLE_SETTINGS:
+        row[key] = summary(samples[key], m * n, ks[key])
+    for key in list(WHOLE_SETTINGS)[1:]:
+        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row["six_launches"]["cell_updates_per_s"]
+    row["spread"] = max(row[key]["spread"] for key in WHOLE_SETTINGS)  # of the worst side
+    return row
+
+
+def main_whole(args):
+    shapes = WHOLE_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting: code objects loaded, allocator and clocks settled
+        run = Together(m, n)
+        for setting in WHOLE_SETTINGS.values():
+            run.whole(*setting)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure_whole(m, n, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:10.1f} us/step" for key in WHOLE_SETTINGS)
+              + f"   ratios {r['ratio_whole_1_step_per_launch']:.2f} {r['ratio_whole_256_steps_per_launch']:.2f}"
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --whole-steps", "model": "relu", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio": min(r["ratio_whole_256_steps_per_launch"] for r in rows),
+                      "max_ratio": max(r["ratio_whole_256_steps_per_launch"] for r in rows)}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None)
@@ -158,7 +222,14 @@ def main():
                     help="only step one Ensemble of this shape --steps times (for a kernel trace)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--solver", choices=("tile", "grid"), default="tile")
+    ap.add_argument("--whole-steps", action="store_true",
+                    help="whole-step launches against the six-launch step of the same Ensemble (tile solver only)")
     args = ap.parse_args()
+    if args.whole_steps:
+        if args.solver != "tile" or args.trace_shape:
+            ap.error("--whole-steps measures the all-pairs ensemble, and takes no --trace-shape")
+        main_whole(args)
+        return
     global GRID, LANES, SHAPES
     if args.solver == "grid":
         GRID, LANES, SHAPES = True, GRID_LANES, GRID_SHAPES

@@ -31,10 +31,12 @@ struct Base {
     virtual void copy_to_device() = 0;
     virtual void copy_to_host() = 0;
     virtual int get_d_n(int r) = 0;
-    virtual void take_steps(float dt, int n_steps) = 0;
+    virtual long take_steps(float dt, int n_steps) = 0;  // returns the whole-step launches it made
     virtual void set_fixed(int mode, int point) = 0;
     virtual float3* d_old_v() = 0;
     virtual void set_lanes(int lanes) = 0;
+    virtual void set_whole_steps(int mode) = 0;
+    virtual void set_steps_per_launch(int steps) = 0;
 };
 
 // models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
@@ -57,7 +59,9 @@ struct Oscillator_ids : public No_gen<float4> {
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
 struct Sim : public Base {
     Ensemble<Pt> cells;
-    Sim(int n_replicas, int n_max) : cells{n_replicas, n_max} {}
+    // The harness's own default is the six-launch step (whole_steps = -1): what its callers ran before the
+    // whole-step launches existed; set_param("whole_steps", 0 | 1) opts in.
+    Sim(int n_replicas, int n_max) : cells{n_replicas, n_max} { cells.whole_steps = -1; }
     int n_floats() override { return sizeof(Pt) / sizeof(float); }
     int n_replicas() override { return cells.n_replicas; }
     int n_max() override { return cells.n_max; }
@@ -66,11 +70,13 @@ struct Sim : public Base {
     void copy_to_device() override { cells.copy_to_device(); }
     void copy_to_host() override { cells.copy_to_host(); }
     int get_d_n(int r) override { return cells.get_d_n(r); }
-    void take_steps(float dt, int n_steps) override
+    long take_steps(float dt, int n_steps) override
     {
+        const long launches_before = cells.whole_step_launches;
         Policy::before_steps(cells.n_max);
         Generic_forces<Pt> gen = Policy::gen(cells.n_replicas, cells.n_max);
-        for (int s = 0; s < n_steps; s++) cells.template take_step<pw_int, pw_friction>(dt, gen);
+        cells.template take_steps<pw_int, pw_friction>(dt, n_steps, gen);  // (push's generic force: never whole steps)
+        return cells.whole_step_launches - launches_before;
     }
     void set_fixed(int mode, int point) override
     {
@@ -80,6 +86,8 @@ struct Sim : public Base {
     }
     float3* d_old_v() override { return cells.d_old_v; }
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
+    void set_whole_steps(int mode) override { cells.whole_steps = mode; }
+    void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
 };
 
 using Factory = Base* (*)(int, int);
@@ -168,8 +176,8 @@ int ya_ens_copy_to_host(ya_ens* e)
 }
 int ya_ens_take_steps(ya_ens* e, float dt, int n_steps)
 {
-    e->p->take_steps(dt, n_steps);
-    return 0;
+    // (at most n_steps launches; 0 with the harness's default of whole_steps = -1)
+    return (int)e->p->take_steps(dt, n_steps);
 }
 int ya_ens_synchronize(ya_ens*)
 {
@@ -204,6 +212,16 @@ int ya_ens_set_param(ya_ens* e, const char* name, double v)
         const int lanes = (int)v;
         if (lanes != 0 && lanes != 1 && lanes != 16 && lanes != 64) return -3;
         e->p->set_lanes(lanes);
+        return 0;
+    }
+    if (std::string(name) == "whole_steps") {
+        if (v != -1 && v != 0 && v != 1) return -3;
+        e->p->set_whole_steps((int)v);
+        return 0;
+    }
+    if (std::string(name) == "steps_per_launch") {
+        if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
+        e->p->set_steps_per_launch((int)v);
         return 0;
     }
     return -2;

@@ -14,7 +14,13 @@ replica and apply to every replica.  Each replica holds, bit for bit, what a
         cells.take_step(0.05, 100)
         X = cells.positions(r)
 
-`GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh).
+`set_param("whole_steps", 1)` lets `take_step(dt, steps)` run as whole-step launches (ya::ens::whole_steps: one
+workgroup per replica runs up to `set_param("steps_per_launch", k)` steps from LDS, no launch boundary in between)
+wherever the model has no generic forces and n_max is at most 1024; 0 leaves the choice to the engine, -1 (this
+harness's default) never does.  The bits are the same either way; `whole_step_launches` counts the launches made.
+
+`GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
+build per stage always.
 """
 import ctypes as C
 
@@ -86,6 +92,7 @@ class Ensemble:
         ptr = self._f("h_X")(self._h)
         self.h_X = np.ctypeslib.as_array(ptr, shape=(self.n_replicas, self.n_max, self.n_floats))
         self.h_n = _Counts(self)
+        self._whole_step_launches = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -119,7 +126,15 @@ class Ensemble:
         return n
 
     def take_step(self, dt, steps=1):
-        _check(self._f("take_steps")(self._h, float(dt), int(steps)), "take_step")
+        launches = self._f("take_steps")(self._h, float(dt), int(steps))  # (>= 0: the whole-step launches it made)
+        _check(min(launches, 0), "take_step")
+        self._whole_step_launches += launches
+
+    @property
+    def whole_step_launches(self):
+        """Whole-step launches made so far (Ensemble::whole_step_launches): 0 unless set_param("whole_steps", 0 | 1)
+        allowed them and the call was eligible."""
+        return self._whole_step_launches
 
     def synchronize(self):
         _check(self._f("synchronize")(self._h), "synchronize")
@@ -188,6 +203,10 @@ class GridEnsemble(Ensemble):
     @cube_size.setter
     def cube_size(self, value):
         _check(self._f("set_cube_size")(self._h, float(value)), "set cube_size")
+
+    @property
+    def whole_step_launches(self):
+        raise AttributeError("a grid ensemble has no whole-step launches")
 
     def status(self, r, clear=True):
         bits = self._f("status")(self._h, int(r), int(bool(clear)))
