@@ -43,9 +43,11 @@
 // no generic forces, it can run as ONE launch per steps_per_launch steps: a workgroup per replica runs the whole
 // steps from LDS (ya::ens::whole_steps, Ensemble::whole_steps).
 //
-// Not here ("Ensembles"): Gabriel_solver ensembles (the Solver template parameter is
-// their door, as it was Grid_solver's), the fast-arithmetic tier, graph capture, a per-replica dt, slabs, whole
-// steps for grid ensembles, several lanes per cell inside the whole-step kernel.
+// Ensemble<Pt, Gabriel_solver> (ensemble_gabriel.cuh, included after it) is the same for M Gabriel_solver systems,
+// on the grid form's build.
+//
+// Not here ("Ensembles"): the fast-arithmetic tier, graph capture, a per-replica dt or
+// gabriel_coefficient, slabs, whole steps for grid ensembles, several lanes per cell inside the whole-step kernel.
 #pragma once
 
 #include "solvers.cuh"
@@ -376,7 +378,7 @@ inline int lanes_for(const int n_replicas, const int n_max)
 namespace ya {
 namespace ens {
 
-// What both forms of Ensemble are: the flat replica-major arrays, the counts, the fixed modes and THE STEP.
+// What every form of Ensemble is: the flat replica-major arrays, the counts, the fixed modes and THE STEP.
 // Form (CRTP) supplies the forces of a stage,
 //     template<pw_int, pw_friction> void forces(const Pt* d_in, Pt* d_rhs, bool has_gen)
 // which leaves every replica's right-hand sides of the cells d_in[r * n_max + 0 .. n_r) in d_rhs, added to what
@@ -556,12 +558,14 @@ protected:
 }  // namespace ya
 
 
-// Ensemble<Pt> / Ensemble<Pt, Tile_solver>{n_replicas, n_max} and Ensemble<Pt, Grid_solver>{n_replicas, n_max,
-// grid_size, cube_size} (ensemble_grid.cuh); no other solver has an ensemble.
+// Ensemble<Pt> / Ensemble<Pt, Tile_solver>{n_replicas, n_max}, Ensemble<Pt, Grid_solver>{n_replicas, n_max,
+// grid_size, cube_size} (ensemble_grid.cuh) and Ensemble<Pt, Gabriel_solver>{n_replicas, n_max, grid_size, cube_size,
+// gabriel_coefficient} (ensemble_gabriel.cuh); no other solver has an ensemble.
 template<typename Pt, template<typename> class Solver = Tile_solver, typename Which = void>
 class Ensemble {
     static_assert(!std::is_same<Which, void>::value,
-        "Ensemble steps all-pairs or grid systems: Ensemble<Pt, Tile_solver> or Ensemble<Pt, Grid_solver>");
+        "Ensemble steps all-pairs, grid or Gabriel systems: Ensemble<Pt, Tile_solver>, Ensemble<Pt, Grid_solver> or "
+        "Ensemble<Pt, Gabriel_solver>");
 };
 
 template<typename Pt, template<typename> class Solver>
@@ -658,3 +662,4 @@ protected:
 };
 
 #include "ensemble_grid.cuh"
+#include "ensemble_gabriel.cuh"

@@ -28,8 +28,11 @@
 // replica's sticky YA_STATUS_OUT_OF_GRID bit in d_status[r]; the step never reads it.  status(r) reads it;
 // copy_to_host() aborts naming the replica, as Grid::check_status does.  Other replicas are unaffected.
 //
-// Not here: Gabriel ensembles, the fast-arithmetic tier, graph capture, a per-replica dt, cube_size or grid_size,
-// the sorted-space second stage, grid_force_bits' tails, slabs.
+// SHARED  The build, its arrays and the status code are ya::ens::Grid_form (below), which Ensemble<Pt, Gabriel_solver>
+// (ensemble_gabriel.cuh) derives from too.
+//
+// Not here: the fast-arithmetic tier, graph capture, a per-replica dt, cube_size or grid_size, the sorted-space
+// second stage, grid_force_bits' tails, slabs.
 #pragma once
 
 #include "cube_id.cuh"
@@ -61,13 +64,16 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_count_batched(const int n_m
 
 // Exclusive scan of a replica's n_cubes counters by ONE workgroup that walks them, 2048 at a time, with a
 // running carry: offs[c] relative to the replica's first row, offs[n_cubes] = n_r, the counters re-zeroed in
-// passing.  No workgroup waits for another.
+// passing.  No workgroup waits for another.  BUILD_EMPTY = false leaves an empty replica's offs as they are (its
+// counters are zero already): what a lone Gabriel_solver's step, which returns before its build, leaves of its Grid.
 constexpr int SCAN_ITEMS = 8;
+template<bool BUILD_EMPTY>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_scan_batched(const int n_max, const int* __restrict__ d_n,
     const int n_cubes, int* __restrict__ count_all, int* __restrict__ offs_all)
 {
     __shared__ int sh_wave[2][UPDATE_BLOCK / 64];
     const int r = blockIdx.x;
+    if (!BUILD_EMPTY && count_of(d_n, r, n_max) <= 0) return;  // (the whole workgroup)
     const int n = max(count_of(d_n, r, n_max), 0);  // (an empty replica's grid is built too, empty: a lone Solution's is)
     int* __restrict__ count = count_all + (size_t)r * n_cubes;
     int* __restrict__ offs = offs_all + (size_t)r * (n_cubes + 1);
@@ -203,15 +209,13 @@ inline int grid_lanes_for(const int n_replicas, const int n_max)
     return cells > 120000 ? 1 : coop::lanes_for((int)cells);
 }
 
-}  // namespace ens
-}  // namespace ya
 
-
-template<typename Pt, template<typename> class Solver>
-class Ensemble<Pt, Solver, std::enable_if_t<std::is_same<Solver<Pt>, Grid_solver<Pt>>::value>>
-    : public ya::ens::Stepper<Pt, Ensemble<Pt, Solver>> {
-    using Base = ya::ens::Stepper<Pt, Ensemble<Pt, Solver>>;
-    friend Base;
+// What the ensembles of the grid-based solvers share (CRTP, between Stepper and Ensemble<Pt, Grid_solver> /
+// Ensemble<Pt, Gabriel_solver>): the per-replica grid arrays of this file's header, their build in four launches,
+// the status bits.  Form is the Ensemble itself; it supplies Stepper's forces of a stage, which start with build().
+template<typename Pt, typename Form>
+class Grid_form : public Stepper<Pt, Form> {
+    using Base = Stepper<Pt, Form>;
 
 public:
     const int grid_size, n_cubes;
@@ -219,18 +223,9 @@ public:
     // The reference's Grid arrays, per replica (this file's header): [rows()], [rows()], [n_replicas * (n_cubes + 1)]
     int *d_cube_id, *d_point_id, *d_offs;
     int* d_status;  // [n_replicas] sticky YA_STATUS_OUT_OF_GRID bits, never read by the step
-    // 0 (default) = the engine's choice: one lane per cell (grid_force_bits_batched) unless the functors are
-    // declared stateless (YA_STATELESS: one thread per cell is the contract of `d_mes_nbs[i] += 1`), then by the
-    // size of the whole launch (ya::ens::grid_lanes_for); 1 = one lane per cell; 4, 8, 16 = grid_force_coop_batched.
-    // Any choice gives the same bits.
-    int lanes_per_cell = 0;
-    Ya_sum_order sum_order = YA_SUM_REFERENCE;  // as Grid_computer::sum_order
-    // the one-lane kernel keeps old_v in LDS too while the launch's n_replicas * n_max cells are at most this many
-    // (Grid_computer::stage_v_max: is the launch big enough to hide the L2's latency?)
-    int stage_v_max = 130000;
 
-    Ensemble(int n_replicas, int n_max, int grid_size = 50, float cube_size = 1)
-        : Base{checked(n_replicas, n_max, grid_size), n_max}, grid_size{grid_size},
+    Grid_form(const char* solver, int n_replicas, int n_max, int grid_size, float cube_size)
+        : Base{checked(solver, n_replicas, n_max, grid_size), n_max}, grid_size{grid_size},
           n_cubes{grid_size * grid_size * grid_size}, cube_size{cube_size}
     {
         const size_t total = this->rows();
@@ -251,7 +246,7 @@ public:
         YA_CHECK(ya_malloc((void**)&d_status, (size_t)n_replicas * sizeof(int)));
         YA_CHECK(ya_memset_async(d_status, 0, (size_t)n_replicas * sizeof(int), nullptr));
     }
-    ~Ensemble()
+    ~Grid_form()
     {
         ya_free(d_cube_id);
         ya_free(d_point_id);
@@ -308,35 +303,79 @@ protected:
     ya::Entry<Pt>* d_sorted;
     float4* d_sorted_v;
 
-    static int checked(int n_replicas, int n_max, int grid_size)
+    static int checked(const char* solver, int n_replicas, int n_max, int grid_size)
     {
         if (!sizes_ok(n_replicas, n_max, grid_size)) {
             fprintf(stderr,
-                "yalla-hip: Ensemble<Pt, Grid_solver>{%d, %d, %d}: sizes must be positive, grid_size <= %d (cube ids "
+                "yalla-hip: Ensemble<Pt, %s>{%d, %d, %d}: sizes must be positive, grid_size <= %d (cube ids "
                 "are binary32), and n_replicas * n_max and n_replicas * (grid_size^3 + 1) at most 2^31 - 1 (ids, "
                 "launch sizes and counter offsets are ints)\n",
-                n_replicas, n_max, grid_size, YA_MAX_GRID_SIZE);
+                solver, n_replicas, n_max, grid_size, YA_MAX_GRID_SIZE);
             abort();
         }
         return n_replicas;
     }
 
+    // Four launches: the grid of every replica from d_in, the cells gathered into d_sorted / d_sorted_v.
+    // BUILD_EMPTY: a replica with n_r = 0 gets an empty grid (true) or keeps the arrays it has (false).
+    template<bool BUILD_EMPTY = true>
+    void build(const Pt* d_in)
+    {
+        const int n_max = this->n_max, n_replicas = this->n_replicas;
+        const int* d_n = this->d_n;
+        const int row_blocks = (n_max + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
+        grid_count_batched<Pt><<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(
+            n_max, row_blocks, d_n, d_in, cube_size, grid_size, n_cubes, d_cube_of, d_rank, d_count, d_status);
+        grid_scan_batched<BUILD_EMPTY><<<n_replicas, ya::UPDATE_BLOCK>>>(n_max, d_n, n_cubes, d_count, d_offs);
+        grid_scatter_batched<<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(
+            n_max, row_blocks, d_n, n_cubes, d_cube_of, d_rank, d_offs, d_arrival, d_cube_id);
+        grid_order_batched<Pt><<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(n_max, row_blocks, d_n, n_cubes,
+            d_arrival, d_cube_id, d_offs, d_in, this->d_old_v, d_point_id, d_sorted, d_sorted_v);
+    }
+};
+
+}  // namespace ens
+}  // namespace ya
+
+
+template<typename Pt, template<typename> class Solver>
+class Ensemble<Pt, Solver, std::enable_if_t<std::is_same<Solver<Pt>, Grid_solver<Pt>>::value>>
+    : public ya::ens::Grid_form<Pt, Ensemble<Pt, Solver>> {
+    using Base = ya::ens::Grid_form<Pt, Ensemble<Pt, Solver>>;
+    friend ya::ens::Stepper<Pt, Ensemble<Pt, Solver>>;
+
+public:
+    // (grid_size, n_cubes, cube_size, d_cube_id, d_point_id, d_offs, d_status, sizes_ok, status, check_status,
+    // copy_to_host: ya::ens::Grid_form)
+    // 0 (default) = the engine's choice: one lane per cell (grid_force_bits_batched) unless the functors are
+    // declared stateless (YA_STATELESS: one thread per cell is the contract of `d_mes_nbs[i] += 1`), then by the
+    // size of the whole launch (ya::ens::grid_lanes_for); 1 = one lane per cell; 4, 8, 16 = grid_force_coop_batched.
+    // Any choice gives the same bits.
+    int lanes_per_cell = 0;
+    Ya_sum_order sum_order = YA_SUM_REFERENCE;  // as Grid_computer::sum_order
+    // the one-lane kernel keeps old_v in LDS too while the launch's n_replicas * n_max cells are at most this many
+    // (Grid_computer::stage_v_max: is the launch big enough to hide the L2's latency?)
+    int stage_v_max = 130000;
+
+    Ensemble(int n_replicas, int n_max, int grid_size = 50, float cube_size = 1)
+        : Base{"Grid_solver", n_replicas, n_max, grid_size, cube_size}
+    {
+    }
+
+protected:
     // Five launches: the grid of every replica from d_in, then the forces.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void forces(const Pt* d_in, Pt* d_rhs, const bool has_gen)
     {
         const int n_max = this->n_max, n_replicas = this->n_replicas;
         const int* d_n = this->d_n;
-        const int row_blocks = (n_max + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
-        ya::ens::grid_count_batched<Pt><<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(
-            n_max, row_blocks, d_n, d_in, cube_size, grid_size, n_cubes, d_cube_of, d_rank, d_count, d_status);
-        ya::ens::grid_scan_batched<<<n_replicas, ya::UPDATE_BLOCK>>>(n_max, d_n, n_cubes, d_count, d_offs);
-        ya::ens::grid_scatter_batched<<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(
-            n_max, row_blocks, d_n, n_cubes, d_cube_of, d_rank, d_offs, d_arrival, d_cube_id);
-        ya::ens::grid_order_batched<Pt><<<this->grid_of(row_blocks), ya::UPDATE_BLOCK>>>(n_max, row_blocks, d_n, n_cubes,
-            d_arrival, d_cube_id, d_offs, d_in, this->d_old_v, d_point_id, d_sorted, d_sorted_v);
+        this->build(d_in);
+        const int grid_size = this->grid_size, n_cubes = this->n_cubes;
+        const int *d_cube_id = this->d_cube_id, *d_offs = this->d_offs;
+        const ya::Entry<Pt>* d_sorted = this->d_sorted;
+        const float4* d_sorted_v = this->d_sorted_v;
 
-        const float cut2 = ya::cutoff_squared(cube_size);
+        const float cut2 = ya::cutoff_squared(this->cube_size);
         const bool by_plane = sum_order == YA_SUM_BY_PLANE;
         int lanes = lanes_per_cell;
         if (lanes == 0)

@@ -1650,9 +1650,11 @@ __device__ __forceinline__ void rank_list(const int lane, const int lanes, const
 // The test and the sum of a cell whose list is ranked: kept[rank] by the lanes, then the kept pairs' terms
 // in one lane, farthest first (the functors are called for i from that lane alone, in the reference's order:
 // functors that count per cell, `d_n_nbs[i] += 1` of tests/test_solvers.cu:343-352, stay right).
+// i and the sorted entries' ids are rows of d_dX; the functors are handed id_base + id (an ensemble's replica
+// starts at id_base, include/ensemble_gabriel.cuh; a lone system's constant 0 folds away).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Index>
 __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, const int s, const Pt Xi,
-    const int i, const int count, const float gabriel_coefficient, const float* x, const float* y,
+    const int i, const int id_base, const int count, const float gabriel_coefficient, const float* x, const float* y,
     const float* z, const float* d, const int* slot, const Index* rank, const Index* order, Index* kept,
     const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, Pt* __restrict__ d_dX,
     const bool has_gen)
@@ -1678,8 +1680,8 @@ __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, co
         const float dist = d[p];
         const Entry<Pt> other = sorted[slot[p]];
         const Pt r = Xi - other.X;
-        F += pw_int(Xi, r, dist, i, other.id);
-        const float friction = pw_friction(Xi, r, dist, i, other.id);
+        F += pw_int(Xi, r, dist, id_base + i, id_base + other.id);
+        const float friction = pw_friction(Xi, r, dist, id_base + i, id_base + other.id);
         sum_friction += friction;
         // the old_v term only where the friction is not zero: the same bits as the reference's
         // unconditional `sum_v += friction * d_old_v[j]` unless old_v is not finite (0 * inf)
@@ -1694,9 +1696,13 @@ __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, co
 }
 }  // namespace gabriel
 
+// ya::gabriel_force's workgroup over ONE system's arrays: the GABRIEL_CELLS sorted slots from `first_slot`.  The
+// functors are handed the ids id_base + id, and a cell left to the dense kernel is appended as dense_base + its
+// slot (an ensemble's replica starts at row id_base = dense_base of the flat arrays and its cube ids and offs[]
+// are its own, include/ensemble_gabriel.cuh; a lone system's constant 0 folds away).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(64) void gabriel_force(const int n,
-    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+__device__ __forceinline__ void gabriel_force_cells(const int n, const int first_slot, const int id_base,
+    const int dense_base, const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
     const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
     const int n_cubes, const float cube_size, const float gabriel_coefficient,
     Pt* __restrict__ d_dX, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
@@ -1713,7 +1719,7 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
 
     const int cell = threadIdx.x / GABRIEL_LANES;
     const int lane = threadIdx.x % GABRIEL_LANES;
-    const int s = blockIdx.x * GABRIEL_CELLS + cell;
+    const int s = first_slot + cell;
     if (s >= n) return;  // (whole groups leave: everything below is per group)
 
     float* x = sh_list[cell][0];
@@ -1731,7 +1737,7 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
     if (count > CAP) {  // ya::gabriel_force_dense does this cell
         if (lane == 0) {
             const int at = atomicAdd(&n_dense[0], 1);
-            dense[at] = s;
+            dense[at] = dense_base + s;
             atomicMax(&n_dense[1], count);
         }
         return;
@@ -1739,8 +1745,8 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
     coop::wave_sync();
     gabriel::rank_list(lane, GABRIEL_LANES, cell * GABRIEL_LANES, count, d, rank, order);
     if constexpr (!stateless_pair<Pt, pw_int, pw_friction>()) {
-        gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, GABRIEL_LANES, s, Xi, i, count, gabriel_coefficient,
-            x, y, z, d, sh_slot[cell], rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+        gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, GABRIEL_LANES, s, Xi, i, id_base, count,
+            gabriel_coefficient, x, y, z, d, sh_slot[cell], rank, order, kept, sorted, sorted_v, d_dX, has_gen);
         return;
     } else {
         // Functors declared stateless (YA_STATELESS): each lane also evaluates the terms of the pairs it keeps
@@ -1773,8 +1779,8 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
             if (!keep[a]) continue;
             const Entry<Pt> other = sorted[k[a]];
             const Pt r = Xi - other.X;
-            const Pt F = pw_int(Xi, r, dist[a], i, other.id);
-            const float friction = pw_friction(Xi, r, dist[a], i, other.id);
+            const Pt F = pw_int(Xi, r, dist[a], id_base + i, id_base + other.id);
+            const float friction = pw_friction(Xi, r, dist[a], id_base + i, id_base + other.id);
 #pragma unroll
             for (int q = 0; q < NF; q++) sh_list[cell][q][rk[a]] = field(F, q);
             sh_list[cell][NF][rk[a]] = friction;
@@ -1808,17 +1814,26 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
     }
 }
 
-// The cells ya::gabriel_force left (more than GABRIEL_CAP candidates): one wavefront per cell, the same
-// stages on lists in a global workspace of `stride` >= the largest count entries each, per workgroup.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(64) void gabriel_force_dense(const int* __restrict__ dense,
-    const int* __restrict__ n_dense, const Entry<Pt>* __restrict__ sorted,
-    const float4* __restrict__ sorted_v, const int* __restrict__ cube_id, const int* __restrict__ offs,
-    const int gs, const int n_cubes, const float cube_size, const float gabriel_coefficient,
-    Pt* __restrict__ d_dX, const bool has_gen, float* __restrict__ workspace, const long stride)
+__global__ __launch_bounds__(64) void gabriel_force(const int n,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
 {
-    const int lane = threadIdx.x;
-    float* x = workspace + GABRIEL_DENSE_ARRAYS * stride * blockIdx.x;
+    gabriel_force_cells<Pt, pw_int, pw_friction>(n, blockIdx.x * GABRIEL_CELLS, 0, 0, sorted, sorted_v, cube_id, offs,
+        gs, n_cubes, cube_size, gabriel_coefficient, d_dX, has_gen, dense, n_dense);
+}
+
+// One cell ya::gabriel_force left (more than GABRIEL_CAP candidates), by one wavefront: the same stages on
+// lists of `stride` >= the cell's count entries each, in global memory from x on.  s is the cell's sorted slot in
+// ONE system's arrays, the functors are handed id_base + id (gabriel_force_cells' comment).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void gabriel_force_dense_cell(const int lane, const int s, const int id_base,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, const int* __restrict__ cube_id,
+    const int* __restrict__ offs, const int gs, const int n_cubes, const float cube_size,
+    const float gabriel_coefficient, Pt* __restrict__ d_dX, const bool has_gen, float* x, const long stride)
+{
     float* y = x + stride;
     float* z = y + stride;
     float* d = z + stride;
@@ -1826,22 +1841,34 @@ __global__ __launch_bounds__(64) void gabriel_force_dense(const int* __restrict_
     int* rank = slot + stride;
     int* order = rank + stride;
     int* kept = order + stride;
-    for (int t = blockIdx.x; t < n_dense[0]; t += gridDim.x) {
-        const int s = dense[t];
-        const Entry<Pt> self = sorted[s];
-        const Pt Xi = self.X;
-        const int count = gabriel::collect(lane, 64, 0, Xi, cube_id[s], sorted, offs, gs, n_cubes, cube_size,
-            (int)stride, x, y, z, d, slot);
-        __threadfence_block();
-        coop::wave_sync();
-        gabriel::rank_list(lane, 64, 0, count, d, rank, order);
-        __threadfence_block();
-        coop::wave_sync();
-        gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, 64, s, Xi, self.id, count, gabriel_coefficient, x, y,
-            z, d, slot, rank, order, kept, sorted, sorted_v, d_dX, has_gen);
-        __threadfence_block();
-        coop::wave_sync();  // the next cell reuses the workspace
-    }
+    const Entry<Pt> self = sorted[s];
+    const Pt Xi = self.X;
+    const int count = gabriel::collect(lane, 64, 0, Xi, cube_id[s], sorted, offs, gs, n_cubes, cube_size,
+        (int)stride, x, y, z, d, slot);
+    __threadfence_block();
+    coop::wave_sync();
+    gabriel::rank_list(lane, 64, 0, count, d, rank, order);
+    __threadfence_block();
+    coop::wave_sync();
+    gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, 64, s, Xi, self.id, id_base, count, gabriel_coefficient, x,
+        y, z, d, slot, rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+    __threadfence_block();
+    coop::wave_sync();  // the next cell reuses the workspace
+}
+
+// The cells ya::gabriel_force left: one wavefront per cell, lists in a global workspace of `stride` >= the
+// largest count entries each, per workgroup.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(64) void gabriel_force_dense(const int* __restrict__ dense,
+    const int* __restrict__ n_dense, const Entry<Pt>* __restrict__ sorted,
+    const float4* __restrict__ sorted_v, const int* __restrict__ cube_id, const int* __restrict__ offs,
+    const int gs, const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen, float* __restrict__ workspace, const long stride)
+{
+    float* x = workspace + GABRIEL_DENSE_ARRAYS * stride * blockIdx.x;
+    for (int t = blockIdx.x; t < n_dense[0]; t += gridDim.x)
+        gabriel_force_dense_cell<Pt, pw_int, pw_friction>(threadIdx.x, dense[t], 0, sorted, sorted_v, cube_id, offs, gs,
+            n_cubes, cube_size, gabriel_coefficient, d_dX, has_gen, x, stride);
 }
 
 // fix = what is subtracted from dX.xyz: 0 = mean (already in d_mean), 1 = the

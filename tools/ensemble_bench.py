@@ -5,6 +5,7 @@
     python tools/ensemble_bench.py --trace-shape 64 800 --steps 50     # what a rocprofv3 run wraps
     python tools/ensemble_bench.py --solver grid [--out profiles/ensemble_grid_bench.json]
     python tools/ensemble_bench.py --solver grid --trace-shape 64 2000 --steps 50
+    python tools/ensemble_bench.py --solver gabriel [--out profiles/ensemble_gabriel_bench.json]
     python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
@@ -23,6 +24,12 @@ grid_size) with lanes 0 (ya::ens::grid_lanes_for), 1, 4, 8, 16; M in {1, 8, 64, 
 5 * 10^4} with M * n <= 5 * 10^6; grid_size fitted to the ball (the ensemble scans M * grid_size^3 counters per
 stage).  The row's spread is that of the worse side.
 
+--solver gabriel: the same protocol for Gabriel_solver systems -- Solution("relu_gabriel", n, grid_size) round-robin
+(each stage of each step waits for the dense-cell count, 2 M blocking reads per step) against one
+GabrielEnsemble("relu", M, n, grid_size) (16 launches and 2 memsets per step, nothing read by the host; there is no
+lanes setting, so the one column is lanes 0); M in {1, 8, 64, 512} x n in {100, 500, 2000, 10^4} with
+M * n <= 5 * 10^6; grid_size fitted to the ball.
+
 --whole-steps: ONE Ensemble("relu", M, n) per shape, the same protocol, three settings alternating: the six-launch
 step (whole_steps -1, the baseline), whole-step launches of one step each (whole_steps 1, steps_per_launch 1: no
 launches between the stages) and of up to 256 steps each (steps_per_launch at its default: none between the steps
@@ -40,7 +47,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from yalla_amd.ensemble import Ensemble, GridEnsemble  # noqa: E402
+from yalla_amd.ensemble import Ensemble, GabrielEnsemble, GridEnsemble  # noqa: E402
 from yalla_amd.solution import Solution  # noqa: E402
 
 SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
@@ -49,8 +56,11 @@ GRID_SHAPES = [(m, n) for n in (500, 2000, 10000, 50000) for m in (1, 8, 64, 512
 GRID_LANES = (0, 1, 4, 8, 16)
 WHOLE_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
 WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), "whole_256_steps_per_launch": (1, 256)}
+GABRIEL_SHAPES = [(m, n) for n in (100, 500, 2000, 10000) for m in (1, 8, 64, 512) if m * n <= 5000000]
+GABRIEL_LANES = (0,)  # (no lanes setting: one column)
 DT = 0.01
 GRID = False  # --solver grid
+GABRIEL = False  # --solver gabriel
 
 
 def grid_size_for(n):
@@ -69,7 +79,8 @@ def ball(n, seed):
 
 class Singles:
     def __init__(self, m, n):
-        self.sims = [Solution("relu_grid", n, grid_size_for(n), 1.0) if GRID else Solution("relu_tile", n)
+        self.sims = [Solution("relu_gabriel", n, grid_size_for(n), 1.0) if GABRIEL
+                     else Solution("relu_grid", n, grid_size_for(n), 1.0) if GRID else Solution("relu_tile", n)
                      for _ in range(m)]
         for r, s in enumerate(self.sims):
             s.h_X[:] = ball(n, r)
@@ -88,12 +99,15 @@ class Singles:
 
 class Together:
     def __init__(self, m, n):
-        self.ens = GridEnsemble("relu", m, n, grid_size_for(n), 1.0) if GRID else Ensemble("relu", m, n)
+        self.ens = (GabrielEnsemble("relu", m, n, grid_size_for(n), 1.0) if GABRIEL
+                    else GridEnsemble("relu", m, n, grid_size_for(n), 1.0) if GRID else Ensemble("relu", m, n))
         for r in range(m):
             self.ens.h_X[r] = ball(n, r)
         self.ens.copy_to_device()
 
     def lanes(self, lanes):
+        if GABRIEL:
+            return
         self.ens.set_param("lanes" if GRID else "tile_lanes", lanes)
 
     def whole(self, whole_steps, steps_per_launch):
@@ -150,7 +164,7 @@ def measure(m, n, window, repeats):
         a.close()
         b.close()
     row = {"n_replicas": m, "n": n, "singles": summary(samples["A"], m * n, ks["A"])}
-    if GRID:
+    if GRID or GABRIEL:
         row["grid_size"] = grid_size_for(n)
     for lanes in LANES:
         row[f"ensemble_lanes_{lanes}"] = summary(samples[lanes], m * n, ks[lanes])
@@ -221,7 +235,7 @@ def main():
     ap.add_argument("--trace-shape", type=int, nargs=2, metavar=("M", "N"), default=None,
                     help="only step one Ensemble of this shape --steps times (for a kernel trace)")
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--solver", choices=("tile", "grid"), default="tile")
+    ap.add_argument("--solver", choices=("tile", "grid", "gabriel"), default="tile")
     ap.add_argument("--whole-steps", action="store_true",
                     help="whole-step launches against the six-launch step of the same Ensemble (tile solver only)")
     args = ap.parse_args()
@@ -230,9 +244,11 @@ def main():
             ap.error("--whole-steps measures the all-pairs ensemble, and takes no --trace-shape")
         main_whole(args)
         return
-    global GRID, LANES, SHAPES
+    global GRID, GABRIEL, LANES, SHAPES
     if args.solver == "grid":
         GRID, LANES, SHAPES = True, GRID_LANES, GRID_SHAPES
+    if args.solver == "gabriel":
+        GABRIEL, LANES, SHAPES = True, GABRIEL_LANES, GABRIEL_SHAPES
 
     if args.trace_shape:
         b = Together(*args.trace_shape)

@@ -15,6 +15,7 @@ DEVICE_LIB_FAST = os.path.join(_HERE, "libyalla_models_fast.so")  # the fast-ari
 CORE_LIB = os.path.join(_HERE, "libyalla_hip.so")
 ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ensemble.h
 GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid.so")  # include/yalla_ensemble_grid.h
+GABRIEL_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel.so")  # include/yalla_ensemble_gabriel.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -114,6 +115,13 @@ GRID_ENSEMBLE_ABI = {
     "ya_gens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
 }
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_gabriel.h one to one: the grid ensemble's functions
+# under another prefix, create with the coefficient, and dense_cells.
+GABRIEL_ENSEMBLE_ABI = {name.replace("ya_gens_", "ya_gabens_"): sig for name, sig in GRID_ENSEMBLE_ABI.items()}
+GABRIEL_ENSEMBLE_ABI["ya_gabens_create"] = (
+    C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(_ens)])
+GABRIEL_ENSEMBLE_ABI["ya_gabens_dense_cells"] = (C.c_int, [_ens])
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -200,3 +208,22 @@ def grid_ensemble_lib():
             fn.argtypes = args
         _grid_ensemble.append(lib)
     return _grid_ensemble[0]
+
+
+_gabriel_ensemble = []
+
+
+def gabriel_ensemble_lib():
+    """The Gabriel ensemble harness, yalla_amd/libyalla_ensemble_gabriel.so (include/yalla_ensemble_gabriel.h),
+    every entry point typed.  Raises if it has not been built: there is no fallback."""
+    if not _gabriel_ensemble:
+        if not os.path.exists(GABRIEL_ENSEMBLE_LIB):
+            raise FileNotFoundError(
+                f"{GABRIEL_ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
+        lib = C.CDLL(GABRIEL_ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
+        for name, (res, args) in GABRIEL_ENSEMBLE_ABI.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
+        _gabriel_ensemble.append(lib)
+    return _gabriel_ensemble[0]

@@ -20,7 +20,7 @@ wherever the model has no generic forces and n_max is at most 1024; 0 leaves the
 harness's default) never does.  The bits are the same either way; `whole_step_launches` counts the launches made.
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
-build per stage always.
+build per stage always; `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh).
 """
 import ctypes as C
 
@@ -224,6 +224,43 @@ class GridEnsemble(Ensemble):
         return a, b, c, d
 
 
+class GabrielEnsemble(GridEnsemble):
+    """Host-side mirror of `Ensemble<Pt, Gabriel_solver>` (include/ensemble_gabriel.cuh) over
+    include/yalla_ensemble_gabriel.h: M independent Gabriel_solver systems of one model, every replica bit for bit
+    what a `Solution("<model>_gabriel", n_max, grid_size, cube_size)` with the same gabriel_coefficient, given the
+    same rows, holds.  Everything `GridEnsemble` offers but its set_param knobs (the only parameter is
+    "gabriel_coefficient"), and: a `gabriel_coefficient` setter (of every replica, from the next step on) and
+    `dense_cells()`, the cells the last force stage left to the dense kernel (more than 64 candidates).
+    """
+    _PREFIX = "ya_gabens_"
+
+    def __init__(self, model, n_replicas, n_max, grid_size=50, cube_size=1.0, gabriel_coefficient=0.8, lib=None):
+        self.lib = lib if lib is not None else _ffi.gabriel_ensemble_lib()
+        handle = C.c_void_p()
+        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), int(grid_size), float(cube_size),
+                                 float(gabriel_coefficient), C.byref(handle))
+        if code == -1:
+            raise YallaError(f"unknown Gabriel ensemble model {model!r}; known: {gabriel_models(self.lib)}")
+        _check(code, "ya_gabens_create")
+        self.grid_size = int(grid_size)
+        self._attach(model, handle, n_replicas, n_max)
+
+    @property
+    def gabriel_coefficient(self):
+        raise AttributeError("gabriel_coefficient is write-only here")
+
+    @gabriel_coefficient.setter
+    def gabriel_coefficient(self, value):
+        _check(self._f("set_param")(self._h, b"gabriel_coefficient", float(value)), "set gabriel_coefficient")
+
+    def dense_cells(self):
+        """Blocking read: how many cells, over all replicas, the last force stage left to the dense kernel."""
+        n = self._f("dense_cells")(self._h)
+        if n < 0:
+            raise YallaError(f"dense_cells() failed with harness code {n}")
+        return n
+
+
 def models(lib=None):
     lib = lib if lib is not None else _ffi.ensemble_lib()
     return [lib.ya_ens_models_name(i).decode() for i in range(lib.ya_ens_models_count())]
@@ -232,3 +269,8 @@ def models(lib=None):
 def grid_models(lib=None):
     lib = lib if lib is not None else _ffi.grid_ensemble_lib()
     return [lib.ya_gens_models_name(i).decode() for i in range(lib.ya_gens_models_count())]
+
+
+def gabriel_models(lib=None):
+    lib = lib if lib is not None else _ffi.gabriel_ensemble_lib()
+    return [lib.ya_gabens_models_name(i).decode() for i in range(lib.ya_gabens_models_count())]
