@@ -6,6 +6,7 @@ yalla_amd/libyalla_models.so (which pulls in libyalla_hip.so through its
 $ORIGIN rpath) and raises if it is missing: the product has no CPU fallback.
 """
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,29 +92,13 @@ ENSEMBLE_ABI = {
     "ya_ens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
 }
 
-# name -> (restype, argtypes); mirrors include/yalla_ensemble_grid.h one to one.
-GRID_ENSEMBLE_ABI = {
-    "ya_gens_models_count": (C.c_int, []),
-    "ya_gens_models_name": (C.c_char_p, [C.c_int]),
-    "ya_gens_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_ens)]),
-    "ya_gens_destroy": (None, [_ens]),
-    "ya_gens_n_floats": (C.c_int, [_ens]),
-    "ya_gens_h_X": (_pf, [_ens]),
-    "ya_gens_set_h_n": (C.c_int, [_ens, C.c_int, C.c_int]),
-    "ya_gens_get_h_n": (C.c_int, [_ens, C.c_int]),
-    "ya_gens_get_d_n": (C.c_int, [_ens, C.c_int]),
-    "ya_gens_copy_to_device": (C.c_int, [_ens]),
-    "ya_gens_copy_to_host": (C.c_int, [_ens]),
-    "ya_gens_take_steps": (C.c_int, [_ens, C.c_float, C.c_int]),
-    "ya_gens_synchronize": (C.c_int, [_ens]),
-    "ya_gens_set_fixed": (C.c_int, [_ens, C.c_int, C.c_int]),
-    "ya_gens_set_cube_size": (C.c_int, [_ens, C.c_float]),
-    "ya_gens_get_old_v": (C.c_int, [_ens, _pf]),
-    "ya_gens_set_old_v": (C.c_int, [_ens, _pf]),
-    "ya_gens_status": (C.c_int, [_ens, C.c_int, C.c_int]),
-    "ya_gens_get_grid": (C.c_int, [_ens, C.c_int, _pi, _pi, _pi, _pi]),
-    "ya_gens_set_param": (C.c_int, [_ens, C.c_char_p, C.c_double]),
-}
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_grid.h one to one: the ensemble's functions under
+# another prefix, create with the grid's size and cube size, set_cube_size, status and get_grid.
+GRID_ENSEMBLE_ABI = {name.replace("ya_ens_", "ya_gens_"): sig for name, sig in ENSEMBLE_ABI.items()}
+GRID_ENSEMBLE_ABI["ya_gens_create"] = (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_ens)])
+GRID_ENSEMBLE_ABI["ya_gens_set_cube_size"] = (C.c_int, [_ens, C.c_float])
+GRID_ENSEMBLE_ABI["ya_gens_status"] = (C.c_int, [_ens, C.c_int, C.c_int])
+GRID_ENSEMBLE_ABI["ya_gens_get_grid"] = (C.c_int, [_ens, C.c_int, _pi, _pi, _pi, _pi])
 
 # name -> (restype, argtypes); mirrors include/yalla_ensemble_gabriel.h one to one: the grid ensemble's functions
 # under another prefix, create with the coefficient, and dense_cells.
@@ -141,17 +126,22 @@ CORE_ABI = [
 ]
 
 
-def bind(path):
-    """Load `path` and type every include/yalla_models.h entry point."""
+def _load(path, table):
+    """Load `path` and type every entry point of `table`."""
     if not os.path.exists(path):
         raise FileNotFoundError(
             f"{path} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
     lib = C.CDLL(path, mode=C.RTLD_LOCAL)
-    for name, (res, args) in MODELS_ABI.items():
+    for name, (res, args) in table.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
     return lib
+
+
+def bind(path):
+    """Load `path` and type every include/yalla_models.h entry point."""
+    return _load(path, MODELS_ABI)
 
 
 _device = {}
@@ -172,58 +162,22 @@ def device_lib(arith="exact"):
     return _device[arith]
 
 
-_ensemble = []
-
-
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
 def ensemble_lib():
     """The ensemble harness, yalla_amd/libyalla_ensemble.so (include/yalla_ensemble.h), every entry
     point typed.  Raises if it has not been built: there is no fallback."""
-    if not _ensemble:
-        if not os.path.exists(ENSEMBLE_LIB):
-            raise FileNotFoundError(
-                f"{ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        lib = C.CDLL(ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
-        for name, (res, args) in ENSEMBLE_ABI.items():
-            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
-        _ensemble.append(lib)
-    return _ensemble[0]
+    return _load(ENSEMBLE_LIB, ENSEMBLE_ABI)
 
 
-_grid_ensemble = []
-
-
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
 def grid_ensemble_lib():
     """The grid ensemble harness, yalla_amd/libyalla_ensemble_grid.so (include/yalla_ensemble_grid.h), every
     entry point typed.  Raises if it has not been built: there is no fallback."""
-    if not _grid_ensemble:
-        if not os.path.exists(GRID_ENSEMBLE_LIB):
-            raise FileNotFoundError(
-                f"{GRID_ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        lib = C.CDLL(GRID_ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
-        for name, (res, args) in GRID_ENSEMBLE_ABI.items():
-            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
-        _grid_ensemble.append(lib)
-    return _grid_ensemble[0]
+    return _load(GRID_ENSEMBLE_LIB, GRID_ENSEMBLE_ABI)
 
 
-_gabriel_ensemble = []
-
-
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
 def gabriel_ensemble_lib():
     """The Gabriel ensemble harness, yalla_amd/libyalla_ensemble_gabriel.so (include/yalla_ensemble_gabriel.h),
     every entry point typed.  Raises if it has not been built: there is no fallback."""
-    if not _gabriel_ensemble:
-        if not os.path.exists(GABRIEL_ENSEMBLE_LIB):
-            raise FileNotFoundError(
-                f"{GABRIEL_ENSEMBLE_LIB} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()')")
-        lib = C.CDLL(GABRIEL_ENSEMBLE_LIB, mode=C.RTLD_LOCAL)
-        for name, (res, args) in GABRIEL_ENSEMBLE_ABI.items():
-            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
-        _gabriel_ensemble.append(lib)
-    return _gabriel_ensemble[0]
+    return _load(GABRIEL_ENSEMBLE_LIB, GABRIEL_ENSEMBLE_ABI)

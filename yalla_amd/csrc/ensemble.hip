@@ -17,23 +17,13 @@
 #include "model_functors.h"
 
 #include "yalla_ensemble.h"
-#include "ensemble_harness.h"  // No_gen, Push_gen
+#include "ensemble_harness.h"  // No_gen, Push_gen, Replicas, Replicas_of, Model, the entry points' bodies
 
 namespace ens_harness {
 
-struct Base {
-    virtual ~Base() {}
-    virtual int n_floats() = 0;
-    virtual int n_replicas() = 0;
-    virtual int n_max() = 0;
-    virtual float* h_X() = 0;
-    virtual int* h_n() = 0;
-    virtual void copy_to_device() = 0;
-    virtual void copy_to_host() = 0;
-    virtual int get_d_n(int r) = 0;
+// What the all-pairs form adds to the shared interface.
+struct Base : public Replicas {
     virtual long take_steps(float dt, int n_steps) = 0;  // returns the whole-step launches it made
-    virtual void set_fixed(int mode, int point) = 0;
-    virtual float3* d_old_v() = 0;
     virtual void set_lanes(int lanes) = 0;
     virtual void set_whole_steps(int mode) = 0;
     virtual void set_steps_per_launch(int steps) = 0;
@@ -57,19 +47,11 @@ struct Oscillator_ids : public No_gen<float4> {
     }
 };
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
-struct Sim : public Base {
-    Ensemble<Pt> cells;
+struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
+    using Replicas_of<Ensemble<Pt>, Base>::cells;
     // The harness's own default is the six-launch step (whole_steps = -1): what its callers ran before the
     // whole-step launches existed; set_param("whole_steps", 0 | 1) opts in.
-    Sim(int n_replicas, int n_max) : cells{n_replicas, n_max} { cells.whole_steps = -1; }
-    int n_floats() override { return sizeof(Pt) / sizeof(float); }
-    int n_replicas() override { return cells.n_replicas; }
-    int n_max() override { return cells.n_max; }
-    float* h_X() override { return reinterpret_cast<float*>(cells.h_X); }
-    int* h_n() override { return cells.h_n; }
-    void copy_to_device() override { cells.copy_to_device(); }
-    void copy_to_host() override { cells.copy_to_host(); }
-    int get_d_n(int r) override { return cells.get_d_n(r); }
+    Sim(int n_replicas, int n_max) : Replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max} { cells.whole_steps = -1; }
     long take_steps(float dt, int n_steps) override
     {
         const long launches_before = cells.whole_step_launches;
@@ -78,39 +60,19 @@ struct Sim : public Base {
         cells.template take_steps<pw_int, pw_friction>(dt, n_steps, gen);  // (push's generic force: never whole steps)
         return cells.whole_step_launches - launches_before;
     }
-    void set_fixed(int mode, int point) override
-    {
-        if (mode == 0) cells.set_fixed();
-        if (mode == 1) cells.set_fixed(point);
-        if (mode == 2) cells.set_fixed_xy(point);
-    }
-    float3* d_old_v() override { return cells.d_old_v; }
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
     void set_whole_steps(int mode) override { cells.whole_steps = mode; }
     void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
 };
 
-using Factory = Base* (*)(int, int);
-struct Model {
-    const char* name;
-    Factory make;
-};
-template<typename S>
-Base* make_sim(int n_replicas, int n_max)
-{
-    return new S{n_replicas, n_max};
-}
-#define YA_ENS_MODEL(name, Pt, pw_int, pw_friction, Policy) \
-    Model { name, &make_sim<Sim<Pt, pw_int, pw_friction, Policy>> }
-
-static const Model model_table[] = {
-    YA_ENS_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENS_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENS_MODEL("fading", float3, models::fading_spring, friction_on_background<float3>, No_gen<float3>),
-    YA_ENS_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENS_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
-    YA_ENS_MODEL("oscillator", float4, oscillator_by_local_id, friction_w_neighbour<float4>, Oscillator_ids),
-    YA_ENS_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
+static const Model<Base* (*)(int, int)> model_table[] = {
+    YA_ENSEMBLE_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("fading", float3, models::fading_spring, friction_on_background<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
+    YA_ENSEMBLE_MODEL("oscillator", float4, oscillator_by_local_id, friction_w_neighbour<float4>, Oscillator_ids),
+    YA_ENSEMBLE_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
@@ -125,7 +87,7 @@ extern "C" {
 int ya_ens_models_count(void) { return ens_harness::n_models; }
 const char* ya_ens_models_name(int i)
 {
-    return (i >= 0 && i < ens_harness::n_models) ? ens_harness::model_table[i].name : nullptr;
+    return ens_harness::name_at(ens_harness::model_table, ens_harness::n_models, i);
 }
 
 int ya_ens_create(const char* model, int n_replicas, int n_max, ya_ens** out)
@@ -134,77 +96,23 @@ int ya_ens_create(const char* model, int n_replicas, int n_max, ya_ens** out)
     // ids and launch sizes are ints (include/ensemble.cuh)
     if ((size_t)n_replicas * (size_t)n_max > (size_t)0x7fffffff) return -3;
     if ((size_t)n_replicas * (size_t)((n_max + 3) / 4) > (size_t)0x7fffffff) return -3;
-    for (int i = 0; i < ens_harness::n_models; i++) {
-        if (std::string(model) == ens_harness::model_table[i].name) {
-            ya_ens* e = new ya_ens;
-            e->p.reset(ens_harness::model_table[i].make(n_replicas, n_max));
-            *out = e;
-            return 0;
-        }
-    }
-    return -1;
+    return ens_harness::create(ens_harness::model_table, ens_harness::n_models, model, out, n_replicas, n_max);
 }
 void ya_ens_destroy(ya_ens* ens) { delete ens; }
 
 int ya_ens_n_floats(ya_ens* e) { return e->p->n_floats(); }
 float* ya_ens_h_X(ya_ens* e) { return e->p->h_X(); }
-int ya_ens_set_h_n(ya_ens* e, int r, int n)
-{
-    if (r < 0 || r >= e->p->n_replicas() || n < 0 || n > e->p->n_max()) return -3;
-    e->p->h_n()[r] = n;
-    return 0;
-}
-int ya_ens_get_h_n(ya_ens* e, int r)
-{
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    return e->p->h_n()[r];
-}
-int ya_ens_get_d_n(ya_ens* e, int r)
-{
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    return e->p->get_d_n(r);
-}
-int ya_ens_copy_to_device(ya_ens* e)
-{
-    e->p->copy_to_device();
-    return 0;
-}
-int ya_ens_copy_to_host(ya_ens* e)
-{
-    e->p->copy_to_host();
-    return 0;
-}
-int ya_ens_take_steps(ya_ens* e, float dt, int n_steps)
-{
-    // (at most n_steps launches; 0 with the harness's default of whole_steps = -1)
-    return (int)e->p->take_steps(dt, n_steps);
-}
-int ya_ens_synchronize(ya_ens*)
-{
-    YA_CHECK(ya_device_synchronize());
-    return 0;
-}
-int ya_ens_set_fixed(ya_ens* e, int mode, int local_point)
-{
-    if (mode < 0 || mode > 2) return -3;
-    if (mode != 0 && (local_point < 0 || local_point >= e->p->n_max())) return -3;
-    e->p->set_fixed(mode, local_point);
-    return 0;
-}
-int ya_ens_get_old_v(ya_ens* e, float* out)
-{
-    if (!out) return -3;
-    YA_CHECK(ya_device_synchronize());
-    YA_CHECK(ya_memcpy_d2h(out, e->p->d_old_v(), (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
-    return 0;
-}
-int ya_ens_set_old_v(ya_ens* e, const float* in)
-{
-    if (!in) return -3;
-    YA_CHECK(ya_device_synchronize());
-    YA_CHECK(ya_memcpy_h2d(e->p->d_old_v(), in, (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
-    return 0;
-}
+int ya_ens_set_h_n(ya_ens* e, int r, int n) { return ens_harness::set_h_n(*e->p, r, n); }
+int ya_ens_get_h_n(ya_ens* e, int r) { return ens_harness::get_h_n(*e->p, r); }
+int ya_ens_get_d_n(ya_ens* e, int r) { return ens_harness::get_d_n(*e->p, r); }
+int ya_ens_copy_to_device(ya_ens* e) { return ens_harness::copy_to_device(*e->p); }
+int ya_ens_copy_to_host(ya_ens* e) { return ens_harness::copy_to_host(*e->p); }
+// (at most n_steps launches; 0 with the harness's default of whole_steps = -1)
+int ya_ens_take_steps(ya_ens* e, float dt, int n_steps) { return (int)e->p->take_steps(dt, n_steps); }
+int ya_ens_synchronize(ya_ens*) { return ens_harness::synchronize(); }
+int ya_ens_set_fixed(ya_ens* e, int mode, int local_point) { return ens_harness::set_fixed(*e->p, mode, local_point); }
+int ya_ens_get_old_v(ya_ens* e, float* out) { return ens_harness::get_old_v(*e->p, out); }
+int ya_ens_set_old_v(ya_ens* e, const float* in) { return ens_harness::set_old_v(*e->p, in); }
 int ya_ens_set_param(ya_ens* e, const char* name, double v)
 {
     if (!name) return -3;

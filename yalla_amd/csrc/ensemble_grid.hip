@@ -6,7 +6,6 @@
 
 #include <memory>
 #include <string>
-#include <vector>
 
 #include "dtypes.cuh"
 #include "inits.cuh"
@@ -18,92 +17,43 @@
 #include "model_functors.h"
 
 #include "yalla_ensemble_grid.h"
-#include "ensemble_harness.h"  // No_gen, Push_gen
+#include "ensemble_harness.h"  // No_gen, Push_gen, Grid_replicas, Grid_replicas_of, Model, the entry points' bodies
 
 namespace gens_harness {
 using ens_harness::No_gen;
 using ens_harness::Push_gen;
+using ens_harness::Grid_replicas;
+using ens_harness::Grid_replicas_of;
+using ens_harness::Model;
 
-struct Base {
-    virtual ~Base() {}
-    virtual int n_floats() = 0;
-    virtual int n_replicas() = 0;
-    virtual int n_max() = 0;
-    virtual int n_cubes() = 0;
-    virtual float* h_X() = 0;
-    virtual int* h_n() = 0;
-    virtual void copy_to_device() = 0;
-    virtual void copy_to_host() = 0;
-    virtual int get_d_n(int r) = 0;
+// What the grid form adds to the shared interface.
+struct Base : public Grid_replicas {
     virtual void take_steps(float dt, int n_steps) = 0;
-    virtual void set_fixed(int mode, int point) = 0;
-    virtual void set_cube_size(float cube_size) = 0;
-    virtual float3* d_old_v() = 0;
     virtual void set_lanes(int lanes) = 0;
     virtual void set_sum_order(int order) = 0;
-    virtual int status(int r, bool clear) = 0;
-    virtual const int* d_cube_id() = 0;
-    virtual const int* d_point_id() = 0;
-    virtual const int* d_offs() = 0;
 };
 
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
-struct Sim : public Base {
-    Ensemble<Pt, Grid_solver> cells;
-    Sim(int n_replicas, int n_max, int grid_size, float cube_size) : cells{n_replicas, n_max, grid_size, cube_size} {}
-    int n_floats() override { return sizeof(Pt) / sizeof(float); }
-    int n_replicas() override { return cells.n_replicas; }
-    int n_max() override { return cells.n_max; }
-    int n_cubes() override { return cells.n_cubes; }
-    float* h_X() override { return reinterpret_cast<float*>(cells.h_X); }
-    int* h_n() override { return cells.h_n; }
-    void copy_to_device() override { cells.copy_to_device(); }
-    void copy_to_host() override { cells.copy_to_host(); }
-    int get_d_n(int r) override { return cells.get_d_n(r); }
+struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
+    using Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>::Grid_replicas_of;
+    using Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>::cells;
     void take_steps(float dt, int n_steps) override
     {
-        Policy::before_steps(cells.n_max);
-        Generic_forces<Pt> gen = Policy::gen(cells.n_replicas, cells.n_max);
-        for (int s = 0; s < n_steps; s++) cells.template take_step<pw_int, pw_friction>(dt, gen);
+        ens_harness::step_by_step<Pt, pw_int, pw_friction, Policy>(cells, dt, n_steps);
     }
-    void set_fixed(int mode, int point) override
-    {
-        if (mode == 0) cells.set_fixed();
-        if (mode == 1) cells.set_fixed(point);
-        if (mode == 2) cells.set_fixed_xy(point);
-    }
-    void set_cube_size(float cube_size) override { cells.cube_size = cube_size; }
-    float3* d_old_v() override { return cells.d_old_v; }
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
     void set_sum_order(int order) override { cells.sum_order = order ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE; }
-    int status(int r, bool clear) override { return cells.status(r, clear); }
-    const int* d_cube_id() override { return cells.d_cube_id; }
-    const int* d_point_id() override { return cells.d_point_id; }
-    const int* d_offs() override { return cells.d_offs; }
 };
 
-using Factory = Base* (*)(int, int, int, float);
-struct Model {
-    const char* name;
-    Factory make;
-};
-template<typename S>
-Base* make_sim(int n_replicas, int n_max, int grid_size, float cube_size)
-{
-    return new S{n_replicas, n_max, grid_size, cube_size};
-}
-#define YA_GENS_MODEL(name, Pt, pw_int, pw_friction, Policy) \
-    Model { name, &make_sim<Sim<Pt, pw_int, pw_friction, Policy>> }
-
-static const Model model_table[] = {
-    YA_GENS_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_GENS_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_GENS_MODEL("fading", float3, models::fading_spring, friction_on_background<float3>, No_gen<float3>),
-    YA_GENS_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_GENS_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
-    YA_GENS_MODEL("relu_cell", Cell, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
-    YA_GENS_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
-    YA_GENS_MODEL("clipped_push", float3, models::clipped_spring, friction_w_neighbour<float3>, Push_gen<float3>),
+static const Model<Base* (*)(int, int, int, float)> model_table[] = {
+    YA_ENSEMBLE_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("fading", float3, models::fading_spring, friction_on_background<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
+    YA_ENSEMBLE_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
+    YA_ENSEMBLE_MODEL("relu_cell", Cell, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
+    YA_ENSEMBLE_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
+    YA_ENSEMBLE_MODEL("clipped_push", float3, models::clipped_spring, friction_w_neighbour<float3>, Push_gen<float3>),
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
@@ -118,7 +68,7 @@ extern "C" {
 int ya_gens_models_count(void) { return gens_harness::n_models; }
 const char* ya_gens_models_name(int i)
 {
-    return (i >= 0 && i < gens_harness::n_models) ? gens_harness::model_table[i].name : nullptr;
+    return ens_harness::name_at(gens_harness::model_table, gens_harness::n_models, i);
 }
 
 int ya_gens_create(const char* model, int n_replicas, int n_max, int grid_size, float cube_size, ya_gens** out)
@@ -126,108 +76,31 @@ int ya_gens_create(const char* model, int n_replicas, int n_max, int grid_size, 
     if (!model || !out) return -3;
     // what the class refuses (include/ensemble_grid.cuh; the limits do not depend on the point type)
     if (!Ensemble<float3, Grid_solver>::sizes_ok(n_replicas, n_max, grid_size) || !(cube_size > 0)) return -3;
-    for (int i = 0; i < gens_harness::n_models; i++) {
-        if (std::string(model) == gens_harness::model_table[i].name) {
-            ya_gens* e = new ya_gens;
-            e->p.reset(gens_harness::model_table[i].make(n_replicas, n_max, grid_size, cube_size));
-            *out = e;
-            return 0;
-        }
-    }
-    return -1;
+    return ens_harness::create(gens_harness::model_table, gens_harness::n_models, model, out,
+        n_replicas, n_max, grid_size, cube_size);
 }
 void ya_gens_destroy(ya_gens* ens) { delete ens; }
 
 int ya_gens_n_floats(ya_gens* e) { return e->p->n_floats(); }
 float* ya_gens_h_X(ya_gens* e) { return e->p->h_X(); }
-int ya_gens_set_h_n(ya_gens* e, int r, int n)
-{
-    if (r < 0 || r >= e->p->n_replicas() || n < 0 || n > e->p->n_max()) return -3;
-    e->p->h_n()[r] = n;
-    return 0;
-}
-int ya_gens_get_h_n(ya_gens* e, int r)
-{
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    return e->p->h_n()[r];
-}
-int ya_gens_get_d_n(ya_gens* e, int r)
-{
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    return e->p->get_d_n(r);
-}
-int ya_gens_copy_to_device(ya_gens* e)
-{
-    e->p->copy_to_device();
-    return 0;
-}
-int ya_gens_copy_to_host(ya_gens* e)
-{
-    e->p->copy_to_host();
-    return 0;
-}
-int ya_gens_take_steps(ya_gens* e, float dt, int n_steps)
-{
-    e->p->take_steps(dt, n_steps);
-    return 0;
-}
-int ya_gens_synchronize(ya_gens*)
-{
-    YA_CHECK(ya_device_synchronize());
-    return 0;
-}
+int ya_gens_set_h_n(ya_gens* e, int r, int n) { return ens_harness::set_h_n(*e->p, r, n); }
+int ya_gens_get_h_n(ya_gens* e, int r) { return ens_harness::get_h_n(*e->p, r); }
+int ya_gens_get_d_n(ya_gens* e, int r) { return ens_harness::get_d_n(*e->p, r); }
+int ya_gens_copy_to_device(ya_gens* e) { return ens_harness::copy_to_device(*e->p); }
+int ya_gens_copy_to_host(ya_gens* e) { return ens_harness::copy_to_host(*e->p); }
+int ya_gens_take_steps(ya_gens* e, float dt, int n_steps) { return ens_harness::take_steps(*e->p, dt, n_steps); }
+int ya_gens_synchronize(ya_gens*) { return ens_harness::synchronize(); }
 int ya_gens_set_fixed(ya_gens* e, int mode, int local_point)
 {
-    if (mode < 0 || mode > 2) return -3;
-    if (mode != 0 && (local_point < 0 || local_point >= e->p->n_max())) return -3;
-    e->p->set_fixed(mode, local_point);
-    return 0;
+    return ens_harness::set_fixed(*e->p, mode, local_point);
 }
-int ya_gens_set_cube_size(ya_gens* e, float cube_size)
-{
-    if (!(cube_size > 0)) return -3;
-    e->p->set_cube_size(cube_size);
-    return 0;
-}
-int ya_gens_get_old_v(ya_gens* e, float* out)
-{
-    if (!out) return -3;
-    YA_CHECK(ya_device_synchronize());
-    YA_CHECK(ya_memcpy_d2h(out, e->p->d_old_v(), (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
-    return 0;
-}
-int ya_gens_set_old_v(ya_gens* e, const float* in)
-{
-    if (!in) return -3;
-    YA_CHECK(ya_device_synchronize());
-    YA_CHECK(ya_memcpy_h2d(e->p->d_old_v(), in, (size_t)e->p->n_replicas() * e->p->n_max() * 3 * sizeof(float)));
-    return 0;
-}
-int ya_gens_status(ya_gens* e, int r, int clear)
-{
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    YA_CHECK(ya_device_synchronize());
-    return e->p->status(r, clear != 0);
-}
+int ya_gens_set_cube_size(ya_gens* e, float cube_size) { return ens_harness::set_cube_size(*e->p, cube_size); }
+int ya_gens_get_old_v(ya_gens* e, float* out) { return ens_harness::get_old_v(*e->p, out); }
+int ya_gens_set_old_v(ya_gens* e, const float* in) { return ens_harness::set_old_v(*e->p, in); }
+int ya_gens_status(ya_gens* e, int r, int clear) { return ens_harness::status(*e->p, r, clear); }
 int ya_gens_get_grid(ya_gens* e, int r, int* cube_id, int* point_id, int* cube_start, int* cube_end)
 {
-    if (r < 0 || r >= e->p->n_replicas()) return -3;
-    const size_t n_max = e->p->n_max(), n_cubes = e->p->n_cubes();
-    YA_CHECK(ya_device_synchronize());
-    if (cube_id) YA_CHECK(ya_memcpy_d2h(cube_id, e->p->d_cube_id() + r * n_max, n_max * sizeof(int)));
-    if (point_id) YA_CHECK(ya_memcpy_d2h(point_id, e->p->d_point_id() + r * n_max, n_max * sizeof(int)));
-    if (cube_start || cube_end) {
-        // Grid's cube_start / cube_end from the replica's offs (not on the step's path)
-        std::vector<int> offs(n_cubes + 1);
-        YA_CHECK(ya_memcpy_d2h(offs.data(), e->p->d_offs() + r * (n_cubes + 1), offs.size() * sizeof(int)));
-        const bool built = offs[n_cubes] >= 0;  // (never built: what a fresh Grid holds)
-        for (size_t c = 0; c < n_cubes; c++) {
-            const bool some = built && offs[c + 1] > offs[c];
-            if (cube_start) cube_start[c] = some ? offs[c] : -1;
-            if (cube_end) cube_end[c] = some ? offs[c + 1] - 1 : (built ? -2 : -1);
-        }
-    }
-    return 0;
+    return ens_harness::get_grid(*e->p, r, cube_id, point_id, cube_start, cube_end);
 }
 int ya_gens_set_param(ya_gens* e, const char* name, double v)
 {

@@ -1,6 +1,11 @@
-// What the two ensemble harnesses (ensemble.hip, ensemble_grid.hip) share: the generic-force policies of their
-// model tables.
+// What the three ensemble harnesses (ensemble.hip, ensemble_grid.hip, ensemble_gabriel.hip) share: the generic-force
+// policies of their model tables, the interfaces their C handles hold, the overrides that forward to an Ensemble,
+// the model table, and the bodies of the C entry points that are the same but for the prefix.  Each .hip writes its
+// own table, what its form adds, create's checks, set_param, and its exported functions as one-line forwards.
 #pragma once
+
+#include <string>
+#include <vector>
 
 namespace ens_harness {
 
@@ -33,5 +38,213 @@ struct Push_gen {
     }
     static void before_steps(int) {}
 };
+
+// THE INTERFACES.  What every form exposes to its C functions, and what the two grid forms add.  take_steps and a
+// form's own setters are declared by the interface each .hip derives from one of these.
+struct Replicas {
+    virtual ~Replicas() {}
+    virtual int n_floats() = 0;
+    virtual int n_replicas() = 0;
+    virtual int n_max() = 0;
+    virtual float* h_X() = 0;
+    virtual int* h_n() = 0;
+    virtual void copy_to_device() = 0;
+    virtual void copy_to_host() = 0;
+    virtual int get_d_n(int r) = 0;
+    virtual void set_fixed(int mode, int point) = 0;
+    virtual float3* d_old_v() = 0;
+};
+struct Grid_replicas : public Replicas {
+    virtual int n_cubes() = 0;
+    virtual void set_cube_size(float cube_size) = 0;
+    virtual int status(int r, bool clear) = 0;
+    virtual const int* d_cube_id() = 0;
+    virtual const int* d_point_id() = 0;
+    virtual const int* d_offs() = 0;
+};
+
+// THE OVERRIDES.  Cells is an Ensemble<Pt, Solver>, Interface what the .hip derived from Replicas or Grid_replicas;
+// the .hip's Sim derives from one of these two and overrides what is left.
+template<typename Cells, typename Interface_>
+struct Replicas_of : public Interface_ {
+    using Interface = Interface_;
+    Cells cells;
+    template<typename... Args>
+    explicit Replicas_of(Args... args) : cells{args...}
+    {
+    }
+    int n_floats() override { return sizeof(*cells.h_X) / sizeof(float); }
+    int n_replicas() override { return cells.n_replicas; }
+    int n_max() override { return cells.n_max; }
+    float* h_X() override { return reinterpret_cast<float*>(cells.h_X); }
+    int* h_n() override { return cells.h_n; }
+    void copy_to_device() override { cells.copy_to_device(); }
+    void copy_to_host() override { cells.copy_to_host(); }
+    int get_d_n(int r) override { return cells.get_d_n(r); }
+    void set_fixed(int mode, int point) override
+    {
+        if (mode == 0) cells.set_fixed();
+        if (mode == 1) cells.set_fixed(point);
+        if (mode == 2) cells.set_fixed_xy(point);
+    }
+    float3* d_old_v() override { return cells.d_old_v; }
+};
+template<typename Cells, typename Interface>
+struct Grid_replicas_of : public Replicas_of<Cells, Interface> {
+    using Replicas_of<Cells, Interface>::Replicas_of;
+    using Replicas_of<Cells, Interface>::cells;
+    int n_cubes() override { return cells.n_cubes; }
+    void set_cube_size(float cube_size) override { cells.cube_size = cube_size; }
+    int status(int r, bool clear) override { return cells.status(r, clear); }
+    const int* d_cube_id() override { return cells.d_cube_id; }
+    const int* d_point_id() override { return cells.d_point_id; }
+    const int* d_offs() override { return cells.d_offs; }
+};
+// The two grid forms' take_steps: one take_step per step, the policy's generic force in each.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy,
+    typename Cells>
+void step_by_step(Cells& cells, float dt, int n_steps)
+{
+    Policy::before_steps(cells.n_max);
+    Generic_forces<Pt> gen = Policy::gen(cells.n_replicas, cells.n_max);
+    for (int s = 0; s < n_steps; s++) cells.template take_step<pw_int, pw_friction>(dt, gen);
+}
+
+// THE MODEL TABLE.  Factory is a pointer to a function that takes create's sizes and values and returns the .hip's
+// interface; make_sim<Sim> is one (its arguments are deduced from the Factory it is stored as).
+template<typename Factory>
+struct Model {
+    const char* name;
+    Factory make;
+};
+template<typename S, typename... Args>
+typename S::Interface* make_sim(Args... args)
+{
+    return new S{args...};
+}
+// (one row of a .hip's table; Sim is that file's)
+#define YA_ENSEMBLE_MODEL(name, Pt, pw_int, pw_friction, Policy) \
+    { name, &ens_harness::make_sim<Sim<Pt, pw_int, pw_friction, Policy>> }
+template<typename Factory>
+const Model<Factory>* find(const Model<Factory>* table, int count, const char* name)
+{
+    for (int i = 0; i < count; i++)
+        if (std::string(name) == table[i].name) return &table[i];
+    return nullptr;
+}
+template<typename Factory>
+const char* name_at(const Model<Factory>* table, int count, int i)
+{
+    return (i >= 0 && i < count) ? table[i].name : nullptr;
+}
+// The end of every create, after its own checks: -1 for a name the table does not hold, else a new handle.
+template<typename Factory, typename Handle, typename... Args>
+int create(const Model<Factory>* table, int count, const char* name, Handle** out, Args... args)
+{
+    const Model<Factory>* model = find(table, count, name);
+    if (!model) return -1;
+    Handle* e = new Handle;
+    e->p.reset(model->make(args...));
+    *out = e;
+    return 0;
+}
+
+// THE ENTRY POINTS' BODIES.  Argument checks first, then ya_device_synchronize, then the copy.
+inline int set_h_n(Replicas& s, int r, int n)
+{
+    if (r < 0 || r >= s.n_replicas() || n < 0 || n > s.n_max()) return -3;
+    s.h_n()[r] = n;
+    return 0;
+}
+inline int get_h_n(Replicas& s, int r)
+{
+    if (r < 0 || r >= s.n_replicas()) return -3;
+    return s.h_n()[r];
+}
+inline int get_d_n(Replicas& s, int r)
+{
+    if (r < 0 || r >= s.n_replicas()) return -3;
+    return s.get_d_n(r);
+}
+inline int copy_to_device(Replicas& s)
+{
+    s.copy_to_device();
+    return 0;
+}
+inline int copy_to_host(Replicas& s)
+{
+    s.copy_to_host();
+    return 0;
+}
+// (the two grid forms'; the all-pairs take_steps returns a count)
+template<typename Interface>
+int take_steps(Interface& s, float dt, int n_steps)
+{
+    s.take_steps(dt, n_steps);
+    return 0;
+}
+inline int synchronize()
+{
+    YA_CHECK(ya_device_synchronize());
+    return 0;
+}
+inline int set_fixed(Replicas& s, int mode, int local_point)
+{
+    if (mode < 0 || mode > 2) return -3;
+    if (mode != 0 && (local_point < 0 || local_point >= s.n_max())) return -3;
+    s.set_fixed(mode, local_point);
+    return 0;
+}
+inline int get_old_v(Replicas& s, float* out)
+{
+    if (!out) return -3;
+    YA_CHECK(ya_device_synchronize());
+    YA_CHECK(ya_memcpy_d2h(out, s.d_old_v(), (size_t)s.n_replicas() * s.n_max() * 3 * sizeof(float)));
+    return 0;
+}
+inline int set_old_v(Replicas& s, const float* in)
+{
+    if (!in) return -3;
+    YA_CHECK(ya_device_synchronize());
+    YA_CHECK(ya_memcpy_h2d(s.d_old_v(), in, (size_t)s.n_replicas() * s.n_max() * 3 * sizeof(float)));
+    return 0;
+}
+inline int set_cube_size(Grid_replicas& s, float cube_size)
+{
+    if (!(cube_size > 0)) return -3;
+    s.set_cube_size(cube_size);
+    return 0;
+}
+inline int status(Grid_replicas& s, int r, int clear)
+{
+    if (r < 0 || r >= s.n_replicas()) return -3;
+    YA_CHECK(ya_device_synchronize());
+    return s.status(r, clear != 0);
+}
+// Grid's cube_start / cube_end from a replica's n_cubes + 1 offs: an empty cube is -1 / -2, and every cube of a grid
+// that was never built (offs[n_cubes] < 0) -1 / -1, which is what a fresh Grid holds.  Host arithmetic only.
+inline void offs_to_start_end(const int* offs, size_t n_cubes, int* cube_start, int* cube_end)
+{
+    const bool built = offs[n_cubes] >= 0;
+    for (size_t c = 0; c < n_cubes; c++) {
+        const bool some = built && offs[c + 1] > offs[c];
+        if (cube_start) cube_start[c] = some ? offs[c] : -1;
+        if (cube_end) cube_end[c] = some ? offs[c + 1] - 1 : (built ? -2 : -1);
+    }
+}
+inline int get_grid(Grid_replicas& s, int r, int* cube_id, int* point_id, int* cube_start, int* cube_end)
+{
+    if (r < 0 || r >= s.n_replicas()) return -3;
+    const size_t n_max = s.n_max(), n_cubes = s.n_cubes();
+    YA_CHECK(ya_device_synchronize());
+    if (cube_id) YA_CHECK(ya_memcpy_d2h(cube_id, s.d_cube_id() + r * n_max, n_max * sizeof(int)));
+    if (point_id) YA_CHECK(ya_memcpy_d2h(point_id, s.d_point_id() + r * n_max, n_max * sizeof(int)));
+    if (cube_start || cube_end) {  // (not on the step's path)
+        std::vector<int> offs(n_cubes + 1);
+        YA_CHECK(ya_memcpy_d2h(offs.data(), s.d_offs() + r * (n_cubes + 1), offs.size() * sizeof(int)));
+        offs_to_start_end(offs.data(), n_cubes, cube_start, cube_end);
+    }
+    return 0;
+}
 
 }  // namespace ens_harness

@@ -69,18 +69,25 @@ class _Counts:
 
 
 class Ensemble:
-    _PREFIX = "ya_ens_"  # the C ABI this class drives (GridEnsemble: ya_gens_, the same functions and more)
+    # What tells the three classes apart: the prefix of the C ABI the class drives (the grid ones: the same functions
+    # and more), the _ffi function that loads its library, and what an unknown model's message calls it.
+    _PREFIX, _LOADER, _NOUN = "ya_ens_", "ensemble_lib", "ensemble"
 
     def _f(self, name):
         return getattr(self.lib, self._PREFIX + name)
 
     def __init__(self, model, n_replicas, n_max, lib=None):
-        self.lib = lib if lib is not None else _ffi.ensemble_lib()
+        self._create(lib, model, n_replicas, n_max)
+
+    def _create(self, lib, model, n_replicas, n_max, *values):
+        """<prefix>create(model, n_replicas, n_max, *values, &handle) on `lib` (None: the class's own library), its
+        codes turned into exceptions, and the handle attached."""
+        self.lib = lib if lib is not None else getattr(_ffi, self._LOADER)()
         handle = C.c_void_p()
-        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), C.byref(handle))
+        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), *values, C.byref(handle))
         if code == -1:
-            raise YallaError(f"unknown ensemble model {model!r}; known: {models(self.lib)}")
-        _check(code, "ya_ens_create")
+            raise YallaError(f"unknown {self._NOUN} model {model!r}; known: {_models(self.lib, self._PREFIX)}")
+        _check(code, self._PREFIX + "create")
         self._attach(model, handle, n_replicas, n_max)
 
     def _attach(self, model, handle, n_replicas, n_max):
@@ -183,18 +190,11 @@ class GridEnsemble(Ensemble):
 
     Every stage scans n_replicas * grid_size**3 counters: pick grid_size to fit the replicas, not 50.
     """
-    _PREFIX = "ya_gens_"
+    _PREFIX, _LOADER, _NOUN = "ya_gens_", "grid_ensemble_lib", "grid ensemble"
 
     def __init__(self, model, n_replicas, n_max, grid_size=50, cube_size=1.0, lib=None):
-        self.lib = lib if lib is not None else _ffi.grid_ensemble_lib()
-        handle = C.c_void_p()
-        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), int(grid_size), float(cube_size),
-                                 C.byref(handle))
-        if code == -1:
-            raise YallaError(f"unknown grid ensemble model {model!r}; known: {grid_models(self.lib)}")
-        _check(code, "ya_gens_create")
+        self._create(lib, model, n_replicas, n_max, int(grid_size), float(cube_size))
         self.grid_size = int(grid_size)
-        self._attach(model, handle, n_replicas, n_max)
 
     @property
     def cube_size(self):
@@ -232,18 +232,11 @@ class GabrielEnsemble(GridEnsemble):
     "gabriel_coefficient"), and: a `gabriel_coefficient` setter (of every replica, from the next step on) and
     `dense_cells()`, the cells the last force stage left to the dense kernel (more than 64 candidates).
     """
-    _PREFIX = "ya_gabens_"
+    _PREFIX, _LOADER, _NOUN = "ya_gabens_", "gabriel_ensemble_lib", "Gabriel ensemble"
 
     def __init__(self, model, n_replicas, n_max, grid_size=50, cube_size=1.0, gabriel_coefficient=0.8, lib=None):
-        self.lib = lib if lib is not None else _ffi.gabriel_ensemble_lib()
-        handle = C.c_void_p()
-        code = self._f("create")(model.encode(), int(n_replicas), int(n_max), int(grid_size), float(cube_size),
-                                 float(gabriel_coefficient), C.byref(handle))
-        if code == -1:
-            raise YallaError(f"unknown Gabriel ensemble model {model!r}; known: {gabriel_models(self.lib)}")
-        _check(code, "ya_gabens_create")
+        self._create(lib, model, n_replicas, n_max, int(grid_size), float(cube_size), float(gabriel_coefficient))
         self.grid_size = int(grid_size)
-        self._attach(model, handle, n_replicas, n_max)
 
     @property
     def gabriel_coefficient(self):
@@ -261,16 +254,18 @@ class GabrielEnsemble(GridEnsemble):
         return n
 
 
+def _models(lib, prefix):
+    names, count = getattr(lib, prefix + "models_name"), getattr(lib, prefix + "models_count")
+    return [names(i).decode() for i in range(count())]
+
+
 def models(lib=None):
-    lib = lib if lib is not None else _ffi.ensemble_lib()
-    return [lib.ya_ens_models_name(i).decode() for i in range(lib.ya_ens_models_count())]
+    return _models(lib if lib is not None else _ffi.ensemble_lib(), "ya_ens_")
 
 
 def grid_models(lib=None):
-    lib = lib if lib is not None else _ffi.grid_ensemble_lib()
-    return [lib.ya_gens_models_name(i).decode() for i in range(lib.ya_gens_models_count())]
+    return _models(lib if lib is not None else _ffi.grid_ensemble_lib(), "ya_gens_")
 
 
 def gabriel_models(lib=None):
-    lib = lib if lib is not None else _ffi.gabriel_ensemble_lib()
-    return [lib.ya_gabens_models_name(i).decode() for i in range(lib.ya_gabens_models_count())]
+    return _models(lib if lib is not None else _ffi.gabriel_ensemble_lib(), "ya_gabens_")
