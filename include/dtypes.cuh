@@ -76,12 +76,15 @@ __host__ __device__ __forceinline__ Pt zero()
 }
 
 // 1 / b rounded to nearest: the factor in the reference's `Pt / b` (dtypes.cuh:202-217
-// multiplies by 1. / b).  On the device this is the compiler's own expansion of
-// 1.0f / b (reciprocal estimate, two refinements, final residual correction)
-// without the rescaling and special-case fix-up, which only matter outside
-// 2^-64 <= |b| <= 2^64; arguments out there take the library path.  Verified against
-// 1.0f / b for EVERY binary32 argument by tests/test_parity_gpu.py
-// (ya::check_reciprocal_all): seven instructions instead of fourteen per pair.
+// multiplies by 1. / b).  On the device: the reciprocal estimate (v_rcp_f32, 1 ulp), one
+// Newton refinement and one residual correction -- four fused multiply-adds.  The
+// compiler's own expansion of 1.0f / b corrects the residual a second time (six) and
+// rescales and fixes up special cases around that, which only matter outside
+// 2^-64 <= |b| <= 2^64; arguments out there take the library path.  The second
+// correction never changes a bit inside that range (round 7; it had been kept through
+// round 6): verified against 1.0f / b for EVERY binary32 argument by
+// tests/test_parity_gpu.py (ya::check_reciprocal_all).  Five instructions instead of
+// fourteen per pair.
 __host__ __device__ __forceinline__ float reciprocal(const float b)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(YA_ARITH_FAST)
@@ -95,9 +98,7 @@ __host__ __device__ __forceinline__ float reciprocal(const float b)
     const float e0 = __builtin_fmaf(-b, r0, 1.0f);
     const float r1 = __builtin_fmaf(e0, r0, r0);
     const float e1 = __builtin_fmaf(-b, r1, 1.0f);
-    const float q1 = __builtin_fmaf(e1, r1, r1);
-    const float e2 = __builtin_fmaf(-b, q1, 1.0f);
-    float out = __builtin_fmaf(e2, r1, q1);
+    float out = __builtin_fmaf(e1, r1, r1);
     if (__builtin_expect(!(a >= 0x1p-64f && a <= 0x1p+64f), 0)) out = 1.0f / b;
     return out;
 #else

@@ -162,7 +162,8 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_order_batched(const int n_m
 // ya::grid_force_bits for every replica at once: a one-wavefront workgroup serves 64 sorted slots of ONE
 // replica.  The tile is grid_force_bits' own (ya::grid_force_bits_tile): whole tiles only (no tail, no parts).
 // Cube ids and offs are the replica's own, so no stencil row reaches another replica's rows.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V>
+// (OFF32: a replica's old_v through 32-bit byte offsets from the replica's own base, bits::offsets_fit_32_bits(n_max))
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool OFF32>
 __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_force_bits_batched(const int n_max,
     const int blocks_per_replica, const int* __restrict__ d_n, const Entry<Pt>* __restrict__ sorted_all,
     const float4* __restrict__ sorted_v_all, const int* __restrict__ cube_id_all, const int* __restrict__ offs_all,
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     if (w.block * bits::BLOCK >= n) return;  // (the whole workgroup: blocks past n[r] return at once)
     const size_t base = (size_t)w.replica * n_max;
     // (tiles in storage order: which workgroup serves which tile changes no result)
-    grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, false>(n, w.block, (int)base, -1, 0, sorted_all + base,
+    grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, false, OFF32>(n, w.block, (int)base, -1, 0, sorted_all + base,
         sorted_v_all + base, cube_id_all + base, offs_all + (size_t)w.replica * (n_cubes + 1), gs, n_cubes, cut2,
         d_dX_all + base, has_gen, n, nullptr, nullptr, nullptr, nullptr, by_plane);
 }
@@ -387,8 +388,8 @@ protected:
             n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen,  \
             by_plane);                                                                                          \
     }
-#define YA_ENS_BITS_LAUNCH(stage_v_)                                                                            \
-    ya::ens::grid_force_bits_batched<Pt, pw_int, pw_friction, stage_v_><<<this->grid_of(blocks), ya::bits::BLOCK>>>( \
+#define YA_ENS_BITS_LAUNCH(stage_v_, off32_)                                                                    \
+    ya::ens::grid_force_bits_batched<Pt, pw_int, pw_friction, stage_v_, off32_><<<this->grid_of(blocks), ya::bits::BLOCK>>>( \
         n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane)
         if (lanes == 16) {
             YA_ENS_COOP_LAUNCH(16)
@@ -399,9 +400,11 @@ protected:
         } else {
             const int blocks = (n_max + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
             if (this->rows() <= (size_t)stage_v_max) {
-                YA_ENS_BITS_LAUNCH(true);
+                YA_ENS_BITS_LAUNCH(true, true);
+            } else if (ya::bits::offsets_fit_32_bits(n_max)) {
+                YA_ENS_BITS_LAUNCH(false, true);
             } else {
-                YA_ENS_BITS_LAUNCH(false);
+                YA_ENS_BITS_LAUNCH(false, false);
             }
         }
 #undef YA_ENS_BITS_LAUNCH

@@ -782,6 +782,7 @@ struct Pops {
 constexpr int BLOCK = YA_BITS_BLOCK;
 constexpr int WORDS = YA_MASK_WORDS;
 constexpr int PASS_BITS = 32 * WORDS;
+static_assert(BLOCK % 32 == 0, "phase 2 steps its word pointer by BLOCK / 32 elements per bit position");
 using Lds_word = __attribute__((address_space(3))) unsigned;
 
 template<typename Pt>
@@ -805,10 +806,19 @@ __device__ __forceinline__ void shift_in(unsigned& m, const float d2, const floa
         : "vcc");
 }
 
+// Phase 2 gathers old_v as `sorted_v` + a 32-bit unsigned BYTE offset (one uniform base, no 64-bit address
+// built per hit) while every slot's offset fits: 16 n < 2^32.  Grid_computer::forces asks here where it picks
+// the launch; larger systems keep the 64-bit form (OFF32 = false).
+__host__ __device__ constexpr bool offsets_fit_32_bits(const long long n)
+{
+    return n >= 0 && 16ll * n < (1ll << 32);
+}
+
 // One pass: up to three candidate segments [b_r, e_r) of the staged cells (LDS indices;
 // empty if b_r >= e_r), at most PASS_BITS bits after padding each to a multiple of four.
 // shift_r turns an LDS index of segment r into a slot of the sorted arrays.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
+    bool OFF32>
 __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const float4* __restrict__ sh_v,
     Lds_word* const words,
     const int b0, const int e0, const int b1, const int e1, const int b2, const int e2,
@@ -856,20 +866,37 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
     if (p & 31) *mp = m << (32 - (p & 31));  // left-align the last, partial word
 
     // ---- phase 2 ----
-    int left = ((p + 31) >> 5) - 1;  // words after the current one
+    // A hit at bit position q of segment r is staged cell q + d_r, sorted slot q + d_r + shift_r.  The three
+    // per-lane BYTE offsets of either are formed once per pass; a hit then costs two compares, the selects and
+    // one shift-and-add per address (round 7: the slot had been an index sum, a select of the uniform shifts
+    // -- moved from SGPRs to VGPRs every trip -- and a 64-bit shift-and-add per hit).
+    constexpr unsigned ENTRY = sizeof(Entry<Pt>);
+    constexpr bool ONE_OFFSET = ENTRY == sizeof(float4);  // sh_e and sh_v share the byte offset
+    const unsigned lds0 = ENTRY * (unsigned)d0, lds1 = ENTRY * (unsigned)d1, lds2 = ENTRY * (unsigned)d2_;
+    const unsigned gat0 = 16u * (unsigned)(d0 + shift0), gat1 = 16u * (unsigned)(d1 + shift1),
+                   gat2 = 16u * (unsigned)(d2_ + shift2);
+    Lds_word* const rp_end = words + ((p + 31) >> 5) * BLOCK;  // past this lane's last word
     unsigned cur = p > 0 ? words[0] : 0u;
-    Lds_word* rp = words + BLOCK;
+    Lds_word* rp = words + BLOCK;  // the word after the current one
     unsigned nxt = *rp;  // one spare row keeps this in bounds
     int wbase = 0;
 #define YA_BITS_LOAD(q_, other_, v_)                                                   \
     {                                                                                  \
         const bool in2 = (q_) >= p2, in1 = (q_) >= p1;                                 \
-        const int t = (q_) + (in2 ? d2_ : (in1 ? d1 : d0));                            \
-        other_ = sh_e[t];                                                              \
-        if (STAGE_V)                                                                   \
-            v_ = sh_v[t];                                                              \
-        else                                                                           \
-            v_ = sorted_v[(unsigned)(t + (in2 ? shift2 : (in1 ? shift1 : shift0)))];   \
+        if constexpr (OFF32 && ONE_OFFSET) {                                           \
+            const unsigned at = ENTRY * (unsigned)(q_) + (in2 ? lds2 : (in1 ? lds1 : lds0)); \
+            other_ = *(const Entry<Pt>*)((const char*)sh_e + at);                      \
+            if (STAGE_V) v_ = *(const float4*)((const char*)sh_v + at);                \
+        } else {                                                                       \
+            const int t = (q_) + (in2 ? d2_ : (in1 ? d1 : d0));                        \
+            other_ = sh_e[t];                                                          \
+            if (STAGE_V) v_ = sh_v[t];                                                 \
+            if (!STAGE_V && !OFF32) v_ = sorted_v[(unsigned)(t + (in2 ? shift2 : (in1 ? shift1 : shift0)))]; \
+        }                                                                              \
+        if constexpr (OFF32 && !STAGE_V) {                                             \
+            const unsigned at = 16u * (unsigned)(q_) + (in2 ? gat2 : (in1 ? gat1 : gat0)); \
+            v_ = *(const float4*)((const char*)sorted_v + (size_t)at);                 \
+        }                                                                              \
     }
 #define YA_BITS_PAIR(other_, v_)                                                       \
     {                                                                                  \
@@ -882,12 +909,11 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
 #ifdef YA_BITS_MEASUREMENT_PROBES  // measurement builds only (tools/micro/force_ab.hip; -Itools/ab): the balance and phase-1 probes
 #include "bits_probe.inc"
 #endif
-    while (cur != 0 || left > 0) {
-        const bool refill = cur == 0;  // then left > 0
-        cur = refill ? nxt : cur;
-        wbase += refill ? 32 : 0;
-        rp += refill ? BLOCK : 0;
-        left -= refill ? 1 : 0;
+    while (cur != 0 || rp < rp_end) {
+        const int step = cur == 0 ? 32 : 0;  // refill (then rp < rp_end): one select moves both wbase and rp
+        cur = cur == 0 ? nxt : cur;
+        wbase += step;
+        rp += step * (BLOCK / 32);
         nxt = *rp;
         if (cur != 0) {
             // up to POPS hits of the word: the loads of the later ones are issued before
@@ -916,15 +942,17 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
 
 // GLOBAL_IDS (z-slab decomposition): functors get global_id[local index]; a template parameter
 // rather than a null test so that the single-GPU kernel carries neither the test nor the gather.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
+    bool OFF32>
 __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile, const int id_base, const int half,
     const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
     const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
     Pt* d_dX, const bool has_gen, const int n_active, Pt* d_dX_sorted,
     const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane);
 
+// OFF32: old_v gathered through 32-bit byte offsets (bits::offsets_fit_32_bits(n); bits::pass)
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V = false,
-    bool GLOBAL_IDS = false>
+    bool GLOBAL_IDS = false, bool OFF32 = true>
 __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_force_bits(const int n,
     const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
     const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
@@ -1002,7 +1030,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
             tile = t_lo + t;
     }
     // which tile is mine ends here; the tile itself is the body an ensemble's kernel shares (include/ensemble_grid.cuh)
-    grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(n, tile, 0, half, compact - whole, sorted,
+    grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32>(n, tile, 0, half, compact - whole, sorted,
         sorted_v, cube_id, offs, gs, n_cubes, cut2, d_dX, has_gen, n_active, d_dX_sorted, global_id, tail_exchange,
         tail_tickets, by_plane);
 }
@@ -1012,7 +1040,8 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
 // handed the ids id_base + id (an ensemble's replica starts at id_base and its cube ids and offs[] are its own, so
 // the clamps of YA_ROW_BOUNDS keep every stencil row inside the replica's segment; a lone system's constant 0
 // folds away).  (No __restrict__ here: what may alias is said once, by the kernels' own parameters.)
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
+    bool OFF32>
 __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile, const int id_base, const int half,
     const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
     const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
@@ -1115,7 +1144,7 @@ __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile
             const int bits_needed = (max(se[0] - sb[0], 0) + 3 & ~3) + (max(se[1] - sb[1], 0) + 3 & ~3) +
                                     (max(se[2] - sb[2], 0) + 3 & ~3);
             if (!__any(bits_needed > bits::PASS_BITS)) {
-                bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(sh_e, sh_v, words, sb[0], se[0], sb[1], se[1], sb[2],
+                bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32>(sh_e, sh_v, words, sb[0], se[0], sb[1], se[1], sb[2],
                     se[2], shift[0], shift[1], shift[2], sorted_v, Xi, gi, cut2, F, sum_v, sum_friction,
                     global_id, id_base);
             } else {
@@ -1127,7 +1156,7 @@ __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile
                     const int rs = r == 0 ? shift[0] : (r == 1 ? shift[1] : shift[2]);
 #pragma unroll 1
                     for (int b = rb; __any(b < re); b += bits::PASS_BITS)
-                        bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS>(sh_e, sh_v, words, b, min(re, b + bits::PASS_BITS),
+                        bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32>(sh_e, sh_v, words, b, min(re, b + bits::PASS_BITS),
                             0, 0, 0, 0, rs, 0, 0, sorted_v, Xi, gi, cut2, F, sum_v, sum_friction, global_id, id_base);
                 }
             }
@@ -2871,6 +2900,13 @@ public:
     Ya_sum_order sum_order = YA_SUM_REFERENCE;
     int coop_lanes = 0;            // force_variant 3: 0 = from n (ya::coop::lanes_for), or 4 / 8 / 16
     int stage_v_max = 130000;      // grid_force_bits keeps old_v in LDS too up to this many cells
+    // grid_force_bits gathers old_v through 32-bit byte offsets while 16 n fits them (ya::bits::offsets_fit_32_bits)
+    // and builds 64-bit addresses beyond: 0 = by n, 64 = the 64-bit form at any size (A/B, tests; same results)
+    int gather_offset_bits = 0;
+    bool gathers_by_32_bit_offsets(const int n) const
+    {
+        return gather_offset_bits != 64 && ya::bits::offsets_fit_32_bits(n);
+    }
     Grid_computer(int n_max, int grid_size = 50, float cube_size = 1)
         : cube_size{cube_size}, grid{n_max, grid_size}
     {
@@ -2953,19 +2989,20 @@ protected:
     // at every step: the members are public and assigned directly).  A member added to forces() that picks a
     // kernel, a launch size or a kernel argument belongs here too.
     struct Step_variant {
-        int force_variant = -1, sum_order = 0, coop_lanes = 0, stage_v_max = 0, tail_tiles = 0;
+        int force_variant = -1, sum_order = 0, coop_lanes = 0, stage_v_max = 0, tail_tiles = 0, gather_offset_bits = 0;
         int tail_areas = 0;  // allocations of tail exchange areas so far: a graph made before one holds freed pointers
         const int* global_id = nullptr;
         bool operator==(const Step_variant& o) const
         {
             return force_variant == o.force_variant && sum_order == o.sum_order && coop_lanes == o.coop_lanes &&
-                   stage_v_max == o.stage_v_max && tail_tiles == o.tail_tiles && tail_areas == o.tail_areas &&
-                   global_id == o.global_id;
+                   stage_v_max == o.stage_v_max && tail_tiles == o.tail_tiles &&
+                   gather_offset_bits == o.gather_offset_bits && tail_areas == o.tail_areas && global_id == o.global_id;
         }
     };
     Step_variant step_variant() const
     {
-        return {force_variant, (int)sum_order, coop_lanes, stage_v_max, force_tail_tiles, tail_areas, d_global_id};
+        return {force_variant, (int)sum_order, coop_lanes, stage_v_max, force_tail_tiles, gather_offset_bits, tail_areas,
+            d_global_id};
     }
     int tail_areas = 0;
     Grid grid;
@@ -3080,8 +3117,8 @@ protected:
         } else if (lanes == 4) {
             YA_COOP_LAUNCH(4);
         } else if (force_variant == 2 || force_variant == 3) {
-#define YA_BITS_LAUNCH(stage_v_, gids_)                                                        \
-    YA_FORCE_LAUNCH((ya::grid_force_bits<Pt, pw_int, pw_friction, stage_v_, gids_>),           \
+#define YA_BITS_LAUNCH(stage_v_, gids_, off32_)                                                \
+    YA_FORCE_LAUNCH((ya::grid_force_bits<Pt, pw_int, pw_friction, stage_v_, gids_, off32_>),   \
         tail < 0 ? 16 * ((tiles + 7) / 8) : tiles + (tail > 0 ? std::min(tail, tiles) + 24 : 0), ya::bits::BLOCK, n, d_cells, \
         d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes, cut2, d_dX,  \
         has_gen, n_active, d_dX_in_cell_order, (const int*)d_global_id, tiles, tail,           \
@@ -3127,16 +3164,23 @@ protected:
             }
             // (old_v in LDS costs a launch of halves the residency it lives on: 13 KB per workgroup are 12 per CU)
             const bool stage_v = n <= stage_v_max && tail >= 0;
+            // (old_v from global memory: through 32-bit byte offsets while 16 n fits them; staged old_v is
+            // addressed in LDS, where every offset does)
+            const bool off32 = gathers_by_32_bit_offsets(n);
             if (d_global_id) {
                 if (stage_v) {
-                    YA_BITS_LAUNCH(true, true);
+                    YA_BITS_LAUNCH(true, true, true);
+                } else if (off32) {
+                    YA_BITS_LAUNCH(false, true, true);
                 } else {
-                    YA_BITS_LAUNCH(false, true);
+                    YA_BITS_LAUNCH(false, true, false);
                 }
             } else if (stage_v) {
-                YA_BITS_LAUNCH(true, false);
+                YA_BITS_LAUNCH(true, false, true);
+            } else if (off32) {
+                YA_BITS_LAUNCH(false, false, true);
             } else {
-                YA_BITS_LAUNCH(false, false);
+                YA_BITS_LAUNCH(false, false, false);
             }
 #undef YA_BITS_LAUNCH
         }

@@ -12,18 +12,17 @@
     // item 5); the scheme's own traffic (parking terms in LDS, adding them in order) comes on top.
     {
         int mine = 0;
-        for (int w = 0; w <= left; w++) mine += __builtin_popcount(words[w * BLOCK]);
+        for (int w = 0; w < (p + 31) >> 5; w++) mine += __builtin_popcount(words[w * BLOCK]);
         int total = mine;
         for (int o = 32; o >= 1; o >>= 1) total += __shfl_xor(total, o, 64);
         const int trips = (total + 64 * POPS - 1) / (64 * POPS);
         int last_q = 0;
         bool seen = false;  // (a lane without a hit so far has nothing valid to repeat: it sits the trip out)
         for (int trip = 0; trip < trips; trip++) {
-            if (cur == 0 && left > 0) {
+            if (cur == 0 && rp < rp_end) {
                 cur = nxt;
                 wbase += 32;
                 rp += BLOCK;
-                left--;
                 nxt = *rp;
             }
             // (the shipped loop's shape: the trip's loads first, then its arithmetic)
@@ -44,10 +43,10 @@
             }
         }
         cur = 0;
-        left = 0;
+        rp = rp_end;
     }
 #endif
 #ifdef YA_BITS_PHASE1_ONLY  // MEASUREMENT ONLY: staging + phase 1 alone (no pair is evaluated; results are wrong)
     F.x += __int_as_float(cur & 1u);  // (keep phase 1 alive)
-    cur = 0, left = 0;
+    cur = 0, rp = rp_end;
 #endif

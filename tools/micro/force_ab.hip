@@ -4,7 +4,8 @@
 // variant 1 (grid_force, byte FIFO) and variant 2 (grid_force_bits, compiled with this
 // executable's -DYA_BITS_BLOCK / -DYA_BITS_POPS / -DYA_MASK_WORDS flags) in interleaved rounds with HIP events,
 // (AB_BASE / AB_TEST select other pairs: 3 = grid_force_coop, 12 = grid_force_bits with old_v in LDS,
-// 102 = grid_force_bits summing by plane, with the tail of half tiles)
+// 102 = grid_force_bits summing by plane, with the tail of half tiles, 1002 = grid_force_bits building a 64-bit
+// address per gathered old_v)
 // and compares their outputs (d_dX by id and d_dX in sorted order) bit for bit.
 // One JSON line per run; tools/micro/force_ab.sh builds and runs a set of configurations.
 #include <algorithm>
@@ -44,10 +45,12 @@ struct Probe : public Solution<Pt, Grid_solver> {
 #endif
         this->stage_v_max = variant % 100 >= 10 ? 2000000000 : 0;
         // variants >= 100: Grid_computer::sum_order = YA_SUM_BY_PLANE (half tiles where the engine chooses them)
-        this->sum_order = variant >= 100 ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE;
+        this->sum_order = variant % 1000 >= 100 ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE;
 #ifdef AB_TAIL_TILES
         this->force_tail_tiles = AB_TAIL_TILES;
 #endif
+        // variants 1000 + v: v with old_v gathered through 64-bit addresses (Grid_computer::gather_offset_bits)
+        this->gather_offset_bits = variant >= 1000 ? 64 : 0;
         this->template forces<models::spring, friction_w_neighbour<Pt>>(
             n, this->d_sorted, this->d_sorted_v, out, false, n, out_sorted);
     }
@@ -124,5 +127,5 @@ int main(int argc, char** argv)
         AB_TAG, AB_BASE, AB_TEST, n, gs, dist, warm, rounds, median(us[0]), *std::min_element(us[0].begin(), us[0].end()),
         median(us[1]), *std::min_element(us[1].begin(), us[1].end()), mismatches, max_abs, max_rel, ya::bits::BLOCK,
         ya::bits::WORDS, YA_BITS_POPS);
-    return mismatches != 0 && (AB_TEST >= 100) == (AB_BASE >= 100);  // the two summation orders differ by rounding
+    return mismatches != 0 && (AB_TEST % 1000 >= 100) == (AB_BASE % 1000 >= 100);  // the two summation orders differ by rounding
 }

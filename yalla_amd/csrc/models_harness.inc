@@ -94,6 +94,7 @@ struct Cells<Pt, TILE> : public Solution<Pt, Tile_solver> {
     int set_force_variant(int) { return -2; }
     int set_coop_lanes(int) { return -2; }
     int set_stage_v_max(int) { return -2; }
+    int set_gather_offset_bits(int) { return -2; }
     int set_tail_tiles(int) { return -2; }
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
@@ -153,6 +154,17 @@ struct Cells<Pt, GRID> : public Solution<Pt, Harness_slab_solver> {
         return -2;
 #else
         this->stage_v_max = v;
+        return 0;
+#endif
+    }
+    // grid_force_bits: old_v through 32-bit byte offsets while they fit (0), or 64-bit addresses at any size (64)
+    int set_gather_offset_bits(int v)
+    {
+#ifdef YA_ORACLE
+        return -2;
+#else
+        if (v != 0 && v != 64) return -1;
+        this->gather_offset_bits = v;
         return 0;
 #endif
     }
@@ -253,6 +265,7 @@ struct Cells<Pt, GABRIEL> : public Solution<Pt, Gabriel_solver> {
     }
     int set_coop_lanes(int) { return -2; }
     int set_stage_v_max(int) { return -2; }
+    int set_gather_offset_bits(int) { return -2; }
     int set_tail_tiles(int) { return -2; }
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
@@ -664,6 +677,7 @@ struct Sim : public Sim_base {
         if (std::string(name) == "coop_lanes") return cells.set_coop_lanes((int)v);
         if (std::string(name) == "stage_v_max") return cells.set_stage_v_max((int)v);
         if (std::string(name) == "tail_tiles") return cells.set_tail_tiles((int)v);
+        if (std::string(name) == "gather_offset_bits") return cells.set_gather_offset_bits((int)v);
         if (std::string(name) == "sum_order") return cells.set_sum_order((int)v);
         if (std::string(name) == "sorted_pipeline") return cells.set_sorted_pipeline((int)v);
         if (std::string(name) == "graph") return cells.set_graph((int)v);
