@@ -41,13 +41,14 @@
 // WHOLE STEPS  cells.take_steps<my_force>(dt, 100) is 100 calls of take_step, bit for bit; where a replica fits
 // one workgroup's LDS (n_max <= ya::ens::whole_step_capacity<Pt>(), 1024 for the usual point types) and there are
 // no generic forces, it can run as ONE launch per steps_per_launch steps: a workgroup per replica runs the whole
-// steps from LDS (ya::ens::whole_steps, Ensemble::whole_steps).
+// steps from LDS (ya::ens::whole_steps, Ensemble::whole_steps) -- with 4, 16 or 64 lanes per cell for functors declared
+// stateless (ya::ens::whole_steps_coop, Ensemble::whole_step_lanes), the same bits.
 //
 // Ensemble<Pt, Gabriel_solver> (ensemble_gabriel.cuh, included after it) is the same for M Gabriel_solver systems,
 // on the grid form's build.
 //
 // Not here ("Ensembles"): the fast-arithmetic tier, graph capture, a per-replica dt or
-// gabriel_coefficient, slabs, whole steps for grid ensembles, several lanes per cell inside the whole-step kernel.
+// gabriel_coefficient, slabs, whole steps for grid ensembles.
 #pragma once
 
 #include "solvers.cuh"
@@ -239,6 +240,51 @@ constexpr int whole_step_capacity()
     return rows < (size_t)WHOLE_STEP_MAX_ROWS ? (int)rows : WHOLE_STEP_MAX_ROWS;
 }
 
+// Several lanes per cell (whole_stage_force_coop below) need a term buffer on top of that: one tile's pair terms,
+// [cell][component][j] floats for the 256 / lanes cells of a round and the NF + 4 components of a cell.  THE RULE for
+// the tile length, in partners: n_max rounded up to a multiple of 4 (phase (b) reads 16 bytes at a time; no replica
+// has more partners), at most WHOLE_STEP_COOP_MAX_TILE, at most what WHOLE_STEP_COOP_BUDGET bytes hold (small
+// replicas keep sharing a CU: with 4 lanes a partner costs 64 cells' terms) but no less than
+// WHOLE_STEP_COOP_MIN_TILE for that reason, and at most what is left of the workgroup's LDS.  Where the LDS has no
+// room for WHOLE_STEP_COOP_MIN_TILE partners the answer is 0: the launch runs with one lane per cell.  Otherwise the
+// answer is the launch's dynamic LDS, the term buffer 16-byte aligned behind whole_step_lds_bytes.  No bit depends
+// on the tile length: a cell's terms are added in ascending j into one running sum, tile after tile.
+// The budget is not measured.
+constexpr int WHOLE_STEP_COOP_MIN_TILE = 16;
+constexpr int WHOLE_STEP_COOP_MAX_TILE = 256;
+constexpr size_t WHOLE_STEP_COOP_BUDGET = 32 * 1024;
+template<typename Pt>
+constexpr size_t whole_step_coop_base(const int n_max)  // where the term buffer starts
+{
+    return (whole_step_lds_bytes<Pt>(n_max) + 15) / 16 * 16;
+}
+template<typename Pt>
+constexpr size_t whole_step_coop_bytes_per_partner(const int lanes)
+{
+    return (size_t)(UPDATE_BLOCK / lanes) * (N_floats<Pt>::value + 4) * sizeof(float);
+}
+template<typename Pt>
+constexpr size_t whole_step_coop_lds_bytes(const int n_max, const int lanes)
+{
+    const size_t base = whole_step_coop_base<Pt>(n_max);
+    const size_t per_partner = whole_step_coop_bytes_per_partner<Pt>(lanes);
+    if (base + WHOLE_STEP_STATIC_LDS + WHOLE_STEP_COOP_MIN_TILE * per_partner > LDS_PER_WORKGROUP) return 0;
+    const size_t room = (LDS_PER_WORKGROUP - WHOLE_STEP_STATIC_LDS - base) / per_partner / 4 * 4;
+    const size_t budget = WHOLE_STEP_COOP_BUDGET / per_partner / 4 * 4;
+    size_t tile = ((size_t)n_max + 3) / 4 * 4;
+    if (tile > (size_t)WHOLE_STEP_COOP_MAX_TILE) tile = WHOLE_STEP_COOP_MAX_TILE;
+    if (tile > budget) tile = budget < (size_t)WHOLE_STEP_COOP_MIN_TILE ? WHOLE_STEP_COOP_MIN_TILE : budget;
+    if (tile > room) tile = room;
+    return base + tile * per_partner;
+}
+// the tile length of that rule, in partners; 0 = no room
+template<typename Pt>
+constexpr int whole_step_coop_tile(const int n_max, const int lanes)
+{
+    const size_t bytes = whole_step_coop_lds_bytes<Pt>(n_max, lanes);
+    return bytes == 0 ? 0 : (int)((bytes - whole_step_coop_base<Pt>(n_max)) / whole_step_coop_bytes_per_partner<Pt>(lanes));
+}
+
 // tile_force_batched for the replica in LDS: one thread per cell (thread t owns rows t, t + 256, ...: the contract
 // of functors that keep per-cell state), partners straight from the LDS copy, j ascending over 0 .. n - 1 with
 // i == j included, ensemble-global ids, the pair and the right-hand side by tile_force_rows' own functions.
@@ -256,6 +302,71 @@ __device__ __forceinline__ void whole_stage_force(const int n, const int id_base
         for (int k = 0; k < n; k++)
             tile_pair<Pt, pw_int, pw_friction>(Xi, sh_in[k], sh_v[k], i, id_base + k, F, sum_v, sum_friction);
         store_rhs(sh_rhs, local, false, F, sum_v, sum_friction);
+    }
+}
+
+// tile_force_coop_batched for the replica in LDS, for functors that keep no per-cell state: COOP_LANES lanes per
+// cell.  The workgroup serves 256 / COOP_LANES cells per round, ceil(n / cells) rounds; per round and per tile of
+// `tile` partners tile_force_coop_rows' two phases, by its own functions: (a) lane l of a cell evaluates partners l,
+// l + COOP_LANES, ... of the tile straight from the stage's LDS arrays and leaves their terms in sh_part,
+// [cell][component][j]; (b) one lane per component (components lane, lane + COOP_LANES, ...) adds the tile's terms
+// in ascending j to a sum that started from +0 and is carried across tiles: whole_stage_force's sums, bit for bit,
+// whatever `tile` is.  The sums then meet in column 0 of the cell's rows and the cell's first lane writes the
+// right-hand side.  n is the workgroup's, so every thread makes every trip and reaches every barrier, those of
+// cells >= n included.  Every thread calls it; the caller's barrier follows.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+__device__ __forceinline__ void whole_stage_force_coop(const int n, const int id_base, const Pt* sh_in,
+    const float3* sh_v, Pt* sh_rhs, float* sh_part, const int tile)
+{
+    static_assert(COOP_LANES == 4 || COOP_LANES == 16 || COOP_LANES == 64, "4, 16 or 64 lanes per cell");
+    constexpr int COOP_CELLS = UPDATE_BLOCK / COOP_LANES;
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int NC = NF + 4;  // components summed per cell: F (NF), friction, friction * old_v (3)
+    constexpr int SLOTS = (NC + COOP_LANES - 1) / COOP_LANES;
+    const int cell = threadIdx.x / COOP_LANES, lane = threadIdx.x % COOP_LANES;
+    float* const my_terms = sh_part + (size_t)cell * NC * tile;  // this cell's [component][j] rows
+    for (int first = 0; first < n; first += COOP_CELLS) {
+        const int local = first + cell;
+        const bool active = local < n;
+        const int i = id_base + local;
+        Pt Xi = ya::zero<Pt>();
+        if (active) Xi = sh_in[local];
+        float acc[SLOTS];
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) acc[a] = 0.f;
+        for (int tile_start = 0; tile_start < n; tile_start += tile) {
+            const int n_tile = min(tile, n - tile_start);
+            __syncthreads();  // (the term buffer's readers of the tile or the round before are done)
+            if (active) {
+#pragma unroll 4
+                for (int jj = lane; jj < n_tile; jj += COOP_LANES) {
+                    const int k = tile_start + jj;
+                    coop_pair_terms<Pt, pw_int, pw_friction>(Xi, sh_in, sh_v, k, i, id_base + k,
+                        [&](const int c, const float term) { my_terms[(size_t)c * tile + jj] = term; });
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int a = 0; a < SLOTS; a++) {
+                const int c = lane + COOP_LANES * a;
+                if (c < NC && active) acc[a] = coop_ordered_sum(acc[a], my_terms + (size_t)c * tile, n_tile);
+            }
+        }
+        // row c of a cell was read by the lane that now writes its column 0, and by no other
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) {
+            const int c = lane + COOP_LANES * a;
+            if (c < NC && active) my_terms[(size_t)c * tile] = acc[a];
+        }
+        __syncthreads();
+        if (active && lane == 0) {
+            Pt F;
+#pragma unroll
+            for (int c = 0; c < NF; c++) field(F, c) = my_terms[(size_t)c * tile];
+            store_rhs(sh_rhs, local, false, F,
+                float3{my_terms[(size_t)(NF + 1) * tile], my_terms[(size_t)(NF + 2) * tile], my_terms[(size_t)(NF + 3) * tile]},
+                my_terms[(size_t)NF * tile]);
+        }
     }
 }
 
@@ -299,10 +410,21 @@ __device__ __forceinline__ float3 whole_stage_fix(const int kind, const int n, c
 // Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
 // end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
 // left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, const int* __restrict__ d_n, const float dt,
+// The body of both kernels below.  LANES = 1: a stage's forces are whole_stage_force; 4, 16 or 64:
+// whole_stage_force_coop with tiles of `tile` partners, everything else the same statements.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+__device__ __forceinline__ void whole_stage_forces(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
+    Pt* sh_rhs, float* sh_part, const int tile)
+{
+    if constexpr (LANES == 1)
+        whole_stage_force<Pt, pw_int, pw_friction>(n, id_base, sh_in, sh_v, sh_rhs);
+    else
+        whole_stage_force_coop<Pt, pw_int, pw_friction, LANES>(n, id_base, sh_in, sh_v, sh_rhs, sh_part, tile);
+}
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+__device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const int* __restrict__ d_n, const float dt,
     const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all)
+    float3* __restrict__ d_old_v_all, const int tile)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char whole_step_lds[];
     constexpr int NF = N_floats<Pt>::value;
@@ -316,6 +438,8 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, con
     float3* sh_v = reinterpret_cast<float3*>(sh_dX1 + n_max);
     float* sh_fold = reinterpret_cast<float*>(sh_v + n_max);
     float* sh_partials = sh_fold + NF * UPDATE_BLOCK;
+    float* sh_part = nullptr;  // the term buffer of several lanes per cell
+    if constexpr (LANES > 1) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
 
     const size_t base = (size_t)replica * n_max;
     Pt* __restrict__ d_X = d_X_all + base;
@@ -328,14 +452,14 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, con
 
     for (int step = 0; step < n_steps; step++) {
         // predictor: X1 = X + (dX - fix) dt (euler_step_batched)
-        whole_stage_force<Pt, pw_int, pw_friction>(n, (int)base, sh_X, sh_v, sh_dX);
+        whole_stage_forces<Pt, pw_int, pw_friction, LANES>(n, (int)base, sh_X, sh_v, sh_dX, sh_part, tile);
         __syncthreads();
         const float3 fix = whole_stage_fix<Pt>(kind1, n, sh_dX, fix_point, sh_fold, sh_partials);
         for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK)
             sh_X1[local] = sh_X[local] + ya::minus_fix(sh_dX[local], fix) * dt;
         __syncthreads();
         // corrector (heun_step_batched): old_v is written only after this barrier, when stage 2's forces have read it
-        whole_stage_force<Pt, pw_int, pw_friction>(n, (int)base, sh_X1, sh_v, sh_dX1);
+        whole_stage_forces<Pt, pw_int, pw_friction, LANES>(n, (int)base, sh_X1, sh_v, sh_dX1, sh_part, tile);
         __syncthreads();
         const float3 fix1 = whole_stage_fix<Pt>(kind2, n, sh_dX1, fix_point, sh_fold, sh_partials);
         const float fix_first[3] = {fix.x, fix.y, fix.z};  // stage 1's, as the predictor leaves it in d_fix_first
@@ -348,6 +472,25 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, con
         d_X[local] = sh_X[local];
         d_old_v[local] = sh_v[local];
     }
+}
+// One thread per cell: dynamic LDS of whole_step_lds_bytes<Pt>(n_max).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, const int* __restrict__ d_n, const float dt,
+    const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all)
+{
+    whole_steps_of_a_replica<Pt, pw_int, pw_friction, 1>(
+        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, 0);
+}
+// COOP_LANES (4, 16 or 64) lanes per cell, for functors that keep no per-cell state: dynamic LDS of
+// whole_step_coop_lds_bytes<Pt>(n_max, COOP_LANES), tile = whole_step_coop_tile<Pt>(n_max, COOP_LANES) > 0.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+__global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_coop(const int n_max, const int* __restrict__ d_n,
+    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const int tile)
+{
+    whole_steps_of_a_replica<Pt, pw_int, pw_friction, COOP_LANES>(
+        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile);
 }
 
 // Whether whole-step launches beat the six-launch step when the model leaves the choice to the engine
@@ -369,6 +512,19 @@ inline int lanes_for(const int n_replicas, const int n_max)
     if (waves >= 2048) return 1;
     if (waves >= 256) return 16;
     return n_max <= 4096 ? 64 : 16;
+}
+
+// Lanes per cell of a whole-step launch when the model leaves the choice to the engine and its functors are
+// stateless (Ensemble::whole_step_lanes == 0): the largest L of 64, 16, 4 with n_max * L <= 256, else 1.  Then one
+// round serves the whole replica, every lane evaluates ceil(n / L) pairs instead of n, and the ordered adds are what
+// they were: the work per lane only falls.  ABOVE 64 CELLS THE ANSWER (1) IS A PLACEHOLDER until measured
+// (profiles/ensemble_whole_lanes_bench.json): whether several lanes also pay with several rounds is not known.
+constexpr int whole_step_lanes_for(const int n_max)
+{
+    if (n_max <= UPDATE_BLOCK / 64) return 64;
+    if (n_max <= UPDATE_BLOCK / 16) return 16;
+    if (n_max <= UPDATE_BLOCK / 4) return 4;
+    return 1;
 }
 
 }  // namespace ens
@@ -591,6 +747,14 @@ public:
     int steps_per_launch = 256;
     // whole-step launches made so far (which path ran)
     long whole_step_launches = 0;
+    // Lanes per cell inside a whole-step launch: 0 (default) = the engine's choice -- one lane per cell unless the
+    // functors are declared stateless (YA_STATELESS), then ya::ens::whole_step_lanes_for(n_max); 1, 4, 16 or 64 = that
+    // many whatever the functor says (several lanes call the functor for one i at once, as with lanes_per_cell).  A
+    // replica whose LDS has no room for the terms of 16 partners (ya::ens::whole_step_coop_lds_bytes) is stepped with
+    // one lane per cell, still as whole-step launches.  Any choice gives the same bits.
+    int whole_step_lanes = 0;
+    // the lanes per cell of the last whole-step launch: 0 before any, 1 after that fallback
+    int whole_step_lanes_used = 0;
 
     // Six launches per take_step (per stage: forces, partial sums, update).
     Ensemble(int n_replicas, int n_max) : Base{n_replicas, n_max}
@@ -616,27 +780,59 @@ public:
             return;
         }
         assert(steps_per_launch >= 1);
-        const auto kernel = &ya::ens::whole_steps<Pt, pw_int, pw_friction>;
-        const size_t lds = ya::ens::whole_step_lds_bytes<Pt>(this->n_max);
-        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
-        static size_t lds_allowed = 64 * 1024;
-        if (lds > lds_allowed) {
-            YA_CHECK((int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_allowed = lds;
-        }
-        for (int done = 0; done < n_steps;) {
-            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
-            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k,
-                this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v);
-            whole_step_launches++;
-            done += k;
-        }
+        int lanes = whole_step_lanes;
+        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
+        if (lanes == 0)
+            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(this->n_max) : 1;
+        if (lanes > 1 && ya::ens::whole_step_coop_lds_bytes<Pt>(this->n_max, lanes) == 0) lanes = 1;  // no room
+        whole_step_lanes_used = lanes;
+        if (lanes == 64)
+            launch_whole_steps<pw_int, pw_friction, 64>(dt, n_steps);
+        else if (lanes == 16)
+            launch_whole_steps<pw_int, pw_friction, 16>(dt, n_steps);
+        else if (lanes == 4)
+            launch_whole_steps<pw_int, pw_friction, 4>(dt, n_steps);
+        else
+            launch_whole_steps<pw_int, pw_friction, 1>(dt, n_steps);
         // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
         this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
     }
 
 protected:
+    // n_steps whole steps as launches of at most steps_per_launch steps each, LANES lanes per cell (which fit).
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+    void launch_whole_steps(const float dt, const int n_steps)
+    {
+        const int tile = LANES > 1 ? ya::ens::whole_step_coop_tile<Pt>(this->n_max, LANES) : 0;
+        const size_t lds = LANES > 1 ? ya::ens::whole_step_coop_lds_bytes<Pt>(this->n_max, LANES)
+                                     : ya::ens::whole_step_lds_bytes<Pt>(this->n_max);
+        assert(LANES == 1 || tile >= 4);
+        const void* kernel;
+        if constexpr (LANES > 1)
+            kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>);
+        else
+            kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps<Pt, pw_int, pw_friction>);
+        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
+        static size_t lds_allowed = 64 * 1024;
+        if (lds > lds_allowed) {
+            YA_CHECK((int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_allowed = lds;
+        }
+        for (int done = 0; done < n_steps;) {
+            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
+            if constexpr (LANES > 1)
+                ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES><<<dim3((unsigned)this->n_replicas),
+                    ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2),
+                    this->fix_point, this->d_X, this->d_old_v, tile);
+            else
+                ya::ens::whole_steps<Pt, pw_int, pw_friction><<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK,
+                    lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point,
+                    this->d_X, this->d_old_v);
+            whole_step_launches++;
+            done += k;
+        }
+    }
+
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void forces(const Pt* d_in, Pt* d_rhs, const bool has_gen)
     {

@@ -454,6 +454,53 @@ __global__ __launch_bounds__(TILE_BLOCK) void tile_force(const int n,
     tile_force_rows<Pt, pw_int, pw_friction>(n, blockIdx.x, 0, d_X, d_old_v, d_dX, has_gen);
 }
 
+// The two phases of the several-lanes all-pairs kernels (tile_force_coop_rows below, ya::ens::whole_stage_force_coop
+// in include/ensemble.cuh), written once: what a pair leaves in LDS, and the order its terms are added in.
+// (a) One pair (i, j), the partner being row k of X and of old_v (LDS): its terms {F (NF), friction,
+// friction * old_v (3)} are handed to store(c, term), c = 0 .. NF + 3, which leaves term c in column j of the
+// caller's [component][j] rows.  (Arrays and a row, not references to the partner: old_v's row is then addressed
+// where it is read, after the functors, and no address lives across their calls.)
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Store>
+__device__ __forceinline__ void coop_pair_terms(const Pt Xi, const Pt* X, const float3* old_v, const int k, const int i,
+    const int j, const Store& store)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    Pt r = Xi - X[k];
+    float dist = dist3(r.x, r.y, r.z);
+    const Pt f = pw_int(Xi, r, dist, i, j);
+    const float friction = pw_friction(Xi, r, dist, i, j);
+#pragma unroll
+    for (int c = 0; c < NF; c++) store(c, field(f, c));
+    store(NF, friction);
+    // the old_v term only where the friction is not zero (solvers.cuh:312-316): a +0
+    // term instead changes no bit of a sum that started at +0 (such a sum never is -0)
+    const float3 v = old_v[k];
+    store(NF + 1, friction != 0 ? friction * v.x : 0.f);
+    store(NF + 2, friction != 0 ? friction * v.y : 0.f);
+    store(NF + 3, friction != 0 ? friction * v.z : 0.f);
+}
+// (b) sum + terms[0] + terms[1] + ... + terms[n_terms - 1], added one after the other in that order.  `terms` is
+// 16-byte aligned.  Sixteen terms per trip: four 16-byte LDS reads in flight, then the adds in order.
+__device__ __forceinline__ float coop_ordered_sum(float sum, const float* terms, const int n_terms)
+{
+    const float4* terms4 = reinterpret_cast<const float4*>(terms);
+    int jj = 0;
+    for (; jj + 16 <= n_terms; jj += 16) {
+        float4 p[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) p[u] = terms4[jj / 4 + u];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            sum += p[u].x;
+            sum += p[u].y;
+            sum += p[u].z;
+            sum += p[u].w;
+        }
+    }
+    for (; jj < n_terms; jj++) sum += terms[jj];
+    return sum;
+}
+
 // The same all-pairs force with 16 or 64 lanes per cell (opt-in: Tile_computer::lanes_per_cell).
 // All pairs of 800 cells are only 13 wavefronts for tile_force, each lane walking its 800
 // partners alone: 0.19 ms per launch on a 256-CU chip.  Here a 256-thread workgroup owns 16 or 4
@@ -527,19 +574,8 @@ __device__ __forceinline__ void tile_force_coop_rows(const int n, const int bloc
 #pragma unroll 4
             for (int jj = lane; jj < n_tile; jj += COOP_LANES) {
                 const int j = id_base + tile_start + jj;
-                Pt r = Xi - sh_X[jj];
-                float dist = dist3(r.x, r.y, r.z);
-                const Pt f = pw_int(Xi, r, dist, i, j);
-                const float friction = pw_friction(Xi, r, dist, i, j);
-#pragma unroll
-                for (int c = 0; c < NF; c++) sh_part[cell][c][jj] = field(f, c);
-                sh_part[cell][NF][jj] = friction;
-                // the old_v term only where the friction is not zero (solvers.cuh:312-316): a +0
-                // term instead changes no bit of a sum that started at +0 (such a sum never is -0)
-                const float3 v = sh_v[jj];
-                sh_part[cell][NF + 1][jj] = friction != 0 ? friction * v.x : 0.f;
-                sh_part[cell][NF + 2][jj] = friction != 0 ? friction * v.y : 0.f;
-                sh_part[cell][NF + 3][jj] = friction != 0 ? friction * v.z : 0.f;
+                coop_pair_terms<Pt, pw_int, pw_friction>(
+                    Xi, sh_X, sh_v, jj, i, j, [&](const int c, const float term) { sh_part[cell][c][jj] = term; });
             }
         }
         __syncthreads();
@@ -547,26 +583,7 @@ __device__ __forceinline__ void tile_force_coop_rows(const int n, const int bloc
 #pragma unroll
         for (int a = 0; a < SLOTS; a++) {
             const int c = lane + COOP_LANES * a;
-            if (c < NC && active) {
-                // sixteen terms per trip: four 16-byte LDS reads in flight, then the adds in order
-                float sum = acc[a];
-                const float4* terms = reinterpret_cast<const float4*>(&sh_part[cell][c][0]);
-                int jj = 0;
-                for (; jj + 16 <= n_tile; jj += 16) {
-                    float4 p[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) p[u] = terms[jj / 4 + u];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        sum += p[u].x;
-                        sum += p[u].y;
-                        sum += p[u].z;
-                        sum += p[u].w;
-                    }
-                }
-                for (; jj < n_tile; jj++) sum += sh_part[cell][c][jj];
-                acc[a] = sum;
-            }
+            if (c < NC && active) acc[a] = coop_ordered_sum(acc[a], &sh_part[cell][c][0], n_tile);
         }
         __syncthreads();
     }

@@ -62,6 +62,9 @@ int ya_ens_set_old_v(ya_ens* ens, const float* in);
  * steps from LDS in one launch (ya::ens::whole_steps) whenever the call is eligible (no generic forces, so never
  * "push"; n_max within the point type's capacity, 1024 for every model here), 0 = the engine's choice.
  * "steps_per_launch": Ensemble::steps_per_launch (>= 1), the most steps one such launch runs.
+ * "whole_step_lanes": Ensemble::whole_step_lanes, the lanes per cell inside such a launch -- 1 (the harness's
+ * default) = one thread per cell (ya::ens::whole_steps), 4, 16 or 64 = that many (ya::ens::whole_steps_coop, whatever
+ * the functor declares), 0 = the engine's choice; any other value is refused (-3).
  * Any setting gives the same bits. */
 int ya_ens_set_param(ya_ens* ens, const char* name, double value);
 

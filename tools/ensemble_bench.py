@@ -7,6 +7,7 @@
     python tools/ensemble_bench.py --solver grid --trace-shape 64 2000 --steps 50
     python tools/ensemble_bench.py --solver gabriel [--out profiles/ensemble_gabriel_bench.json]
     python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
+    python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -35,6 +36,11 @@ step (whole_steps -1, the baseline), whole-step launches of one step each (whole
 launches between the stages) and of up to 256 steps each (steps_per_launch at its default: none between the steps
 either).  M in {1, 16, 64, 256, 1024, 4096} x n in {32, 100, 256, 512, 1024} with M * n^2 <= 2^28, so that a window
 stays short.  ratio_* = the setting's rate over the baseline's.
+
+--whole-steps --whole-step-lanes 0,1,4,16,64: ONE Ensemble("relu", M, n) per shape with whole_steps 1 (up to 256 steps
+per launch), the same protocol, the listed whole_step_lanes settings alternating; lanes 1 (one thread per cell, the
+reference column) is always among them.  n in {4, 16, 32, 64, 100, 256, 1024} x the same M range, M * n^2 <= 2^28.
+ratio_lanes_L = the rate with L lanes per cell over the rate with 1.
 """
 import argparse
 import json
@@ -56,6 +62,8 @@ GRID_SHAPES = [(m, n) for n in (500, 2000, 10000, 50000) for m in (1, 8, 64, 512
 GRID_LANES = (0, 1, 4, 8, 16)
 WHOLE_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
 WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), "whole_256_steps_per_launch": (1, 256)}
+WHOLE_LANES_SHAPES = [(m, n) for n in (4, 16, 32, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)
+                      if m * n * n <= 2 ** 28]
 GABRIEL_SHAPES = [(m, n) for n in (100, 500, 2000, 10000) for m in (1, 8, 64, 512) if m * n <= 5000000]
 GABRIEL_LANES = (0,)  # (no lanes setting: one column)
 DT = 0.01
@@ -113,6 +121,9 @@ class Together:
     def whole(self, whole_steps, steps_per_launch):
         self.ens.set_param("whole_steps", whole_steps)
         self.ens.set_param("steps_per_launch", steps_per_launch)
+
+    def whole_lanes(self, lanes):
+        self.ens.set_param("whole_step_lanes", lanes)
 
     def steps(self, k):
         self.ens.take_step(DT, k)
@@ -226,6 +237,60 @@ def main_whole(args):
                       "max_ratio": max(r["ratio_whole_256_steps_per_launch"] for r in rows)}))
 
 
+def measure_whole_lanes(m, n, lanes_list, window, repeats):
+    b = Together(m, n)
+    try:
+        b.whole(1, 256)
+        ks = {}
+        for lanes in lanes_list:
+            b.whole_lanes(lanes)
+            b.steps(3)
+            ks[lanes] = calibrate(b, window)
+        samples = {lanes: [] for lanes in lanes_list}
+        for _ in range(repeats):  # L0, L1, L4, ..., L0, ...
+            for lanes in lanes_list:
+                b.whole_lanes(lanes)
+                samples[lanes].append(timed(b, ks[lanes]))
+        launches = b.ens.whole_step_launches
+    finally:
+        b.close()
+    row = {"n_replicas": m, "n": n, "whole_step_launches": launches}
+    for lanes in lanes_list:
+        row[f"lanes_{lanes}"] = summary(samples[lanes], m * n, ks[lanes])
+    for lanes in lanes_list:
+        row[f"ratio_lanes_{lanes}"] = row[f"lanes_{lanes}"]["cell_updates_per_s"] / row["lanes_1"]["cell_updates_per_s"]
+    row["spread"] = max(row[f"lanes_{lanes}"]["spread"] for lanes in lanes_list)  # of the worst side
+    return row
+
+
+def main_whole_lanes(args):
+    lanes_list = sorted({int(v) for v in args.whole_step_lanes.split(",")} | {1})
+    shapes = WHOLE_LANES_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting
+        run = Together(m, n)
+        run.whole(1, 256)
+        for lanes in lanes_list:
+            run.whole_lanes(lanes)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure_whole_lanes(m, n, lanes_list, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"L{lanes}: {r[f'lanes_{lanes}']['us_per_step']:9.2f}" for lanes in lanes_list)
+              + " us/step   ratios " + " ".join(f"{r[f'ratio_lanes_{lanes}']:.2f}" for lanes in lanes_list)
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --whole-steps --whole-step-lanes " + args.whole_step_lanes,
+                      "model": "relu", "dt": DT, "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio_lanes_0": min(r.get("ratio_lanes_0", 1.0) for r in rows),
+                      "max_ratio_lanes_0": max(r.get("ratio_lanes_0", 1.0) for r in rows)}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None)
@@ -238,11 +303,20 @@ def main():
     ap.add_argument("--solver", choices=("tile", "grid", "gabriel"), default="tile")
     ap.add_argument("--whole-steps", action="store_true",
                     help="whole-step launches against the six-launch step of the same Ensemble (tile solver only)")
+    ap.add_argument("--whole-step-lanes", default=None, metavar="L,L,...",
+                    help="with --whole-steps: these whole_step_lanes settings against lanes 1 of the same Ensemble")
     args = ap.parse_args()
+    if args.whole_step_lanes and not args.whole_steps:
+        ap.error("--whole-step-lanes goes with --whole-steps")
     if args.whole_steps:
         if args.solver != "tile" or args.trace_shape:
             ap.error("--whole-steps measures the all-pairs ensemble, and takes no --trace-shape")
-        main_whole(args)
+        if args.whole_step_lanes:
+            if not set(args.whole_step_lanes.split(",")) <= {"0", "1", "4", "16", "64"}:
+                ap.error("--whole-step-lanes takes a list out of 0,1,4,16,64")
+            main_whole_lanes(args)
+        else:
+            main_whole(args)
         return
     global GRID, GABRIEL, LANES, SHAPES
     if args.solver == "grid":

@@ -27,6 +27,7 @@ struct Base : public Replicas {
     virtual void set_lanes(int lanes) = 0;
     virtual void set_whole_steps(int mode) = 0;
     virtual void set_steps_per_launch(int steps) = 0;
+    virtual void set_whole_step_lanes(int lanes) = 0;
 };
 
 // models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
@@ -50,8 +51,14 @@ template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_
 struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
     using Replicas_of<Ensemble<Pt>, Base>::cells;
     // The harness's own default is the six-launch step (whole_steps = -1): what its callers ran before the
-    // whole-step launches existed; set_param("whole_steps", 0 | 1) opts in.
-    Sim(int n_replicas, int n_max) : Replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max} { cells.whole_steps = -1; }
+    // whole-step launches existed; set_param("whole_steps", 0 | 1) opts in.  Likewise one lane per cell inside a
+    // whole-step launch (whole_step_lanes = 1): the kernel its callers ran before there was a choice;
+    // set_param("whole_step_lanes", 0 | 4 | 16 | 64) changes it.
+    Sim(int n_replicas, int n_max) : Replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max}
+    {
+        cells.whole_steps = -1;
+        cells.whole_step_lanes = 1;
+    }
     long take_steps(float dt, int n_steps) override
     {
         const long launches_before = cells.whole_step_launches;
@@ -63,6 +70,7 @@ struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
     void set_whole_steps(int mode) override { cells.whole_steps = mode; }
     void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
+    void set_whole_step_lanes(int lanes) override { cells.whole_step_lanes = lanes; }
 };
 
 static const Model<Base* (*)(int, int)> model_table[] = {
@@ -130,6 +138,11 @@ int ya_ens_set_param(ya_ens* e, const char* name, double v)
     if (std::string(name) == "steps_per_launch") {
         if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
         e->p->set_steps_per_launch((int)v);
+        return 0;
+    }
+    if (std::string(name) == "whole_step_lanes") {
+        if (v != 0 && v != 1 && v != 4 && v != 16 && v != 64) return -3;
+        e->p->set_whole_step_lanes((int)v);
         return 0;
     }
     return -2;

@@ -18,6 +18,11 @@ replica and apply to every replica.  Each replica holds, bit for bit, what a
 workgroup per replica runs up to `set_param("steps_per_launch", k)` steps from LDS, no launch boundary in between)
 wherever the model has no generic forces and n_max is at most 1024; 0 leaves the choice to the engine, -1 (this
 harness's default) never does.  The bits are the same either way; `whole_step_launches` counts the launches made.
+`set_param("whole_step_lanes", L)` sets the lanes per cell inside such a launch (Ensemble::whole_step_lanes): 1 (this
+harness's default) is one thread per cell, 4, 16 or 64 share a cell's pairs among that many lanes whatever the functor
+declares (ya::ens::whole_steps_coop; for replicas of a few dozen cells, which leave most of a workgroup idle
+otherwise), 0 leaves it to the engine: one lane unless the model's functors are declared YA_STATELESS, else the
+largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice gives the same bits.
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
 build per stage always; `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh).
