@@ -44,6 +44,11 @@
 // steps from LDS (ya::ens::whole_steps, Ensemble::whole_steps) -- with 4, 16 or 64 lanes per cell for functors declared
 // stateless (ya::ens::whole_steps_coop, Ensemble::whole_step_lanes), the same bits.
 //
+// LINKS  cells.take_steps<my_force>(dt, K, ya::ens::Replica_links{links, S}) steps with the ORDERED link forces of a
+// Links object over the flat id space (ensemble_links.cuh: S slots per replica, a cell's terms added in slot order,
+// no atomics): the one generic force that also runs inside whole-step launches (ya::ens::whole_steps_linked), the
+// same bits as the six-launch step with ya::ens::link_forces_ordered as its generic force.
+//
 // Ensemble<Pt, Gabriel_solver> (ensemble_gabriel.cuh, included after it) is the same for M Gabriel_solver systems,
 // on the grid form's build.
 //
@@ -263,10 +268,10 @@ constexpr size_t whole_step_coop_bytes_per_partner(const int lanes)
 {
     return (size_t)(UPDATE_BLOCK / lanes) * (N_floats<Pt>::value + 4) * sizeof(float);
 }
+// (the rule for a term buffer that starts at `base`, a multiple of 16: with links a list lies in between)
 template<typename Pt>
-constexpr size_t whole_step_coop_lds_bytes(const int n_max, const int lanes)
+constexpr size_t whole_step_coop_bytes_behind(const size_t base, const int n_max, const int lanes)
 {
-    const size_t base = whole_step_coop_base<Pt>(n_max);
     const size_t per_partner = whole_step_coop_bytes_per_partner<Pt>(lanes);
     if (base + WHOLE_STEP_STATIC_LDS + WHOLE_STEP_COOP_MIN_TILE * per_partner > LDS_PER_WORKGROUP) return 0;
     const size_t room = (LDS_PER_WORKGROUP - WHOLE_STEP_STATIC_LDS - base) / per_partner / 4 * 4;
@@ -277,6 +282,11 @@ constexpr size_t whole_step_coop_lds_bytes(const int n_max, const int lanes)
     if (tile > room) tile = room;
     return base + tile * per_partner;
 }
+template<typename Pt>
+constexpr size_t whole_step_coop_lds_bytes(const int n_max, const int lanes)
+{
+    return whole_step_coop_bytes_behind<Pt>(whole_step_coop_base<Pt>(n_max), n_max, lanes);
+}
 // the tile length of that rule, in partners; 0 = no room
 template<typename Pt>
 constexpr int whole_step_coop_tile(const int n_max, const int lanes)
@@ -285,10 +295,22 @@ constexpr int whole_step_coop_tile(const int n_max, const int lanes)
     return bytes == 0 ? 0 : (int)((bytes - whole_step_coop_base<Pt>(n_max)) / whole_step_coop_bytes_per_partner<Pt>(lanes));
 }
 
+}  // namespace ens
+}  // namespace ya
+
+// ordered link forces: Replica_links, link_forces_ordered, the LDS rule and the pieces of whole_steps_linked
+#define YA_ENSEMBLE_LINKS_FROM_ENSEMBLE_CUH
+#include "ensemble_links.cuh"
+#undef YA_ENSEMBLE_LINKS_FROM_ENSEMBLE_CUH
+
+namespace ya {
+namespace ens {
+
 // tile_force_batched for the replica in LDS: one thread per cell (thread t owns rows t, t + 256, ...: the contract
 // of functors that keep per-cell state), partners straight from the LDS copy, j ascending over 0 .. n - 1 with
 // i == j included, ensemble-global ids, the pair and the right-hand side by tile_force_rows' own functions.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+// HAS_GEN: the right-hand sides hold a start the forces are added to (the ordered link forces, ensemble_links.cuh).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool HAS_GEN = false>
 __device__ __forceinline__ void whole_stage_force(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
     Pt* sh_rhs)
 {
@@ -301,7 +323,7 @@ __device__ __forceinline__ void whole_stage_force(const int n, const int id_base
 #pragma unroll YA_TILE_UNROLL
         for (int k = 0; k < n; k++)
             tile_pair<Pt, pw_int, pw_friction>(Xi, sh_in[k], sh_v[k], i, id_base + k, F, sum_v, sum_friction);
-        store_rhs(sh_rhs, local, false, F, sum_v, sum_friction);
+        store_rhs(sh_rhs, local, HAS_GEN, F, sum_v, sum_friction);
     }
 }
 
@@ -314,7 +336,8 @@ __device__ __forceinline__ void whole_stage_force(const int n, const int id_base
 // whatever `tile` is.  The sums then meet in column 0 of the cell's rows and the cell's first lane writes the
 // right-hand side.  n is the workgroup's, so every thread makes every trip and reaches every barrier, those of
 // cells >= n included.  Every thread calls it; the caller's barrier follows.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES,
+    bool HAS_GEN = false>
 __device__ __forceinline__ void whole_stage_force_coop(const int n, const int id_base, const Pt* sh_in,
     const float3* sh_v, Pt* sh_rhs, float* sh_part, const int tile)
 {
@@ -363,7 +386,7 @@ __device__ __forceinline__ void whole_stage_force_coop(const int n, const int id
             Pt F;
 #pragma unroll
             for (int c = 0; c < NF; c++) field(F, c) = my_terms[(size_t)c * tile];
-            store_rhs(sh_rhs, local, false, F,
+            store_rhs(sh_rhs, local, HAS_GEN, F,
                 float3{my_terms[(size_t)(NF + 1) * tile], my_terms[(size_t)(NF + 2) * tile], my_terms[(size_t)(NF + 3) * tile]},
                 my_terms[(size_t)NF * tile]);
         }
@@ -406,25 +429,30 @@ __device__ __forceinline__ float3 whole_stage_fix(const int kind, const int n, c
     return fix;
 }
 
-// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
-// Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
-// end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
-// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
-// The body of both kernels below.  LANES = 1: a stage's forces are whole_stage_force; 4, 16 or 64:
-// whole_stage_force_coop with tiles of `tile` partners, everything else the same statements.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+// A stage's forces by LANES: 1 = whole_stage_force, 4, 16 or 64 = whole_stage_force_coop with tiles of `tile` partners.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool HAS_GEN = false>
 __device__ __forceinline__ void whole_stage_forces(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
     Pt* sh_rhs, float* sh_part, const int tile)
 {
     if constexpr (LANES == 1)
-        whole_stage_force<Pt, pw_int, pw_friction>(n, id_base, sh_in, sh_v, sh_rhs);
+        whole_stage_force<Pt, pw_int, pw_friction, HAS_GEN>(n, id_base, sh_in, sh_v, sh_rhs);
     else
-        whole_stage_force_coop<Pt, pw_int, pw_friction, LANES>(n, id_base, sh_in, sh_v, sh_rhs, sh_part, tile);
+        whole_stage_force_coop<Pt, pw_int, pw_friction, LANES, HAS_GEN>(n, id_base, sh_in, sh_v, sh_rhs, sh_part, tile);
 }
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+
+// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
+// Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
+// end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
+// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
+// The body of the kernels below.  LANES = 1: a stage's forces are whole_stage_force; 4, 16 or 64:
+// whole_stage_force_coop with tiles of `tile` partners, everything else the same statements.
+// LINKED (whole_steps_linked below): once per launch the workgroup builds the replica's incidence list behind the
+// step's arrays (whole_links_build); every stage starts with the ordered link forces of its positions as the
+// right-hand sides (whole_stage_links), to which the stage's forces are added.  Links do not change during a launch.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED = false>
 __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const int* __restrict__ d_n, const float dt,
     const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const int tile)
+    float3* __restrict__ d_old_v_all, const int tile, const Links_view links = Links_view{})
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char whole_step_lds[];
     constexpr int NF = N_floats<Pt>::value;
@@ -439,7 +467,17 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
     float* sh_fold = reinterpret_cast<float*>(sh_v + n_max);
     float* sh_partials = sh_fold + NF * UPDATE_BLOCK;
     float* sh_part = nullptr;  // the term buffer of several lanes per cell
-    if constexpr (LANES > 1) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
+    if constexpr (LANES > 1 && !LINKED) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
+    int* sh_off = nullptr;        // the incidence list: n_max + 1 offsets,
+    unsigned* sh_ent = nullptr;   // at most 2 slots_per_replica entries
+    if constexpr (LINKED) {
+        sh_off = reinterpret_cast<int*>(whole_step_lds + whole_step_links_base<Pt>(n_max));
+        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
+        if constexpr (LANES > 1)
+            sh_part = reinterpret_cast<float*>(
+                whole_step_lds + whole_step_links_part_base<Pt>(n_max, links.slots_per_replica));
+        whole_links_build(links, replica, n, n_max, sh_off, sh_ent, reinterpret_cast<int*>(sh_fold));
+    }
 
     const size_t base = (size_t)replica * n_max;
     Pt* __restrict__ d_X = d_X_all + base;
@@ -452,14 +490,22 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
 
     for (int step = 0; step < n_steps; step++) {
         // predictor: X1 = X + (dX - fix) dt (euler_step_batched)
-        whole_stage_forces<Pt, pw_int, pw_friction, LANES>(n, (int)base, sh_X, sh_v, sh_dX, sh_part, tile);
+        if constexpr (LINKED) {
+            whole_stage_links<Pt>(n, sh_X, sh_dX, sh_off, sh_ent, links.strength);
+            if constexpr (LANES > 1) __syncthreads();  // (another thread adds the cell's forces to it)
+        }
+        whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_X, sh_v, sh_dX, sh_part, tile);
         __syncthreads();
         const float3 fix = whole_stage_fix<Pt>(kind1, n, sh_dX, fix_point, sh_fold, sh_partials);
         for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK)
             sh_X1[local] = sh_X[local] + ya::minus_fix(sh_dX[local], fix) * dt;
         __syncthreads();
         // corrector (heun_step_batched): old_v is written only after this barrier, when stage 2's forces have read it
-        whole_stage_forces<Pt, pw_int, pw_friction, LANES>(n, (int)base, sh_X1, sh_v, sh_dX1, sh_part, tile);
+        if constexpr (LINKED) {
+            whole_stage_links<Pt>(n, sh_X1, sh_dX1, sh_off, sh_ent, links.strength);
+            if constexpr (LANES > 1) __syncthreads();
+        }
+        whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_X1, sh_v, sh_dX1, sh_part, tile);
         __syncthreads();
         const float3 fix1 = whole_stage_fix<Pt>(kind2, n, sh_dX1, fix_point, sh_fold, sh_partials);
         const float fix_first[3] = {fix.x, fix.y, fix.z};  // stage 1's, as the predictor leaves it in d_fix_first
@@ -491,6 +537,18 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_coop(const int n_max
 {
     whole_steps_of_a_replica<Pt, pw_int, pw_friction, COOP_LANES>(
         n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile);
+}
+// The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage; LANES = 1,
+// 4, 16 or 64: dynamic LDS of whole_step_links_lds_bytes<Pt>(n_max, links.slots_per_replica, LANES) > 0, tile =
+// whole_step_links_tile<Pt>(n_max, links.slots_per_replica, LANES).  Besides what whole_steps reads, the replica's
+// slots of links.d_link and *links.d_n are read, at the start of the launch.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+__global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_linked(const int n_max, const int* __restrict__ d_n,
+    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const int tile, const Links_view links)
+{
+    whole_steps_of_a_replica<Pt, pw_int, pw_friction, LANES, true>(
+        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile, links);
 }
 
 // Whether whole-step launches beat the six-launch step when the model leaves the choice to the engine
@@ -798,6 +856,58 @@ public:
         this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
     }
 
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, links);
+    }
+    // n_steps Heun steps of every replica with the ORDERED link forces of `links` as the generic force
+    // (ensemble_links.cuh: slot s belongs to replica s / slots_per_replica, a slot with an end outside its replica's
+    // rows is skipped, a cell's terms are added in slot order).  Bit for bit n_steps calls of
+    // take_step(dt, gen) where gen calls ya::ens::link_forces_ordered, and that loop unless the call runs whole:
+    // as whole-step launches (ya::ens::whole_steps_linked) where whole_steps allows it, n_max <=
+    // ya::ens::whole_step_capacity<Pt>() and the incidence list fits the workgroup's LDS
+    // (ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots_per_replica, 1) > 0); with whole_step_lanes lanes per
+    // cell where the term buffer fits beside the list, with one otherwise.  A launch reads the links and their
+    // count at its start: what a model's kernel left there before the call is what the call sees.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
+    {
+        const int slots = links.slots_per_replica;
+        assert(slots >= 0 && (size_t)this->n_replicas * (size_t)slots <= (size_t)links.links.n_max);
+        const bool eligible = this->n_max <= ya::ens::whole_step_capacity<Pt>() &&
+                              ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, slots, 1) != 0;
+        const bool whole = eligible && (whole_steps > 0 ||
+                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, this->n_max)));
+        if (!whole) {
+            const int n_max = this->n_max;
+            const int* d_n = this->d_n;
+            Links* l = &links.links;
+            Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
+                ya::ens::link_forces_ordered<Pt>(ya::ens::Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
+            };
+            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
+            return;
+        }
+        assert(steps_per_launch >= 1);
+        int lanes = whole_step_lanes;
+        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
+        if (lanes == 0)
+            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(this->n_max) : 1;
+        if (lanes > 1 && ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, slots, lanes) == 0) lanes = 1;  // no room
+        whole_step_lanes_used = lanes;
+        const ya::ens::Links_view view = ya::ens::view_of(links);
+        if (lanes == 64)
+            launch_whole_steps_linked<pw_int, pw_friction, 64>(dt, n_steps, view);
+        else if (lanes == 16)
+            launch_whole_steps_linked<pw_int, pw_friction, 16>(dt, n_steps, view);
+        else if (lanes == 4)
+            launch_whole_steps_linked<pw_int, pw_friction, 4>(dt, n_steps, view);
+        else
+            launch_whole_steps_linked<pw_int, pw_friction, 1>(dt, n_steps, view);
+        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;  // (as above)
+    }
+
 protected:
     // n_steps whole steps as launches of at most steps_per_launch steps each, LANES lanes per cell (which fit).
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
@@ -828,6 +938,29 @@ protected:
                 ya::ens::whole_steps<Pt, pw_int, pw_friction><<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK,
                     lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point,
                     this->d_X, this->d_old_v);
+            whole_step_launches++;
+            done += k;
+        }
+    }
+
+    // The same with the ordered link forces of `links` in every stage (ya::ens::whole_steps_linked; LANES fit).
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
+    void launch_whole_steps_linked(const float dt, const int n_steps, const ya::ens::Links_view links)
+    {
+        const int tile = ya::ens::whole_step_links_tile<Pt>(this->n_max, links.slots_per_replica, LANES);
+        const size_t lds = ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, links.slots_per_replica, LANES);
+        assert(lds > 0 && (LANES == 1 || tile >= 4));
+        const void* kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>);
+        static size_t lds_allowed = 64 * 1024;  // (as above)
+        if (lds > lds_allowed) {
+            YA_CHECK((int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_allowed = lds;
+        }
+        for (int done = 0; done < n_steps;) {
+            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
+            ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES><<<dim3((unsigned)this->n_replicas),
+                ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2),
+                this->fix_point, this->d_X, this->d_old_v, tile, links);
             whole_step_launches++;
             done += k;
         }

@@ -8,6 +8,7 @@
     python tools/ensemble_bench.py --solver gabriel [--out profiles/ensemble_gabriel_bench.json]
     python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
     python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
+    python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -41,6 +42,14 @@ stays short.  ratio_* = the setting's rate over the baseline's.
 per launch), the same protocol, the listed whole_step_lanes settings alternating; lanes 1 (one thread per cell, the
 reference column) is always among them.  n in {4, 16, 32, 64, 100, 256, 1024} x the same M range, M * n^2 <= 2^28.
 ratio_lanes_L = the rate with L lanes per cell over the rate with 1.
+
+--links: ONE LinkedEnsemble("relu_links", M, n, S = n) per shape (every cell holds one link to a random other cell of
+its replica), the same protocol, four settings alternating: link_forces with global atomics as a generic force of
+the six-launch step (links_path 1, whole_steps -1: a memset and the atomics kernel per stage -- the way before the
+ordered forces, the baseline), the ordered forces on the six-launch step (link_forces_ordered), and the ordered
+forces inside whole-step launches of one step each (a model that renews its links every step) and of up to 256 steps
+each.  M in {1, 16, 64, 256, 1024, 4096} x n in {32, 100, 256, 1024} with M * n^2 <= 2^28.  ratio_* = the setting's
+rate over the baseline's.
 """
 import argparse
 import json
@@ -53,7 +62,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from yalla_amd.ensemble import Ensemble, GabrielEnsemble, GridEnsemble  # noqa: E402
+from yalla_amd.ensemble import Ensemble, GabrielEnsemble, GridEnsemble, LinkedEnsemble  # noqa: E402
 from yalla_amd.solution import Solution  # noqa: E402
 
 SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
@@ -64,6 +73,10 @@ WHOLE_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 2
 WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), "whole_256_steps_per_launch": (1, 256)}
 WHOLE_LANES_SHAPES = [(m, n) for n in (4, 16, 32, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)
                       if m * n * n <= 2 ** 28]
+LINKS_SHAPES = [(m, n) for n in (32, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
+# (links_path, whole_steps, steps_per_launch)
+LINKS_SETTINGS = {"atomics_six_launches": (1, -1, 256), "ordered_six_launches": (0, -1, 256),
+                  "ordered_whole_1_step_per_launch": (0, 1, 1), "ordered_whole_256_steps_per_launch": (0, 1, 256)}
 GABRIEL_SHAPES = [(m, n) for n in (100, 500, 2000, 10000) for m in (1, 8, 64, 512) if m * n <= 5000000]
 GABRIEL_LANES = (0,)  # (no lanes setting: one column)
 DT = 0.01
@@ -124,6 +137,33 @@ class Together:
 
     def whole_lanes(self, lanes):
         self.ens.set_param("whole_step_lanes", lanes)
+
+    def steps(self, k):
+        self.ens.take_step(DT, k)
+        self.ens.synchronize()
+
+    def close(self):
+        self.ens.close()
+
+
+class Linked:
+    """One LinkedEnsemble("relu_links", m, n, n): cell i of every replica linked to a random other cell of it."""
+
+    def __init__(self, m, n):
+        self.ens = LinkedEnsemble("relu_links", m, n, n)
+        rng = np.random.default_rng(m * 10007 + n)
+        for r in range(m):
+            self.ens.h_X[r] = ball(n, r)
+        a = np.broadcast_to(np.arange(n), (m, n))
+        b = (a + 1 + rng.integers(0, n - 1, (m, n))) % n
+        self.ens.h_link[:] = np.stack([a, b], axis=2) + (np.arange(m) * n)[:, None, None]
+        self.ens.n_links = m * n
+        self.ens.copy_to_device()
+
+    def setting(self, links_path, whole_steps, steps_per_launch):
+        self.ens.set_param("links_path", links_path)
+        self.ens.set_param("whole_steps", whole_steps)
+        self.ens.set_param("steps_per_launch", steps_per_launch)
 
     def steps(self, k):
         self.ens.take_step(DT, k)
@@ -237,6 +277,60 @@ def main_whole(args):
                       "max_ratio": max(r["ratio_whole_256_steps_per_launch"] for r in rows)}))
 
 
+def measure_links(m, n, window, repeats):
+    b = Linked(m, n)
+    try:
+        ks = {}
+        for key, setting in LINKS_SETTINGS.items():
+            b.setting(*setting)
+            b.steps(3)
+            ks[key] = calibrate(b, window)
+        samples = {key: [] for key in ks}
+        for _ in range(repeats):  # atomics, ordered six, whole 1, whole 256, atomics, ...
+            for key, setting in LINKS_SETTINGS.items():
+                b.setting(*setting)
+                samples[key].append(timed(b, ks[key]))
+        launches = b.ens.whole_step_launches
+    finally:
+        b.close()
+    row = {"n_replicas": m, "n": n, "slots_per_replica": n, "whole_step_launches": launches}
+    for key in LINKS_SETTINGS:
+        row[key] = summary(samples[key], m * n, ks[key])
+    for key in list(LINKS_SETTINGS)[1:]:
+        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row["atomics_six_launches"]["cell_updates_per_s"]
+    row["spread"] = max(row[key]["spread"] for key in LINKS_SETTINGS)  # of the worst side
+    return row
+
+
+def main_links(args):
+    shapes = LINKS_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting
+        run = Linked(m, n)
+        for setting in LINKS_SETTINGS.values():
+            run.setting(*setting)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure_links(m, n, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:9.1f}" for key in LINKS_SETTINGS)
+              + " us/step   ratios " + " ".join(f"{r['ratio_' + key]:.2f}" for key in list(LINKS_SETTINGS)[1:])
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --links", "model": "relu_links", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows),
+                      "min_ratio_whole_1": min(r["ratio_ordered_whole_1_step_per_launch"] for r in rows),
+                      "max_ratio_whole_1": max(r["ratio_ordered_whole_1_step_per_launch"] for r in rows),
+                      "min_ratio_whole_256": min(r["ratio_ordered_whole_256_steps_per_launch"] for r in rows),
+                      "max_ratio_whole_256": max(r["ratio_ordered_whole_256_steps_per_launch"] for r in rows)}))
+
+
 def measure_whole_lanes(m, n, lanes_list, window, repeats):
     b = Together(m, n)
     try:
@@ -305,7 +399,14 @@ def main():
                     help="whole-step launches against the six-launch step of the same Ensemble (tile solver only)")
     ap.add_argument("--whole-step-lanes", default=None, metavar="L,L,...",
                     help="with --whole-steps: these whole_step_lanes settings against lanes 1 of the same Ensemble")
+    ap.add_argument("--links", action="store_true",
+                    help="ordered link forces (six launches, whole steps) against link_forces with atomics")
     args = ap.parse_args()
+    if args.links:
+        if args.solver != "tile" or args.trace_shape or args.whole_steps:
+            ap.error("--links measures the linked all-pairs ensemble on its own")
+        main_links(args)
+        return
     if args.whole_step_lanes and not args.whole_steps:
         ap.error("--whole-step-lanes goes with --whole-steps")
     if args.whole_steps:

@@ -17,6 +17,7 @@ CORE_LIB = os.path.join(_HERE, "libyalla_hip.so")
 ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ensemble.h
 GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid.so")  # include/yalla_ensemble_grid.h
 GABRIEL_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel.so")  # include/yalla_ensemble_gabriel.h
+LINKED_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_links.so")  # include/yalla_ensemble_links.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -107,6 +108,17 @@ GABRIEL_ENSEMBLE_ABI["ya_gabens_create"] = (
     C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(_ens)])
 GABRIEL_ENSEMBLE_ABI["ya_gabens_dense_cells"] = (C.c_int, [_ens])
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_links.h one to one: the ensemble's functions under
+# another prefix, create with the slots per replica and the links' strength, the links' host mirror and count, the
+# lanes of the last whole-step launch and the LDS rule.
+LINKED_ENSEMBLE_ABI = {name.replace("ya_ens_", "ya_lens_"): sig for name, sig in ENSEMBLE_ABI.items()}
+LINKED_ENSEMBLE_ABI["ya_lens_create"] = (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_ens)])
+LINKED_ENSEMBLE_ABI["ya_lens_h_link"] = (_pi, [_ens])
+LINKED_ENSEMBLE_ABI["ya_lens_set_n_links"] = (C.c_int, [_ens, C.c_int])
+LINKED_ENSEMBLE_ABI["ya_lens_get_n_links"] = (C.c_int, [_ens])
+LINKED_ENSEMBLE_ABI["ya_lens_whole_step_lanes_used"] = (C.c_int, [_ens])
+LINKED_ENSEMBLE_ABI["ya_lens_lds_bytes"] = (C.c_long, [C.c_char_p, C.c_int, C.c_int, C.c_int])
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -181,3 +193,10 @@ def gabriel_ensemble_lib():
     """The Gabriel ensemble harness, yalla_amd/libyalla_ensemble_gabriel.so (include/yalla_ensemble_gabriel.h),
     every entry point typed.  Raises if it has not been built: there is no fallback."""
     return _load(GABRIEL_ENSEMBLE_LIB, GABRIEL_ENSEMBLE_ABI)
+
+
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
+def linked_ensemble_lib():
+    """The linked ensemble harness, yalla_amd/libyalla_ensemble_links.so (include/yalla_ensemble_links.h), every
+    entry point typed.  Raises if it has not been built: there is no fallback."""
+    return _load(LINKED_ENSEMBLE_LIB, LINKED_ENSEMBLE_ABI)

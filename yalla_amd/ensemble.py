@@ -25,7 +25,8 @@ otherwise), 0 leaves it to the engine: one lane unless the model's functors are 
 largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice gives the same bits.
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
-build per stage always; `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh).
+build per stage always; `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh);
+`LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh).
 """
 import ctypes as C
 
@@ -259,6 +260,64 @@ class GabrielEnsemble(GridEnsemble):
         return n
 
 
+class LinkedEnsemble(Ensemble):
+    """Host-side mirror of `Ensemble<Pt, Tile_solver>` stepped with `ya::ens::Replica_links` (include/ensemble_links.cuh)
+    over include/yalla_ensemble_links.h: M all-pairs systems of one model, each with `slots_per_replica` link slots of
+    one `Links` object over the flat id space.  Everything `Ensemble` offers, and: `h_link`, the host mirror of the
+    links as an `(n_replicas, slots_per_replica, 2)` int32 view of ENSEMBLE-GLOBAL ids (replica r's cell i is
+    r * n_max + i); `n_links`, the used-slot count (slots from it on are ignored; a slot with a == b is inert; a slot
+    with an end outside its own replica's rows [r * n_max, r * n_max + n_r) is skipped); `copy_to_device()` hands both
+    over.  A cell's link terms are added in ascending slot order, so results repeat bit for bit and equal the CPU
+    restatement's serial loop; `set_param("whole_steps", 1)` runs them inside whole-step launches where the
+    incidence list fits (`LinkedEnsemble.lds_bytes(...) > 0` with one lane), the same bits.
+    `set_param("links_path", 1)` is `link_forces` with global atomics instead (no fixed order, never whole steps).
+
+        with LinkedEnsemble("relu_links", n_replicas=64, n_max=200, slots_per_replica=200) as cells:
+            cells.h_link[r, s] = (r * 200 + a, r * 200 + b); cells.n_links = 64 * 200
+            cells.copy_to_device()
+            cells.take_step(0.05, 100)
+    """
+    _PREFIX, _LOADER, _NOUN = "ya_lens_", "linked_ensemble_lib", "linked ensemble"
+
+    def __init__(self, model, n_replicas, n_max, slots_per_replica, strength=0.2, lib=None):
+        self._create(lib, model, n_replicas, n_max, int(slots_per_replica), C.c_float(strength))
+        self.slots_per_replica = int(slots_per_replica)
+        self.strength = float(strength)
+        shape = (self.n_replicas, self.slots_per_replica, 2)
+        if self.n_replicas * self.slots_per_replica > 0:
+            self.h_link = np.ctypeslib.as_array(self._f("h_link")(self._h), shape=shape)
+        else:
+            self.h_link = np.zeros(shape, np.int32)
+
+    def close(self):
+        self.h_link = None
+        super().close()
+
+    @property
+    def n_links(self):
+        return self._f("get_n_links")(self._h)
+
+    @n_links.setter
+    def n_links(self, value):
+        _check(self._f("set_n_links")(self._h, int(value)), "set n_links")
+
+    @property
+    def whole_step_lanes_used(self):
+        """The lanes per cell of the last whole-step launch: 0 before any, 1 where the term buffer of several lanes
+        did not fit beside the incidence list."""
+        return self._f("whole_step_lanes_used")(self._h)
+
+    @staticmethod
+    def lds_bytes(model, n_max, slots_per_replica, lanes=1, lib=None):
+        """ya::ens::whole_step_links_lds_bytes for the model's point type: the dynamic LDS of a linked whole-step
+        launch, 0 where there is no room.  Needs no GPU."""
+        lib = lib if lib is not None else _ffi.linked_ensemble_lib()
+        code = lib.ya_lens_lds_bytes(model.encode(), int(n_max), int(slots_per_replica), int(lanes))
+        if code < 0:
+            raise YallaError(f"ya_lens_lds_bytes({model!r}, {n_max}, {slots_per_replica}, {lanes}) failed with {code}")
+        return code
+
+
 def _models(lib, prefix):
     names, count = getattr(lib, prefix + "models_name"), getattr(lib, prefix + "models_count")
     return [names(i).decode() for i in range(count())]
@@ -274,3 +333,7 @@ def grid_models(lib=None):
 
 def gabriel_models(lib=None):
     return _models(lib if lib is not None else _ffi.gabriel_ensemble_lib(), "ya_gabens_")
+
+
+def linked_models(lib=None):
+    return _models(lib if lib is not None else _ffi.linked_ensemble_lib(), "ya_lens_")
