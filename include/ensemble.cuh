@@ -830,30 +830,12 @@ public:
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
-        const bool eligible = ya::is_no_gen_forces<Pt>(gen_forces) && this->n_max <= ya::ens::whole_step_capacity<Pt>();
-        const bool whole = eligible && (whole_steps > 0 ||
-                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, this->n_max)));
-        if (!whole) {
+        const Whole_plan plan = plan_whole<pw_int, pw_friction>(-1, !ya::is_no_gen_forces<Pt>(gen_forces));
+        if (!plan.whole) {
             for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
             return;
         }
-        assert(steps_per_launch >= 1);
-        int lanes = whole_step_lanes;
-        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
-        if (lanes == 0)
-            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(this->n_max) : 1;
-        if (lanes > 1 && ya::ens::whole_step_coop_lds_bytes<Pt>(this->n_max, lanes) == 0) lanes = 1;  // no room
-        whole_step_lanes_used = lanes;
-        if (lanes == 64)
-            launch_whole_steps<pw_int, pw_friction, 64>(dt, n_steps);
-        else if (lanes == 16)
-            launch_whole_steps<pw_int, pw_friction, 16>(dt, n_steps);
-        else if (lanes == 4)
-            launch_whole_steps<pw_int, pw_friction, 4>(dt, n_steps);
-        else
-            launch_whole_steps<pw_int, pw_friction, 1>(dt, n_steps);
-        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
-        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
+        run_whole<pw_int, pw_friction, false>(dt, n_steps, plan, ya::ens::Links_view{});
     }
 
     template<Pairwise_interaction<Pt> pw_int>
@@ -875,11 +857,8 @@ public:
     {
         const int slots = links.slots_per_replica;
         assert(slots >= 0 && (size_t)this->n_replicas * (size_t)slots <= (size_t)links.links.n_max);
-        const bool eligible = this->n_max <= ya::ens::whole_step_capacity<Pt>() &&
-                              ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, slots, 1) != 0;
-        const bool whole = eligible && (whole_steps > 0 ||
-                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, this->n_max)));
-        if (!whole) {
+        const Whole_plan plan = plan_whole<pw_int, pw_friction>(slots);
+        if (!plan.whole) {
             const int n_max = this->n_max;
             const int* d_n = this->d_n;
             Links* l = &links.links;
@@ -889,81 +868,97 @@ public:
             for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
             return;
         }
+        run_whole<pw_int, pw_friction, true>(dt, n_steps, plan, ya::ens::view_of(links));
+    }
+
+protected:
+    // How a take_steps call runs: as whole-step launches or not; if so, with how many lanes per cell, the term
+    // buffer's tile length in partners (0 with one lane) and the launch's dynamic LDS.
+    struct Whole_plan {
+        bool whole;
+        int lanes;
+        int tile;
+        size_t lds;
+    };
+    // THE PLAN of a take_steps call with the ordered links of `slots` slots per replica (slots < 0: without links,
+    // and has_gen says whether the call has generic forces).  Whole where the call is eligible -- the replica fits
+    // (whole_step_capacity), and without links there are no generic forces, with links the incidence list fits the
+    // workgroup's LDS too -- and whole_steps allows it; with whole_step_lanes lanes per cell (0: the engine's choice)
+    // where the term buffer fits, with one otherwise.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    Whole_plan plan_whole(const int slots, const bool has_gen = false) const
+    {
+        const int n_max = this->n_max;
+        const bool linked = slots >= 0;
+        const bool eligible = n_max <= ya::ens::whole_step_capacity<Pt>() &&
+                              (linked ? ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots, 1) != 0 : !has_gen);
+        const bool whole = eligible && (whole_steps > 0 ||
+                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, n_max)));
+        if (!whole) return {false, 0, 0, 0};
         assert(steps_per_launch >= 1);
         int lanes = whole_step_lanes;
         assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
         if (lanes == 0)
-            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(this->n_max) : 1;
-        if (lanes > 1 && ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, slots, lanes) == 0) lanes = 1;  // no room
-        whole_step_lanes_used = lanes;
-        const ya::ens::Links_view view = ya::ens::view_of(links);
-        if (lanes == 64)
-            launch_whole_steps_linked<pw_int, pw_friction, 64>(dt, n_steps, view);
-        else if (lanes == 16)
-            launch_whole_steps_linked<pw_int, pw_friction, 16>(dt, n_steps, view);
-        else if (lanes == 4)
-            launch_whole_steps_linked<pw_int, pw_friction, 4>(dt, n_steps, view);
-        else
-            launch_whole_steps_linked<pw_int, pw_friction, 1>(dt, n_steps, view);
-        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;  // (as above)
+            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(n_max) : 1;
+        // (an unlinked launch and a linked one of no slots differ: the list's n_max + 1 offsets are in the linked one)
+        const auto lds_with = [=](const int l) {
+            return linked  ? ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots, l)
+                   : l > 1 ? ya::ens::whole_step_coop_lds_bytes<Pt>(n_max, l)
+                           : ya::ens::whole_step_lds_bytes<Pt>(n_max);
+        };
+        if (lanes > 1 && lds_with(lanes) == 0) lanes = 1;  // no room
+        const int tile = linked      ? ya::ens::whole_step_links_tile<Pt>(n_max, slots, lanes)
+                         : lanes > 1 ? ya::ens::whole_step_coop_tile<Pt>(n_max, lanes)
+                                     : 0;
+        const size_t lds = lds_with(lanes);
+        assert(lds > 0 && (lanes == 1 || tile >= 4));
+        return {true, lanes, tile, lds};
     }
 
-protected:
-    // n_steps whole steps as launches of at most steps_per_launch steps each, LANES lanes per cell (which fit).
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
-    void launch_whole_steps(const float dt, const int n_steps)
+    // A planned whole run: the kernel of the plan's lanes.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
+    void run_whole(const float dt, const int n_steps, const Whole_plan plan, const ya::ens::Links_view links)
     {
-        const int tile = LANES > 1 ? ya::ens::whole_step_coop_tile<Pt>(this->n_max, LANES) : 0;
-        const size_t lds = LANES > 1 ? ya::ens::whole_step_coop_lds_bytes<Pt>(this->n_max, LANES)
-                                     : ya::ens::whole_step_lds_bytes<Pt>(this->n_max);
-        assert(LANES == 1 || tile >= 4);
-        const void* kernel;
-        if constexpr (LANES > 1)
-            kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>);
+        whole_step_lanes_used = plan.lanes;
+        if (plan.lanes == 64)
+            launch_whole<pw_int, pw_friction, 64, LINKED>(dt, n_steps, plan, links);
+        else if (plan.lanes == 16)
+            launch_whole<pw_int, pw_friction, 16, LINKED>(dt, n_steps, plan, links);
+        else if (plan.lanes == 4)
+            launch_whole<pw_int, pw_friction, 4, LINKED>(dt, n_steps, plan, links);
         else
-            kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps<Pt, pw_int, pw_friction>);
+            launch_whole<pw_int, pw_friction, 1, LINKED>(dt, n_steps, plan, links);
+        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
+        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
+    }
+
+    // n_steps whole steps as launches of at most steps_per_launch steps each, LANES lanes per cell (which fit); LINKED:
+    // with the ordered link forces of `links` in every stage (ya::ens::whole_steps_linked).
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
+    void launch_whole(const float dt, const int n_steps, const Whole_plan plan, const ya::ens::Links_view links)
+    {
         // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
         static size_t lds_allowed = 64 * 1024;
-        if (lds > lds_allowed) {
-            YA_CHECK((int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_allowed = lds;
-        }
-        for (int done = 0; done < n_steps;) {
-            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
-            if constexpr (LANES > 1)
-                ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES><<<dim3((unsigned)this->n_replicas),
-                    ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2),
-                    this->fix_point, this->d_X, this->d_old_v, tile);
-            else
-                ya::ens::whole_steps<Pt, pw_int, pw_friction><<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK,
-                    lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point,
-                    this->d_X, this->d_old_v);
-            whole_step_launches++;
-            done += k;
-        }
-    }
-
-    // The same with the ordered link forces of `links` in every stage (ya::ens::whole_steps_linked; LANES fit).
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
-    void launch_whole_steps_linked(const float dt, const int n_steps, const ya::ens::Links_view links)
-    {
-        const int tile = ya::ens::whole_step_links_tile<Pt>(this->n_max, links.slots_per_replica, LANES);
-        const size_t lds = ya::ens::whole_step_links_lds_bytes<Pt>(this->n_max, links.slots_per_replica, LANES);
-        assert(lds > 0 && (LANES == 1 || tile >= 4));
-        const void* kernel = reinterpret_cast<const void*>(&ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>);
-        static size_t lds_allowed = 64 * 1024;  // (as above)
-        if (lds > lds_allowed) {
-            YA_CHECK((int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_allowed = lds;
-        }
-        for (int done = 0; done < n_steps;) {
-            const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
-            ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES><<<dim3((unsigned)this->n_replicas),
-                ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k, this->fix_kind_of(1), this->fix_kind_of(2),
-                this->fix_point, this->d_X, this->d_old_v, tile, links);
-            whole_step_launches++;
-            done += k;
-        }
+        const auto launch = [&](auto kernel, auto... more) {
+            if (plan.lds > lds_allowed) {
+                YA_CHECK((int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+                lds_allowed = plan.lds;
+            }
+            for (int done = 0; done < n_steps;) {
+                const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
+                kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, plan.lds>>>(this->n_max, this->d_n, dt, k,
+                    this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v, more...);
+                whole_step_launches++;
+                done += k;
+            }
+        };
+        if constexpr (LINKED)
+            launch(&ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>, plan.tile, links);
+        else if constexpr (LANES > 1)
+            launch(&ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>, plan.tile);
+        else
+            launch(&ya::ens::whole_steps<Pt, pw_int, pw_friction>);
     }
 
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>

@@ -14,51 +14,10 @@
 //   * nothing is read back until the end.
 // Every replica is then compared with memcmp -- positions, old_v, count, the per-cell arrays -- with a
 // Solution<float3, Gabriel_solver> run of the same system, with the centre of mass fixed and after set_fixed_xy.
-#include "../../include/dtypes.cuh"
-#include "../../include/inits.cuh"
-#include "../../include/links.cuh"
-#include "../../include/property.cuh"
-#include "../../include/solvers.cuh"
-#include "../../include/ensemble.cuh"
+#include "support.cuh"
 
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-static int failures = 0;
-#define EXPECT(cond)                                                  \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);   \
-            failures++;                                               \
-        }                                                             \
-    } while (0)
-
-// the model's own arrays: one strength per replica, one kind and one neighbour counter per cell (flat id space)
-__device__ const float* d_strength;
-__device__ const int* d_kind;
-__device__ int* d_n_nbs;
-__device__ int d_rows_per_replica;
-
-__device__ float3 sweep_spring(float3 Xi, float3 r, float dist, int i, int j)
-{
-    float3 dF{0.f, 0.f, 0.f};
-    if (i == j || dist >= 1.f) return dF;
-    const float s = d_strength[i / d_rows_per_replica];   // <- the sweep: this replica's parameter
-    const float k = d_kind[i] == d_kind[j] ? 2.f : 1.f;
-    return r * (k * s * (0.6f - dist) / dist);
-}
-YA_STATELESS(float3, sweep_spring)
-
-// the same force, counting neighbours as examples/passive_growth.cu does: NOT stateless
-__device__ float3 counting_spring(float3 Xi, float3 r, float dist, int i, int j)
-{
-    float3 dF{0.f, 0.f, 0.f};
-    if (i == j || dist >= 1.f) return dF;
-    d_n_nbs[i] += 1;
-    const float s = d_strength[i / d_rows_per_replica];
-    return r * (s * (0.6f - dist) / dist);
-}
+using by_strength::counting_spring;  // the strength sweep with kinds and its counting twin (support.cuh)
+using by_strength::sweep_spring;
 
 // the reference's counting functor (its test_solvers.cu) on the model's own counters
 __device__ float3 count_gabriel_neighbours(float3 Xi, float3 r, float dist, int i, int j)
@@ -74,49 +33,18 @@ __global__ void reset_counters(int n, int* nbs)
     if (i < n) nbs[i] = 0;
 }
 
-// Replica r (of the array handed over) divides if its number in the sweep, first + r, is even and it has room:
-// cell 3 % n gets a daughter at row n, and d_n[r] grows -- on the device, nothing travels.
-__global__ void divide(int n_replicas, int n_max, int first, float3* d_X, float3* d_old_v, int* d_n, int* kind)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_replicas || (first + r) % 2 != 0) return;
-    const int n = d_n[r];
-    if (n <= 0 || n >= n_max) return;
-    const size_t base = (size_t)r * n_max;
-    const size_t mother = base + 3 % n, daughter = base + n;
-    d_X[daughter] = float3{d_X[mother].x + 0.05f, d_X[mother].y - 0.03f, d_X[mother].z + 0.02f};
-    d_old_v[daughter] = d_old_v[mother];
-    kind[daughter] = kind[mother];
-    d_n[r] = n + 1;
-}
-
 constexpr int M = 6, N_MAX = 400, STEPS = 6, GRID_SIZE = 12, DENSE = 3;
 constexpr float COEFFICIENT = 0.8f;
 static const int counts[M] = {300, 0, 64, 257, 129, 3};
 static const float strengths[M] = {0.5f, 0.75f, 1.f, 1.25f, 1.5f, 2.f};
 
-struct State {
-    std::vector<float3> X, v;
-    std::vector<int> kind, nbs;
-    int n;
-};
-
 // the initial rows of replica r: a seeded box well inside the 12^3 grid, different for every replica; replica
 // DENSE's box is half as wide: 257 cells in 1.5^3, more than 64 candidates for all but the outermost cells
-static void seed_rows(int r, float3* rows)
+static void seed_replica(int r, float3* rows)
 {
-    unsigned s = 12345u + 977u * (unsigned)r;
-    auto next = [&s]() {
-        s = s * 1664525u + 1013904223u;
-        return (float)(s >> 8) / 16777216.f;
-    };
     const float w = r == DENSE ? 1.5f : 3.f;
-    for (int i = 0; i < counts[r]; i++) rows[i] = float3{w * next() - w / 2, w * next() - w / 2, w * next() - w / 2};
+    seed_rows(12345u + 977u * (unsigned)r, counts[r], w, w / 2, rows);
 }
-static int kind_of(int r, int i) { return (i * 7 + r) % 3; }
-// links (2k, 2k + 1) of a replica: every cell in at most one link, so the atomic adds of link_forces have one
-// term per row and their order cannot matter
-static int n_links_of(int r) { return counts[r] / 4; }
 
 template<typename Cells>
 static void model_steps(Cells& cells, Links& links, Property<int>& kind, int n_replicas, int first, int fixed_xy,
@@ -135,27 +63,19 @@ static void model_steps(Cells& cells, Links& links, Property<int>& kind, int n_r
     }
 }
 
-static void point_model_at(const float* strength, const int* kind, int* nbs, int rows_per_replica)
-{
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_strength), &strength, sizeof(strength));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_kind), &kind, sizeof(kind));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_n_nbs), &nbs, sizeof(nbs));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rows_per_replica), &rows_per_replica, sizeof(int));
-}
-
 static State single(int r, const float* d_strengths, int fixed_xy, bool counting)
 {
     Solution<float3, Gabriel_solver> cells{N_MAX, GRID_SIZE, 1.f, COEFFICIENT};
     *cells.h_n = counts[r];
-    seed_rows(r, cells.h_X);
+    seed_replica(r, cells.h_X);
     cells.copy_to_device();
     Property<int> kind{N_MAX, "kind"}, nbs{N_MAX, "nbs"};
     for (int i = 0; i < N_MAX; i++) kind.h_prop[i] = kind_of(r, i), nbs.h_prop[i] = 0;
     kind.copy_to_device();
     nbs.copy_to_device();
     Links links{N_MAX, 0.3f};
-    for (int k = 0; k < n_links_of(r); k++) links.h_link[k] = Link{2 * k, 2 * k + 1};
-    *links.h_n = n_links_of(r);
+    for (int k = 0; k < n_links_of(counts[r]); k++) links.h_link[k] = Link{2 * k, 2 * k + 1};
+    *links.h_n = n_links_of(counts[r]);
     links.copy_to_device();
     point_model_at(d_strengths + r, kind.d_prop, nbs.d_prop, N_MAX);   // i / N_MAX == 0: this system's one parameter
     model_steps(cells, links, kind, 1, r, counts[r] > 0 ? fixed_xy : -1, counting);
@@ -177,7 +97,7 @@ static std::vector<State> together(const float* d_strengths, int fixed_xy, bool 
     Ensemble<float3, Gabriel_solver> cells{M, N_MAX, GRID_SIZE, 1.f, COEFFICIENT};
     for (int r = 0; r < M; r++) {
         cells.h_n[r] = counts[r];
-        seed_rows(r, cells.row(r, 0));
+        seed_replica(r, cells.row(r, 0));
     }
     cells.copy_to_device();
     Property<int> kind{M * N_MAX, "kind"}, nbs{M * N_MAX, "nbs"};   // sized for the flat id space, indexed by global id
@@ -188,7 +108,7 @@ static std::vector<State> together(const float* d_strengths, int fixed_xy, bool 
     Links links{M * N_MAX, 0.3f};
     int n_links = 0;
     for (int r = 0; r < M; r++)
-        for (int k = 0; k < n_links_of(r); k++)
+        for (int k = 0; k < n_links_of(counts[r]); k++)
             links.h_link[n_links++] = Link{(int)cells.index(r, 2 * k), (int)cells.index(r, 2 * k + 1)};
     *links.h_n = n_links;
     links.copy_to_device();
@@ -212,18 +132,6 @@ static std::vector<State> together(const float* d_strengths, int fixed_xy, bool 
         out[r].nbs.assign(nbs.h_prop + cells.index(r, 0), nbs.h_prop + cells.index(r, 0) + N_MAX);
     }
     return out;
-}
-
-static void compare(const std::vector<State>& ens, const std::vector<State>& alone)
-{
-    for (int r = 0; r < M; r++) {
-        const int n = alone[r].n;
-        EXPECT(ens[r].n == n);
-        EXPECT(memcmp(ens[r].X.data(), alone[r].X.data(), n * sizeof(float3)) == 0);
-        EXPECT(memcmp(ens[r].v.data(), alone[r].v.data(), n * sizeof(float3)) == 0);
-        EXPECT(memcmp(ens[r].kind.data(), alone[r].kind.data(), n * sizeof(int)) == 0);
-        EXPECT(memcmp(ens[r].nbs.data(), alone[r].nbs.data(), n * sizeof(int)) == 0);
-    }
 }
 
 // The reference's known answer in every replica, at global ids.
@@ -261,9 +169,7 @@ static void known_answer()
 int main()
 {
     known_answer();
-    float* d_strengths;
-    (void)hipMalloc(&d_strengths, sizeof(strengths));
-    (void)hipMemcpy(d_strengths, strengths, sizeof(strengths), hipMemcpyHostToDevice);
+    float* d_strengths = on_device(strengths, M);
     for (int fixed_xy : {-1, 2}) {
         std::vector<State> alone;
         for (int r = 0; r < M; r++) alone.push_back(single(r, d_strengths, fixed_xy, false));
@@ -287,9 +193,7 @@ int main()
         float swapped[M];
         memcpy(swapped, strengths, sizeof(strengths));
         swapped[0] = strengths[4];
-        float* d_swapped;
-        (void)hipMalloc(&d_swapped, sizeof(swapped));
-        (void)hipMemcpy(d_swapped, swapped, sizeof(swapped), hipMemcpyHostToDevice);
+        float* d_swapped = on_device(swapped, M);
         const std::vector<State> a = together(d_strengths, -1, false), b = together(d_swapped, -1, false);
         EXPECT(memcmp(a[0].X.data(), b[0].X.data(), counts[0] * sizeof(float3)) != 0);
         EXPECT(memcmp(a[2].X.data(), b[2].X.data(), counts[2] * sizeof(float3)) == 0);

@@ -12,45 +12,16 @@
 // that only ever takes the six-launch ordered path, in the three fixed modes, with 1 and 3 protrusions per cell.
 // Last, replicas of at most 40 cells under the default lanes: the counting functor keeps one lane per cell (and its
 // counters), the same force declared YA_STATELESS gets 4, the bits are the twin's either way.
-#include "../../include/dtypes.cuh"
-#include "../../include/inits.cuh"
-#include "../../include/links.cuh"
-#include "../../include/property.cuh"
-#include "../../include/solvers.cuh"
-#include "../../include/ensemble.cuh"
+#include "support.cuh"
 
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-static int failures = 0;
-#define EXPECT(cond)                                                  \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);   \
-            failures++;                                               \
-        }                                                             \
-    } while (0)
-
-__device__ const float* d_rest;
-__device__ int* d_n_nbs;
-__device__ int d_rows_per_replica;
-
-__device__ float3 counting_spring(float3 Xi, float3 r, float dist, int i, int j)
-{
-    float3 dF{0.f, 0.f, 0.f};
-    if (i == j || dist >= 1.f) return dF;
-    d_n_nbs[i] += 1;                                  // <- per-cell state without atomics: one thread per cell
-    const float L = d_rest[i / d_rows_per_replica];   // <- the sweep: this replica's parameter
-    return r * ((L - dist) / dist);
-}
+using by_rest::counting_spring;  // (support.cuh: reads d_sweep, counts in d_n_nbs)
 
 // The same force without the counter, and declared stateless: under the default the engine may give it several lanes.
 __device__ float3 plain_spring(float3 Xi, float3 r, float dist, int i, int j)
 {
     float3 dF{0.f, 0.f, 0.f};
     if (i == j || dist >= 1.f) return dF;
-    const float L = d_rest[i / d_rows_per_replica];
+    const float L = d_sweep[i / d_rows_per_replica];
     return r * ((L - dist) / dist);
 }
 YA_STATELESS(float3, plain_spring)
@@ -81,42 +52,11 @@ __global__ void update_protrusions(int n_replicas, int n_max, int prots_per_cell
     d_link[s] = l;
 }
 
-__global__ void divide(int n_replicas, int n_max, float3* d_X, float3* d_old_v, int* d_n)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_replicas || r % 2 != 0) return;
-    const int n = d_n[r];
-    if (n <= 0 || n >= n_max) return;
-    const size_t base = (size_t)r * n_max;
-    const size_t mother = base + 3 % n, daughter = base + n;
-    d_X[daughter] = float3{d_X[mother].x + 0.05f, d_X[mother].y - 0.03f, d_X[mother].z + 0.02f};
-    d_old_v[daughter] = d_old_v[mother];
-    d_n[r] = n + 1;
-}
-
 constexpr int M = 6, N_MAX = 300;
 static const int counts[M] = {120, 0, 64, 257, 298, 3};   // (298 + 2 daughters: the replica ends full)
 static const float rests[M] = {0.5f, 0.55f, 0.6f, 0.65f, 0.7f, 0.75f};
 
-struct State {
-    std::vector<float3> X, v;
-    std::vector<int> n, nbs;
-    long launches;
-    int lanes_used;
-};
-
-static void seed_rows(int r, float3* rows)
-{
-    unsigned s = 4321u + 977u * (unsigned)r;
-    auto next = [&s]() {
-        s = s * 1664525u + 1013904223u;
-        return (float)(s >> 8) / 16777216.f;
-    };
-    const float side = 1.f + 0.012f * (float)counts[r];
-    for (int i = 0; i < counts[r]; i++) rows[i] = float3{side * next(), side * next(), side * next()};
-}
-
-static State run(const float* d_rests, const bool whole, const int fixed_mode, const int prots_per_cell)
+static Run run(const float* d_rests, const bool whole, const int fixed_mode, const int prots_per_cell)
 {
     const int S = N_MAX * prots_per_cell;
     Ensemble<float3> cells{M, N_MAX};
@@ -124,17 +64,14 @@ static State run(const float* d_rests, const bool whole, const int fixed_mode, c
     cells.steps_per_launch = 2;
     for (int r = 0; r < M; r++) {
         cells.h_n[r] = counts[r];
-        seed_rows(r, cells.row(r, 0));
+        seed_rows(r, counts[r], cells.row(r, 0));
     }
     cells.copy_to_device();
     Property<int> nbs{M * N_MAX, "n_nbs"};
     for (int i = 0; i < M * N_MAX; i++) nbs.h_prop[i] = 0;
     nbs.copy_to_device();
     Links protrusions{M * S, 0.1f};
-    int rows_per_replica = N_MAX;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rest), &d_rests, sizeof(d_rests));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_n_nbs), &nbs.d_prop, sizeof(nbs.d_prop));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rows_per_replica), &rows_per_replica, sizeof(int));
+    point_model_at(d_rests, nullptr, nbs.d_prop, N_MAX);
 
     if (fixed_mode == 1) cells.set_fixed(2);
     if (fixed_mode == 2) cells.set_fixed_xy(1);
@@ -153,20 +90,7 @@ static State run(const float* d_rests, const bool whole, const int fixed_mode, c
     }
     cells.take_steps<counting_spring, friction_w_neighbour<float3>>(0.02f, 3, rl);  // 2 launches if whole
 
-    State out;
-    cells.copy_to_host();
-    out.X.assign(cells.h_X, cells.h_X + M * N_MAX);
-    out.v.resize(M * N_MAX);
-    (void)hipMemcpy(out.v.data(), cells.d_old_v, out.v.size() * sizeof(float3), hipMemcpyDeviceToHost);
-    nbs.copy_to_host();
-    out.nbs.assign(nbs.h_prop, nbs.h_prop + M * N_MAX);
-    for (int r = 0; r < M; r++) {
-        out.n.push_back(cells.h_n[r]);
-        EXPECT(cells.get_d_n(r) == cells.h_n[r]);
-    }
-    out.launches = cells.whole_step_launches;
-    out.lanes_used = cells.whole_step_lanes_used;
-    return out;
+    return read_back(cells, &nbs);
 }
 
 // Replicas of at most 40 cells, where ya::ens::whole_step_lanes_for gives a stateless functor 4 lanes per cell: the
@@ -175,7 +99,7 @@ constexpr int SMALL_M = 5, SMALL_N_MAX = 40, SMALL_PROTS = 2;
 static const int small_counts[SMALL_M] = {40, 0, 17, 33, 1};
 
 template<Pairwise_interaction<float3> force>
-static State small_run(const float* d_rests, const bool whole)
+static Run small_run(const float* d_rests, const bool whole)
 {
     const int S = SMALL_N_MAX * SMALL_PROTS;
     Ensemble<float3> cells{SMALL_M, SMALL_N_MAX};
@@ -197,10 +121,7 @@ static State small_run(const float* d_rests, const bool whole)
     for (int i = 0; i < SMALL_M * SMALL_N_MAX; i++) nbs.h_prop[i] = 0;
     nbs.copy_to_device();
     Links protrusions{SMALL_M * S, 0.1f};
-    int rows_per_replica = SMALL_N_MAX;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rest), &d_rests, sizeof(d_rests));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_n_nbs), &nbs.d_prop, sizeof(nbs.d_prop));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rows_per_replica), &rows_per_replica, sizeof(int));
+    point_model_at(d_rests, nullptr, nbs.d_prop, SMALL_N_MAX);
     const ya::ens::Replica_links rl{protrusions, S};
     for (int step = 0; step < 4; step++) {
         update_protrusions<<<(SMALL_M * S + 255) / 256, 256>>>(
@@ -208,17 +129,7 @@ static State small_run(const float* d_rests, const bool whole)
         cells.take_steps<force>(0.05f, 1, rl);   // 4 launches if whole
     }
     cells.take_steps<force>(0.02f, 3, rl);       // 1 launch if whole
-    State out;
-    cells.copy_to_host();
-    out.X.assign(cells.h_X, cells.h_X + SMALL_M * SMALL_N_MAX);
-    out.v.resize(SMALL_M * SMALL_N_MAX);
-    (void)hipMemcpy(out.v.data(), cells.d_old_v, out.v.size() * sizeof(float3), hipMemcpyDeviceToHost);
-    nbs.copy_to_host();
-    out.nbs.assign(nbs.h_prop, nbs.h_prop + SMALL_M * SMALL_N_MAX);
-    for (int r = 0; r < SMALL_M; r++) out.n.push_back(cells.h_n[r]);
-    out.launches = cells.whole_step_launches;
-    out.lanes_used = cells.whole_step_lanes_used;
-    return out;
+    return read_back(cells, &nbs);
 }
 
 int main()
@@ -226,14 +137,12 @@ int main()
     static_assert(ya::ens::whole_step_links_lds_bytes<float3>(N_MAX, 3 * N_MAX, 1) > 0, "the list of 3 protrusions per cell fits");
     static_assert(ya::ens::whole_step_links_lds_bytes<float3>(N_MAX, 3 * N_MAX, 1) % 16 == 0, "16-byte aligned");
     static_assert(ya::ens::whole_step_links_lds_bytes<float3>(1024, 20000, 1) == 0, "and a list beyond the LDS does not");
-    float* d_rests;
-    (void)hipMalloc(&d_rests, sizeof(rests));
-    (void)hipMemcpy(d_rests, rests, sizeof(rests), hipMemcpyHostToDevice);
+    float* d_rests = on_device(rests, M);
     for (int prots_per_cell : {1, 3}) {
-        State first;
+        Run first;
         for (int fixed_mode : {0, 1, 2}) {
-            const State twin = run(d_rests, false, fixed_mode, prots_per_cell);
-            const State mixed = run(d_rests, true, fixed_mode, prots_per_cell);
+            const Run twin = run(d_rests, false, fixed_mode, prots_per_cell);
+            const Run mixed = run(d_rests, true, fixed_mode, prots_per_cell);
             EXPECT(twin.launches == 0 && twin.lanes_used == 0);
             EXPECT(mixed.launches == 5 + 2);
             EXPECT(mixed.lanes_used == 1);  // (the functor is not declared stateless)
@@ -254,7 +163,7 @@ int main()
         }
         // the links matter: with one protrusion per cell the same run ends elsewhere
         if (prots_per_cell == 3) {
-            const State one = run(d_rests, true, 0, 1);
+            const Run one = run(d_rests, true, 0, 1);
             EXPECT(memcmp(one.X.data(), first.X.data(), counts[0] * sizeof(float3)) != 0);
         }
     }
@@ -265,9 +174,9 @@ int main()
         static_assert(ya::ens::whole_step_lanes_for(SMALL_N_MAX) == 4, "a stateless functor gets 4 lanes at 40 cells");
         static_assert(!ya::stateless_pair<float3, counting_spring, friction_w_neighbour<float3>>(), "not declared");
         static_assert(ya::stateless_pair<float3, plain_spring, friction_w_neighbour<float3>>(), "declared");
-        const State twin = small_run<counting_spring>(d_rests, false);
-        const State counting = small_run<counting_spring>(d_rests, true);
-        const State plain = small_run<plain_spring>(d_rests, true);
+        const Run twin = small_run<counting_spring>(d_rests, false);
+        const Run counting = small_run<counting_spring>(d_rests, true);
+        const Run plain = small_run<plain_spring>(d_rests, true);
         EXPECT(twin.launches == 0 && counting.launches == 5 && plain.launches == 5);
         EXPECT(counting.lanes_used == 1);
         EXPECT(plain.lanes_used == 4);

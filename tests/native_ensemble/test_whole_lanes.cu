@@ -9,31 +9,7 @@
 //   * ONE Ensemble alternates take_steps with 16 lanes per cell with take_step carrying Links, a kernel bumping
 //     d_n[r] in between, against a twin that only calls take_step.
 // Every comparison is of bit patterns.
-#include "../../include/dtypes.cuh"
-#include "../../include/inits.cuh"
-#include "../../include/links.cuh"
-#include "../../include/property.cuh"
-#include "../../include/solvers.cuh"
-#include "../../include/ensemble.cuh"
-
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-static int failures = 0;
-#define EXPECT(cond)                                                  \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);   \
-            failures++;                                               \
-        }                                                             \
-    } while (0)
-
-static float next_float(unsigned& s)
-{
-    s = s * 1664525u + 1013904223u;
-    return (float)(s >> 8) / 16777216.f;
-}
+#include "support.cuh"
 
 // ---- 1. which lanes called the functor ---------------------------------------------------------------------------
 __device__ unsigned* d_lane_mask;  // [cell][8]: bit t of a cell's 256 = thread t of a workgroup called the functor for it
@@ -89,8 +65,6 @@ static void lanes_case(const int n_max, const int setting, const int expected)
 }
 
 // ---- 2. per-cell state without atomics: one lane per cell under the default -------------------------------------------
-__device__ int* d_n_nbs;
-
 __device__ float3 counting_spring(float3 Xi, float3 r, float dist, int i, int j)
 {
     float3 dF{0.f, 0.f, 0.f};
@@ -121,7 +95,7 @@ static Counted counting_run(const bool whole)
     Property<int> nbs{M * N_MAX, "n_nbs"};
     for (int i = 0; i < M * N_MAX; i++) nbs.h_prop[i] = 0;
     nbs.copy_to_device();
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_n_nbs), &nbs.d_prop, sizeof(nbs.d_prop));
+    point_model_at(nullptr, nullptr, nbs.d_prop, N_MAX);
     EXPECT(cells.whole_step_lanes == 0);
     if (whole)
         cells.take_steps<counting_spring>(0.05f, 3);
@@ -213,41 +187,20 @@ static void pt8_case(const int n_max, const int lanes_expected)
 }
 
 // ---- 4. whole-step launches with 16 lanes per cell alternate with linked steps ------------------------------------
-__device__ const float* d_rest;
-__device__ int d_rows_per_replica;
-
 __device__ float3 sweep_spring(float3 Xi, float3 r, float dist, int i, int j)
 {
     float3 dF{0.f, 0.f, 0.f};
     if (i == j || dist >= 1.f) return dF;
-    const float L = d_rest[i / d_rows_per_replica];  // <- the sweep: this replica's parameter
+    const float L = d_sweep[i / d_rows_per_replica];  // <- the sweep: this replica's parameter
     return r * ((L - dist) / dist);
 }
 YA_STATELESS(float3, sweep_spring)
-
-__global__ void divide(int n_replicas, int n_max, float3* d_X, float3* d_old_v, int* d_n)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_replicas || r % 2 != 0) return;
-    const int n = d_n[r];
-    if (n <= 0 || n >= n_max) return;
-    const size_t base = (size_t)r * n_max;
-    const size_t mother = base + 3 % n, daughter = base + n;
-    d_X[daughter] = float3{d_X[mother].x + 0.05f, d_X[mother].y - 0.03f, d_X[mother].z + 0.02f};
-    d_old_v[daughter] = d_old_v[mother];
-    d_n[r] = n + 1;
-}
 
 constexpr int M = 7, N_MAX = 130;
 static const int counts[M] = {100, 0, 64, 17, 97, 3, 128};  // (128 + 2 daughters: the replica ends full)
 static const float rests[M] = {0.5f, 0.55f, 0.6f, 0.65f, 0.7f, 0.75f, 0.8f};
 
-struct State {
-    std::vector<float3> X, v;
-    std::vector<int> n;
-    long launches;
-};
-static State alternating_run(const float* d_rests, const bool whole, const int fixed_mode)
+static Run alternating_run(const float* d_rests, const bool whole, const int fixed_mode)
 {
     Ensemble<float3> cells{M, N_MAX};
     cells.whole_steps = whole ? 1 : -1;
@@ -255,24 +208,17 @@ static State alternating_run(const float* d_rests, const bool whole, const int f
     cells.steps_per_launch = 2;
     for (int r = 0; r < M; r++) {
         cells.h_n[r] = counts[r];
-        unsigned s = 4321u + 977u * (unsigned)r;
-        const float side = 1.f + 0.012f * (float)counts[r];
-        for (int i = 0; i < counts[r]; i++)
-            *cells.row(r, i) = float3{side * next_float(s), side * next_float(s), side * next_float(s)};
+        seed_rows(r, counts[r], cells.row(r, 0));
     }
     cells.copy_to_device();
-    // links (2k, 2k + 1) of a replica: every cell in at most one link, so the order of link_forces' atomic adds
-    // cannot matter
     Links links{M * N_MAX, 0.3f};
     int n_links = 0;
     for (int r = 0; r < M; r++)
-        for (int k = 0; k < counts[r] / 4; k++)
+        for (int k = 0; k < n_links_of(counts[r]); k++)
             links.h_link[n_links++] = Link{(int)cells.index(r, 2 * k), (int)cells.index(r, 2 * k + 1)};
     *links.h_n = n_links;
     links.copy_to_device();
-    int rows_per_replica = N_MAX;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rest), &d_rests, sizeof(d_rests));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rows_per_replica), &rows_per_replica, sizeof(int));
+    point_model_at(d_rests, nullptr, nullptr, N_MAX);
 
     if (fixed_mode == 1) cells.set_fixed(2);
     if (fixed_mode == 2) cells.set_fixed_xy(1);
@@ -295,14 +241,7 @@ static State alternating_run(const float* d_rests, const bool whole, const int f
     quiet(0.05f, 2);  // 1 launch
     if (whole) EXPECT(cells.whole_step_lanes_used == 16);
 
-    State out;
-    cells.copy_to_host();
-    out.X.assign(cells.h_X, cells.h_X + M * N_MAX);
-    out.v.resize(M * N_MAX);
-    (void)hipMemcpy(out.v.data(), cells.d_old_v, out.v.size() * sizeof(float3), hipMemcpyDeviceToHost);
-    for (int r = 0; r < M; r++) out.n.push_back(cells.h_n[r]);
-    out.launches = cells.whole_step_launches;
-    return out;
+    return read_back(cells);
 }
 
 int main()
@@ -348,12 +287,10 @@ int main()
 
     // 4. alternation, in all three fixed modes
     {
-        float* d_rests;
-        (void)hipMalloc(&d_rests, sizeof(rests));
-        (void)hipMemcpy(d_rests, rests, sizeof(rests), hipMemcpyHostToDevice);
+        float* d_rests = on_device(rests, M);
         for (int fixed_mode : {0, 1, 2}) {
-            const State twin = alternating_run(d_rests, false, fixed_mode);
-            const State mixed = alternating_run(d_rests, true, fixed_mode);
+            const Run twin = alternating_run(d_rests, false, fixed_mode);
+            const Run mixed = alternating_run(d_rests, true, fixed_mode);
             EXPECT(twin.launches == 0);
             EXPECT(mixed.launches == 2 + 1 + 3 + 1);
             for (int r = 0; r < M; r++) {

@@ -8,89 +8,24 @@
 //     whose right-hand sides must be zeroed again after the launches that never touched them.
 // Everything -- positions, old_v, counts, the neighbour counters -- is compared bit for bit with a twin Ensemble
 // that only ever calls take_step, with the centre of mass fixed, a point fixed and after set_fixed_xy.
-#include "../../include/dtypes.cuh"
-#include "../../include/inits.cuh"
-#include "../../include/links.cuh"
-#include "../../include/property.cuh"
-#include "../../include/solvers.cuh"
-#include "../../include/ensemble.cuh"
+#include "support.cuh"
 
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-static int failures = 0;
-#define EXPECT(cond)                                                  \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);   \
-            failures++;                                               \
-        }                                                             \
-    } while (0)
-
-// the model's own arrays: one rest length per replica, one neighbour counter per cell (flat id space)
-__device__ const float* d_rest;
-__device__ int* d_n_nbs;
-__device__ int d_rows_per_replica;
-
-__device__ float3 counting_spring(float3 Xi, float3 r, float dist, int i, int j)
-{
-    float3 dF{0.f, 0.f, 0.f};
-    if (i == j || dist >= 1.f) return dF;
-    d_n_nbs[i] += 1;                                  // <- per-cell state without atomics: one thread per cell
-    const float L = d_rest[i / d_rows_per_replica];   // <- the sweep: this replica's parameter
-    return r * ((L - dist) / dist);
-}
-
-// Replica r divides if r is even and it has room: cell 3 % n gets a daughter at row n, and d_n[r] grows -- on the
-// device, nothing travels.
-__global__ void divide(int n_replicas, int n_max, float3* d_X, float3* d_old_v, int* d_n)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_replicas || r % 2 != 0) return;
-    const int n = d_n[r];
-    if (n <= 0 || n >= n_max) return;
-    const size_t base = (size_t)r * n_max;
-    const size_t mother = base + 3 % n, daughter = base + n;
-    d_X[daughter] = float3{d_X[mother].x + 0.05f, d_X[mother].y - 0.03f, d_X[mother].z + 0.02f};
-    d_old_v[daughter] = d_old_v[mother];
-    d_n[r] = n + 1;
-}
+using by_rest::counting_spring;  // (support.cuh: reads d_sweep, counts in d_n_nbs)
 
 constexpr int M = 7, N_MAX = 520;
 static const int counts[M] = {300, 0, 64, 257, 129, 3, 518};   // (518 + 2 daughters: the replica ends full)
 static const float rests[M] = {0.5f, 0.55f, 0.6f, 0.65f, 0.7f, 0.75f, 0.8f};
 
-struct State {
-    std::vector<float3> X, v;
-    std::vector<int> n, nbs;
-    long launches;
-};
-
-static void seed_rows(int r, float3* rows)
-{
-    unsigned s = 4321u + 977u * (unsigned)r;
-    auto next = [&s]() {
-        s = s * 1664525u + 1013904223u;
-        return (float)(s >> 8) / 16777216.f;
-    };
-    const float side = 1.f + 0.012f * (float)counts[r];
-    for (int i = 0; i < counts[r]; i++) rows[i] = float3{side * next(), side * next(), side * next()};
-}
-// links (2k, 2k + 1) of a replica: every cell in at most one link, so the atomic adds of link_forces have one
-// term per row and their order cannot matter
-static int n_links_of(int r) { return counts[r] / 4; }
-
 // The model's run.  whole: the quiet stretches are take_steps calls (whole_steps = 1, at most 2 steps per
 // launch); otherwise every step is a take_step (whole_steps = -1 for good measure).
-static State run(const float* d_rests, const bool whole, const int fixed_mode)
+static Run run(const float* d_rests, const bool whole, const int fixed_mode)
 {
     Ensemble<float3> cells{M, N_MAX};
     cells.whole_steps = whole ? 1 : -1;
     cells.steps_per_launch = 2;
     for (int r = 0; r < M; r++) {
         cells.h_n[r] = counts[r];
-        seed_rows(r, cells.row(r, 0));
+        seed_rows(r, counts[r], cells.row(r, 0));
     }
     cells.copy_to_device();
     Property<int> nbs{M * N_MAX, "n_nbs"};
@@ -99,14 +34,11 @@ static State run(const float* d_rests, const bool whole, const int fixed_mode)
     Links links{M * N_MAX, 0.3f};
     int n_links = 0;
     for (int r = 0; r < M; r++)
-        for (int k = 0; k < n_links_of(r); k++)
+        for (int k = 0; k < n_links_of(counts[r]); k++)
             links.h_link[n_links++] = Link{(int)cells.index(r, 2 * k), (int)cells.index(r, 2 * k + 1)};
     *links.h_n = n_links;
     links.copy_to_device();
-    int rows_per_replica = N_MAX;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rest), &d_rests, sizeof(d_rests));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_n_nbs), &nbs.d_prop, sizeof(nbs.d_prop));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rows_per_replica), &rows_per_replica, sizeof(int));
+    point_model_at(d_rests, nullptr, nbs.d_prop, N_MAX);
 
     if (fixed_mode == 1) cells.set_fixed(2);
     if (fixed_mode == 2) cells.set_fixed_xy(1);
@@ -134,31 +66,17 @@ static State run(const float* d_rests, const bool whole, const int fixed_mode)
     else
         for (int s = 0; s < 2; s++) linked(0.05f);
 
-    State out;
-    cells.copy_to_host();
-    out.X.assign(cells.h_X, cells.h_X + M * N_MAX);
-    out.v.resize(M * N_MAX);
-    (void)hipMemcpy(out.v.data(), cells.d_old_v, out.v.size() * sizeof(float3), hipMemcpyDeviceToHost);
-    nbs.copy_to_host();
-    out.nbs.assign(nbs.h_prop, nbs.h_prop + M * N_MAX);
-    for (int r = 0; r < M; r++) {
-        out.n.push_back(cells.h_n[r]);
-        EXPECT(cells.get_d_n(r) == cells.h_n[r]);
-    }
-    out.launches = cells.whole_step_launches;
-    return out;
+    return read_back(cells, &nbs);
 }
 
 int main()
 {
     static_assert(ya::ens::whole_step_capacity<float3>() == 1024, "float3 replicas of up to 1024 cells fit");
     static_assert(ya::ens::whole_step_capacity<float4>() == 1024, "float4 too");
-    float* d_rests;
-    (void)hipMalloc(&d_rests, sizeof(rests));
-    (void)hipMemcpy(d_rests, rests, sizeof(rests), hipMemcpyHostToDevice);
+    float* d_rests = on_device(rests, M);
     for (int fixed_mode : {0, 1, 2}) {
-        const State twin = run(d_rests, false, fixed_mode);
-        const State mixed = run(d_rests, true, fixed_mode);
+        const Run twin = run(d_rests, false, fixed_mode);
+        const Run mixed = run(d_rests, true, fixed_mode);
         EXPECT(twin.launches == 0);
         EXPECT(mixed.launches == 2 + 1 + 3 + 1);
         for (int r = 0; r < M; r++) {
@@ -179,10 +97,8 @@ int main()
         float swapped[M];
         memcpy(swapped, rests, sizeof(rests));
         swapped[0] = rests[4];
-        float* d_swapped;
-        (void)hipMalloc(&d_swapped, sizeof(swapped));
-        (void)hipMemcpy(d_swapped, swapped, sizeof(swapped), hipMemcpyHostToDevice);
-        const State a = run(d_rests, true, 0), b = run(d_swapped, true, 0);
+        float* d_swapped = on_device(swapped, M);
+        const Run a = run(d_rests, true, 0), b = run(d_swapped, true, 0);
         EXPECT(memcmp(a.X.data(), b.X.data(), counts[0] * sizeof(float3)) != 0);
         EXPECT(memcmp(a.X.data() + 2 * N_MAX, b.X.data() + 2 * N_MAX, counts[2] * sizeof(float3)) == 0);
         (void)hipFree(d_swapped);

@@ -2,62 +2,29 @@
 declares and the ctypes table mirrors, and refuses what it does not know (no compute calls here)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
+from ensemble_support import ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble.so")
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ya_[A-Za-z0-9_]+)\s*\(", text)))
-
-
-def built(path):
-    if not os.path.exists(path):
-        import __graft_entry__
-        __graft_entry__.build()
-    return path
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", built(path)], capture_output=True, text=True, check=True).stdout
-    return [(line.split()[-2], line.split()[-1]) for line in out.splitlines() if line.strip()]
 
 
 def test_header_table_and_library_agree():
     from yalla_amd import _ffi
-    names = declared_functions("yalla_ensemble.h")
-    assert len(names) == 17 and all(n.startswith("ya_ens_") for n in names)
-    assert set(names) == set(_ffi.ENSEMBLE_ABI), "ctypes table and header disagree"
-    functions = {sym for kind, sym in exported(LIB) if kind == "T" and sym.startswith("ya_")}
-    assert functions == set(names), "library and header disagree"
-    lib = _ffi.ensemble_lib()  # types every entry point; AttributeError if one is missing
-    assert lib is _ffi.ensemble_lib()
+    check_abi("yalla_ensemble.h", "ya_ens_", _ffi.ENSEMBLE_ABI, LIB, _ffi.ensemble_lib, 17, set())
     assert _ffi.ENSEMBLE_LIB == LIB
 
 
 def test_only_the_ensemble_c_abi_is_exported():
-    """-fvisibility=hidden: nothing but ya_ens_* and the HIP registration symbols (fatbin wrapper, kernel
-    handles and stubs' data) leaves the library -- no engine or harness C++ symbol, and no ya_sim_* / ya_models_*
-    entry point of the model harness."""
-    for kind, sym in exported(LIB):
-        if sym.startswith("ya_ens_") or sym.startswith("__hip") or kind in ("V", "D", "B", "R"):
-            continue
-        raise AssertionError(f"{kind} {sym}")
-    assert not [sym for _, sym in exported(LIB) if sym.startswith("ya_") and not sym.startswith("ya_ens_")]
+    """No ya_sim_* / ya_models_* entry point of the model harness either."""
+    check_only_the_c_abi_is_exported(LIB, "ya_ens_")
 
 
 def test_the_model_table():
     from yalla_amd import ensemble
     names = ensemble.models()
     assert names == ["springs", "clipped", "fading", "relu", "relu_po", "oscillator", "push"]
-    lib = ensemble._ffi.ensemble_lib()
-    assert lib.ya_ens_models_name(-1) is None and lib.ya_ens_models_name(len(names)) is None
+    check_models_name_bounds(ensemble._ffi.ensemble_lib().ya_ens_models_name, len(names))
 
 
 def test_unknown_models_and_bad_sizes_are_refused_before_the_device_is_touched():

@@ -2,39 +2,20 @@
 header declares and the ctypes table mirrors, and refuses what it does not know (no compute calls here)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
+from ensemble_support import (ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported,
+                              declared_functions)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble_gabriel.so")
 MODELS = ["relu", "clipped", "relu_plain", "relu_po", "relu_cell", "clipped_push"]
 
 
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ya_[A-Za-z0-9_]+)\s*\(", text)))
-
-
-def built(path):
-    if not os.path.exists(path):
-        import __graft_entry__
-        __graft_entry__.build()
-    return path
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", built(path)], capture_output=True, text=True, check=True).stdout
-    return [(line.split()[-2], line.split()[-1]) for line in out.splitlines() if line.strip()]
-
-
 def test_header_table_and_library_agree():
     from yalla_amd import _ffi
-    names = declared_functions("yalla_ensemble_gabriel.h")
-    assert len(names) == 21 and all(n.startswith("ya_gabens_") for n in names)
-    assert set(names) == set(_ffi.GABRIEL_ENSEMBLE_ABI), "ctypes table and header disagree"
+    names = check_abi("yalla_ensemble_gabriel.h", "ya_gabens_", _ffi.GABRIEL_ENSEMBLE_ABI, LIB,
+                      _ffi.gabriel_ensemble_lib, 21,
+                      {"ya_gabens_set_cube_size", "ya_gabens_status", "ya_gabens_get_grid", "ya_gabens_dense_cells"})
     # the grid harness's twenty functions, and dense_cells
     from_grid = {n.replace("ya_gens_", "ya_gabens_") for n in declared_functions("yalla_ensemble_grid.h")}
     assert len(from_grid) == 20 and set(names) - from_grid == {"ya_gabens_dense_cells"}
@@ -42,21 +23,11 @@ def test_header_table_and_library_agree():
     grid_args = _ffi.GRID_ENSEMBLE_ABI["ya_gens_create"][1]
     args = _ffi.GABRIEL_ENSEMBLE_ABI["ya_gabens_create"][1]
     assert args == grid_args[:-1] + [ctypes.c_float] + grid_args[-1:]
-    functions = {sym for kind, sym in exported(LIB) if kind == "T" and sym.startswith("ya_")}
-    assert functions == set(names), "library and header disagree"
-    lib = _ffi.gabriel_ensemble_lib()  # types every entry point; AttributeError if one is missing
-    assert lib is _ffi.gabriel_ensemble_lib()
     assert _ffi.GABRIEL_ENSEMBLE_LIB == LIB
 
 
 def test_only_the_gabriel_ensemble_c_abi_is_exported():
-    """-fvisibility=hidden: nothing but ya_gabens_* and the HIP registration symbols (fatbin wrapper, kernel handles
-    and stubs' data) leaves the library -- no engine or harness C++ symbol, no entry point of another harness."""
-    for kind, sym in exported(LIB):
-        if sym.startswith("ya_gabens_") or sym.startswith("__hip") or kind in ("V", "D", "B", "R"):
-            continue
-        raise AssertionError(f"{kind} {sym}")
-    assert not [sym for _, sym in exported(LIB) if sym.startswith("ya_") and not sym.startswith("ya_gabens_")]
+    check_only_the_c_abi_is_exported(LIB, "ya_gabens_")
 
 
 def test_the_model_table():
@@ -64,8 +35,7 @@ def test_the_model_table():
     assert issubclass(GabrielEnsemble, GridEnsemble)   # grid(r), status(r) and the cube_size setter come with it
     names = ensemble.gabriel_models()
     assert names == MODELS
-    lib = ensemble._ffi.gabriel_ensemble_lib()
-    assert lib.ya_gabens_models_name(-1) is None and lib.ya_gabens_models_name(len(names)) is None
+    check_models_name_bounds(ensemble._ffi.gabriel_ensemble_lib().ya_gabens_models_name, len(names))
 
 
 def test_unknown_models_bad_sizes_and_bad_values_are_refused_before_the_device_is_touched():

@@ -18,6 +18,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gabriel_statement as gab  # noqa: E402
+from ensemble_support import DT, Lockstep, bits, compare, seeded_rows  # noqa: E402
 from test_gabriel import clusters, fine_lattice, hexagon, lattice, random_260, widened  # noqa: E402
 
 from yalla_amd.ensemble import GabrielEnsemble, gabriel_models  # noqa: E402
@@ -27,38 +28,12 @@ pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 MODELS = ["relu", "clipped", "relu_plain", "relu_po", "relu_cell", "clipped_push"]
-DT = 0.05
 CAP = 64   # GABRIEL_CAP: candidates of a cell the LDS list holds
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def same_grid(mine, theirs, n):
-    """cube_id[:n], point_id[:n], and every cube's cube_start and cube_end"""
-    return (np.array_equal(mine[0][:n], theirs[0][:n]) and np.array_equal(mine[1][:n], theirs[1][:n])
-            and np.array_equal(mine[2], theirs[2]) and np.array_equal(mine[3], theirs[3]))
 
 
 def lone_first(X):
     """The input with its last row, the lone cell, first (this file's docstring)."""
     return np.ascontiguousarray(np.roll(np.asarray(X, f32), 1, axis=0))
-
-
-def seeded_rows(n, seed, n_floats=3):
-    """n points uniform in a ball of random_sphere(0.75)'s density, the first one moved far away: a lone cell."""
-    rng = np.random.default_rng(seed)
-    rows = np.zeros((n, n_floats), f32)
-    if n == 0:
-        return rows
-    direction = rng.normal(size=(n, 3))
-    direction /= np.linalg.norm(direction, axis=1)[:, None]
-    radius = 0.75 * (n / 0.64) ** (1 / 3) / 2 * rng.random(n) ** (1 / 3)
-    rows[:, :3] = (direction * radius[:, None]).astype(f32)
-    rows[:, 3:] = rng.random((n, n_floats - 3)).astype(f32)
-    rows[0, :3] = rows[:, :3].max(axis=0) + 3.0
-    return rows
 
 
 def seeded_old_v(m, n_max, seed=5):
@@ -89,78 +64,26 @@ def n_dense(X, gs):
     return int(((ids >= 0).sum(axis=1) > CAP).sum())
 
 
-class Lockstep:
-    """A GabrielEnsemble and one Solution per compared replica, fed the same rows, old_v and settings."""
+class GabrielLockstep(Lockstep):
+    """A GabrielEnsemble and one Solution per compared replica, fed the same rows (given, not seeded), old_v, Gabriel
+    coefficient and fixed cell; the four grid arrays are part of every result."""
 
     def __init__(self, model, rows, n_max, grid_size, cube_size=1.0, coefficient=0.8, singles=None,
                  single_model=None, old_v=None, fixed=0):
-        self.model, self.n_max, self.grid_size = model, n_max, grid_size
-        self.counts = [len(X) for X in rows]
-        self.ens = GabrielEnsemble(model, len(rows), n_max, grid_size, cube_size, coefficient)
-        self.which = list(range(len(rows))) if singles is None else list(singles)
-        name = (single_model or model) + "_gabriel"
-        self.single = {r: Solution(name, n_max, grid_size, cube_size) for r in self.which}
-        for r, X in enumerate(rows):
-            self.ens.h_X[r, :len(X)] = X
-            self.ens.h_n[r] = len(X)
-            if r in self.single:
-                self.single[r].h_X[:len(X)] = X
-                self.single[r].h_n = len(X)
-        self.each(lambda s: s.copy_to_device())
+        super().__init__(GabrielEnsemble, "_gabriel", model, [len(X) for X in rows], n_max, (grid_size, cube_size),
+                         ens_args=(coefficient,), grids=True, singles=singles, rows=rows, single_model=single_model)
+        self.grid_size = grid_size
         for s in self.single.values():
             s.set_param("gabriel_coefficient", coefficient)
         if old_v is not None:
-            self.ens.set_old_v(old_v)
-            for r, s in self.single.items():
-                s.set_old_v(old_v[r])
+            self.set_old_v(old_v)
         if fixed is not None:
             self.each(lambda s: s.set_fixed(fixed))
-
-    def each(self, call):
-        call(self.ens)
-        for s in self.single.values():
-            call(s)
-
-    def step(self, dt, steps=1):
-        self.each(lambda s: s.take_step(dt, steps))
 
     def set_coefficient(self, coefficient):
         self.ens.gabriel_coefficient = coefficient
         for s in self.single.values():
             s.set_param("gabriel_coefficient", coefficient)
-
-    def set_cube_size(self, cube_size):
-        def assign(s):
-            s.cube_size = cube_size
-        self.each(assign)
-
-    def results(self):
-        out = {}
-        for r, s in self.single.items():
-            n = self.counts[r]
-            assert s.h_n == n
-            out[r] = (bits(s.positions()).copy(), bits(s.old_v()[:n]).copy(), s.grid())
-        return out
-
-    def check(self, what=""):
-        compare(self.ens, self.counts, self.results(), (what, self.model))
-
-    def close(self):
-        self.ens.close()
-        for s in self.single.values():
-            s.close()
-
-
-def compare(ens, counts, reference, what=""):
-    """The ensemble's replicas against `reference` (Lockstep.results): positions, old_v and the four grid arrays."""
-    ens.copy_to_host()
-    v = ens.old_v()
-    for r, (X, old_v, grid) in reference.items():
-        n = counts[r]
-        assert ens.h_n[r] == n and ens.get_d_n(r) == n, (what, r)
-        assert np.array_equal(bits(ens.h_X[r, :n]), X), (what, "positions of replica", r, n)
-        assert np.array_equal(bits(v[r, :n]), old_v), (what, "old_v of replica", r, n)
-        assert same_grid(ens.grid(r), grid, n), (what, "grid arrays of replica", r, n)
 
 
 def test_the_models_are_those_of_the_gabriel_harness():
@@ -186,7 +109,7 @@ def test_the_mixed_ensemble_is_its_single_systems_bit_for_bit(model, coefficient
     rows = mixed_rows()
     n_max = len(clusters()[0])
     assert n_max == 3427
-    run = Lockstep(model, rows, n_max, MIXED_GS, coefficient=coefficient, old_v=seeded_old_v(len(rows), n_max))
+    run = GabrielLockstep(model, rows, n_max, MIXED_GS, coefficient=coefficient, old_v=seeded_old_v(len(rows), n_max))
     try:
         assert run.ens.dense_cells() == 0   # (nothing stepped yet)
         run.step(DT, 3)
@@ -233,14 +156,14 @@ def test_a_right_hand_side_against_the_numpy_statement(model):
 
 def test_ragged_counts_around_the_workgroup_of_four_cells():
     sizes = [0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65]
-    rows = [seeded_rows(n, 300 + r) for r, n in enumerate(sizes)]
-    run = Lockstep("relu", rows, 65, 12, old_v=seeded_old_v(len(sizes), 65))
+    rows = [seeded_rows(3, n, 300 + r, lone=True) for r, n in enumerate(sizes)]
+    run = GabrielLockstep("relu", rows, 65, 12, old_v=seeded_old_v(len(sizes), 65))
     try:
         run.step(DT, 3)
         run.check("M = 12")
     finally:
         run.close()
-    run = Lockstep("clipped", [seeded_rows(800, 17)], 800, 16, old_v=seeded_old_v(1, 800))
+    run = GabrielLockstep("clipped", [seeded_rows(3, 800, 17, lone=True)], 800, 16, old_v=seeded_old_v(1, 800))
     try:
         run.step(DT, 3)
         run.check("M = 1")
@@ -255,7 +178,7 @@ def test_wide_point_types(model):
     rows = [lone_first(widened(random_260()[0], wide)), np.zeros((0, gab.WIDTH[wide]), f32),
             lone_first(widened(clusters()[0], wide, seed=10))]
     n_max = len(rows[2])
-    run = Lockstep(model, rows, n_max, MIXED_GS, old_v=seeded_old_v(3, n_max))
+    run = GabrielLockstep(model, rows, n_max, MIXED_GS, old_v=seeded_old_v(3, n_max))
     try:
         run.step(DT, 3)
         run.check()
@@ -306,8 +229,8 @@ def test_a_generic_force_beside_the_pairwise_one():
 
 def test_all_three_fixed_modes():
     """set_fixed() first (the default), set_fixed(i), set_fixed_xy(i) followed by steps, and back."""
-    rows = [seeded_rows(n, 500 + r) for r, n in enumerate([300, 70, 0, 64, 257, 5])]
-    run = Lockstep("clipped", rows, 300, 16, fixed=None)
+    rows = [seeded_rows(3, n, 500 + r, lone=True) for r, n in enumerate([300, 70, 0, 64, 257, 5])]
+    run = GabrielLockstep("clipped", rows, 300, 16, fixed=None)
     try:
         run.step(DT, 2)
         run.check("set_fixed()")
@@ -330,10 +253,11 @@ def test_all_three_fixed_modes():
 def test_settings_changed_between_steps():
     """gabriel_coefficient and cube_size changed on a live ensemble: the change is visible (the step differs from
     that of an ensemble left alone) and there is no stale step (the singles, changed alike, agree)."""
-    rows = [lone_first(random_260()[0]), np.zeros((0, 3), f32), lone_first(clusters(64)[0]), seeded_rows(200, 8)]
+    rows = [lone_first(random_260()[0]), np.zeros((0, 3), f32), lone_first(clusters(64)[0]),
+            seeded_rows(3, 200, 8, lone=True)]
     n_max = max(len(X) for X in rows)
-    run = Lockstep("relu", rows, n_max, MIXED_GS)
-    alone = Lockstep("relu", rows, n_max, MIXED_GS, singles=[])
+    run = GabrielLockstep("relu", rows, n_max, MIXED_GS)
+    alone = GabrielLockstep("relu", rows, n_max, MIXED_GS, singles=[])
     try:
         run.step(DT, 2)
         alone.step(DT, 2)
@@ -439,7 +363,7 @@ def test_grid_faces_do_not_leak_into_the_next_replica():
     for X in rows:
         assert X.min() < -2.99 and X.min() > -3 and X.max() < 3
     n_max = max(len(X) for X in rows)
-    run = Lockstep("clipped", rows, n_max, 6)
+    run = GabrielLockstep("clipped", rows, n_max, 6)
     try:
         run.step(DT, 3)
         for r in range(3):
@@ -452,9 +376,9 @@ def test_grid_faces_do_not_leak_into_the_next_replica():
 def test_a_replica_that_leaves_its_grid_is_reported_and_harms_nobody():
     counts = [100, 64, 257, 30]
     bad = 2
-    rows = [seeded_rows(n, 90 + r) for r, n in enumerate(counts)]
+    rows = [seeded_rows(3, n, 90 + r, lone=True) for r, n in enumerate(counts)]
     rows[bad][5] = (0.0, 0.0, 100.0)  # far above the 12^3 grid: its cube id is past the last cube's
-    run = Lockstep("relu", rows, 300, 12, singles=[r for r in range(len(counts)) if r != bad])
+    run = GabrielLockstep("relu", rows, 300, 12, singles=[r for r in range(len(counts)) if r != bad])
     try:
         run.step(DT, 1)
         for r in range(len(counts)):

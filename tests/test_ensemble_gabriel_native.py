@@ -1,21 +1,8 @@
 """Ensemble<Pt, Gabriel_solver> as a model program uses the header
-(tests/native_ensemble_gabriel/test_ensemble_gabriel.cu, built by its own Makefile -- __graft_entry__.build() does
+(tests/native_ensemble/test_ensemble_gabriel.cu, built by that directory's Makefile -- __graft_entry__.build() does
 it -- and run here on the GPU)."""
-import os
-import subprocess
-
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native_ensemble_gabriel")
-
-
-def run(name, marker, args=(), cwd=None):
-    exe = os.path.join(NATIVE, name)
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", NATIVE, name], check=True, capture_output=True)
-    proc = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300, cwd=cwd)
-    assert proc.returncode == 0 and marker in proc.stdout, proc.stdout[-2000:] + proc.stderr[-2000:]
+from ensemble_support import run_native
 
 
 @pytest.mark.gpu
@@ -26,4 +13,4 @@ def test_a_gabriel_sweep_written_against_the_header():
     are the generic forces, a kernel divides cells of some replicas by raising d_n[r] on the device between steps,
     one replica is dense -- every replica memcmp-equal to a Solution<float3, Gabriel_solver> run of the same system,
     with the centre of mass fixed and after set_fixed_xy."""
-    run("test_ensemble_gabriel", "ALL GABRIEL ENSEMBLE TESTS PASSED")
+    run_native("test_ensemble_gabriel", "ALL GABRIEL ENSEMBLE TESTS PASSED")

@@ -2,8 +2,12 @@
 sequence.  THE REFERENCE of every comparison is the existing single-system path -- a Solution("<model>_tile",
 n_max) per replica given the same rows, the same old_v and the same settings -- and every comparison is of bit
 patterns (uint32, array_equal): no tolerance anywhere."""
+import functools
+
 import numpy as np
 import pytest
+from ensemble_support import DT, bits, seeded_rows
+from ensemble_support import Lockstep as AnyLockstep
 
 from yalla_amd.ensemble import Ensemble, models
 from yalla_amd.solution import Solution
@@ -13,99 +17,14 @@ pytestmark = pytest.mark.gpu
 MODELS = ["springs", "clipped", "fading", "relu", "relu_po", "oscillator", "push"]
 # a partial wavefront, exactly one tile of 64 / 256, more than one tile, B_r = 1, 2, 4, 6 partial-sum blocks
 SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 800, 1500]
-DT = 0.05
+# An Ensemble and one Solution("<model>_tile", n_max) per replica: (model, counts, n_max, seed=0, singles=None).  A
+# check compares h_n, get_d_n, positions and old_v[:n].
+Lockstep = functools.partial(AnyLockstep, Ensemble, "_tile")
 
 
 def counts_for(m):
     """Ragged counts out of SIZES: 800 for a lone replica, every size once M >= 10."""
     return [SIZES[(3 * r + 8) % len(SIZES)] for r in range(m)]
-
-
-def seeded_rows(n_floats, n, seed):
-    """random_sphere-like: n points uniform in a ball whose density is that of random_sphere(0.75); further
-    components (w, theta / phi) uniform in [0, 1)."""
-    rng = np.random.default_rng(seed)
-    rows = np.zeros((n, n_floats), dtype=np.float32)
-    if n == 0:
-        return rows
-    direction = rng.normal(size=(n, 3))
-    direction /= np.linalg.norm(direction, axis=1)[:, None]
-    radius = 0.75 * (n / 0.64) ** (1 / 3) / 2 * rng.random(n) ** (1 / 3)
-    rows[:, :3] = (direction * radius[:, None]).astype(np.float32)
-    rows[:, 3:] = rng.random((n, n_floats - 3)).astype(np.float32)
-    return rows
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-class Lockstep:
-    """An Ensemble and one Solution per replica, fed the same rows, old_v and settings."""
-
-    def __init__(self, model, counts, n_max, seed=0, singles=None):
-        self.model, self.n_max = model, n_max
-        self.ens = Ensemble(model, len(counts), n_max)
-        self.which = list(range(len(counts))) if singles is None else list(singles)
-        self.single = {r: Solution(model + "_tile", n_max) for r in self.which}
-        self.counts = list(counts)
-        for r, n in enumerate(counts):
-            rows = seeded_rows(self.ens.n_floats, n, 1000 * seed + r)
-            self.ens.h_X[r, :n] = rows
-            self.ens.h_n[r] = n
-            if r in self.single:
-                self.single[r].h_X[:n] = rows
-                self.single[r].h_n = n
-        self.ens.copy_to_device()
-        for s in self.single.values():
-            s.copy_to_device()
-
-    def each(self, call):
-        call(self.ens)
-        for s in self.single.values():
-            call(s)
-
-    def step(self, dt, steps=1):
-        self.each(lambda s: s.take_step(dt, steps))
-
-    def set_old_v(self, v):
-        """v: (n_replicas, n_max, 3)"""
-        self.ens.set_old_v(v)
-        for r, s in self.single.items():
-            s.set_old_v(v[r])
-
-    def set_counts(self, new):
-        """h_n[r] changed on the host: the rows travel with it, as copy_to_device moves them (both sides hold
-        the same rows, a replica that grows gets fresh ones at its end)."""
-        self.ens.copy_to_host()
-        for r, s in self.single.items():
-            s.copy_to_host()
-        for r, n in new.items():
-            grown = seeded_rows(self.ens.n_floats, max(n - self.counts[r], 0), 77 + r)
-            self.ens.h_X[r, self.counts[r]:n] = grown
-            self.ens.h_n[r] = n
-            if r in self.single:
-                self.single[r].h_X[self.counts[r]:n] = grown
-                self.single[r].h_n = n
-            self.counts[r] = n
-        self.ens.copy_to_device()
-        for s in self.single.values():
-            s.copy_to_device()
-
-    def check(self, what=""):
-        self.ens.copy_to_host()
-        v = self.ens.old_v()
-        for r, s in self.single.items():
-            n = self.counts[r]
-            assert self.ens.h_n[r] == n == s.h_n and self.ens.get_d_n(r) == n, (what, r)
-            X = s.positions()
-            assert np.array_equal(bits(self.ens.h_X[r, :n]), bits(X)), (what, self.model, "positions of replica", r, n)
-            assert np.array_equal(bits(v[r, :n]), bits(s.old_v()[:n])), (what, self.model, "old_v of replica", r, n)
-
-    def close(self):
-        self.ens.close()
-        for s in self.single.values():
-            s.close()
 
 
 def test_the_models_are_those_of_the_tile_harness():

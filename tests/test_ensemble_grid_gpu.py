@@ -5,6 +5,8 @@ and every comparison is of bit patterns (uint32, array_equal): no tolerance anyw
 four grid arrays of every compared replica are compared."""
 import numpy as np
 import pytest
+from ensemble_support import DT, bits, compare, same_grid, seeded_rows
+from ensemble_support import Lockstep as AnyLockstep
 
 from yalla_amd.ensemble import GridEnsemble, grid_models
 from yalla_amd.solution import Solution
@@ -16,7 +18,6 @@ MODELS = ["springs", "clipped", "fading", "relu", "relu_po", "relu_cell", "push"
 # kernels' blocks), an empty replica, a lone cell
 SIZES = [0, 1, 15, 16, 17, 31, 33, 63, 64, 65, 255, 256, 257, 800, 1500]
 LANES = [0, 1, 4, 8, 16]
-DT = 0.05
 
 
 def counts_for(m):
@@ -24,120 +25,10 @@ def counts_for(m):
     return [SIZES[(r + 13) % len(SIZES)] for r in range(m)]
 
 
-def seeded_rows(n_floats, n, seed):
-    """random_sphere-like: n points uniform in a ball whose density is that of random_sphere(0.75); further
-    components (w, theta / phi, ...) uniform in [0, 1)."""
-    rng = np.random.default_rng(seed)
-    rows = np.zeros((n, n_floats), dtype=np.float32)
-    if n == 0:
-        return rows
-    direction = rng.normal(size=(n, 3))
-    direction /= np.linalg.norm(direction, axis=1)[:, None]
-    radius = 0.75 * (n / 0.64) ** (1 / 3) / 2 * rng.random(n) ** (1 / 3)
-    rows[:, :3] = (direction * radius[:, None]).astype(np.float32)
-    rows[:, 3:] = rng.random((n, n_floats - 3)).astype(np.float32)
-    return rows
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_grid(mine, theirs, n):
-    """cube_id[:n], point_id[:n], and every cube's cube_start and cube_end"""
-    return (np.array_equal(mine[0][:n], theirs[0][:n]) and np.array_equal(mine[1][:n], theirs[1][:n])
-            and np.array_equal(mine[2], theirs[2]) and np.array_equal(mine[3], theirs[3]))
-
-
-class Lockstep:
-    """A GridEnsemble and one Solution per replica, fed the same rows, old_v and settings."""
-
-    def __init__(self, model, counts, n_max, grid_size, cube_size=1.0, seed=0, singles=None, rows=None):
-        self.model, self.n_max = model, n_max
-        self.ens = GridEnsemble(model, len(counts), n_max, grid_size, cube_size)
-        self.which = list(range(len(counts))) if singles is None else list(singles)
-        self.single = {r: Solution(model + "_grid", n_max, grid_size, cube_size) for r in self.which}
-        self.counts = list(counts)
-        for r, n in enumerate(counts):
-            X = seeded_rows(self.ens.n_floats, n, 1000 * seed + r) if rows is None else rows[r]
-            self.ens.h_X[r, :n] = X
-            self.ens.h_n[r] = n
-            if r in self.single:
-                self.single[r].h_X[:n] = X
-                self.single[r].h_n = n
-        self.ens.copy_to_device()
-        for s in self.single.values():
-            s.copy_to_device()
-
-    def each(self, call):
-        call(self.ens)
-        for s in self.single.values():
-            call(s)
-
-    def step(self, dt, steps=1):
-        self.each(lambda s: s.take_step(dt, steps))
-
-    def set_old_v(self, v):
-        """v: (n_replicas, n_max, 3)"""
-        self.ens.set_old_v(v)
-        for r, s in self.single.items():
-            s.set_old_v(v[r])
-
-    def set_cube_size(self, cube_size):
-        def assign(s):
-            s.cube_size = cube_size
-        self.each(assign)
-
-    def set_sum_order(self, order):
-        self.each(lambda s: s.set_param("sum_order", order))
-
-    def set_counts(self, new):
-        """h_n[r] changed on the host: the rows travel with it, as copy_to_device moves them (both sides hold
-        the same rows, a replica that grows gets fresh ones at its end)."""
-        self.ens.copy_to_host()
-        for r, s in self.single.items():
-            s.copy_to_host()
-        for r, n in new.items():
-            grown = seeded_rows(self.ens.n_floats, max(n - self.counts[r], 0), 77 + r)
-            self.ens.h_X[r, self.counts[r]:n] = grown
-            self.ens.h_n[r] = n
-            if r in self.single:
-                self.single[r].h_X[self.counts[r]:n] = grown
-                self.single[r].h_n = n
-            self.counts[r] = n
-        self.ens.copy_to_device()
-        for s in self.single.values():
-            s.copy_to_device()
-
-    def results(self):
-        """Per compared replica: (positions, old_v[:n], grid arrays) of its Solution."""
-        out = {}
-        for r, s in self.single.items():
-            n = self.counts[r]
-            assert s.h_n == n
-            out[r] = (bits(s.positions()).copy(), bits(s.old_v()[:n]).copy(), s.grid())
-        return out
-
-    def check(self, what="", reference=None):
-        reference = self.results() if reference is None else reference
-        compare(self.ens, self.counts, reference, (what, self.model))
-
-    def close(self):
-        self.ens.close()
-        for s in self.single.values():
-            s.close()
-
-
-def compare(ens, counts, reference, what=""):
-    """The ensemble's replicas against `reference` (Lockstep.results): positions, old_v and the four grid arrays."""
-    ens.copy_to_host()
-    v = ens.old_v()
-    for r, (X, old_v, grid) in reference.items():
-        n = counts[r]
-        assert ens.h_n[r] == n and ens.get_d_n(r) == n, (what, r)
-        assert np.array_equal(bits(ens.h_X[r, :n]), X), (what, "positions of replica", r, n)
-        assert np.array_equal(bits(v[r, :n]), old_v), (what, "old_v of replica", r, n)
-        assert same_grid(ens.grid(r), grid, n), (what, "grid arrays of replica", r, n)
+def Lockstep(model, counts, n_max, grid_size, cube_size=1.0, **kw):
+    """A GridEnsemble and one Solution("<model>_grid", n_max, grid_size, cube_size) per replica; the four grid arrays
+    are part of every result."""
+    return AnyLockstep(GridEnsemble, "_grid", model, counts, n_max, (grid_size, cube_size), grids=True, **kw)
 
 
 def stepped_ensemble(model, counts, n_max, grid_size, lanes, dt, steps, seed=0, rows=None, cube_size=1.0):

@@ -4,66 +4,34 @@ arithmetic only -- with ya::ens::whole_step_links_lds_bytes, held here against a
 compute calls here)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
+from ensemble_support import (LDS, LINKED_MODELS, ROOT, STATIC_LDS, check_abi, check_models_name_bounds,
+                              check_only_the_c_abi_is_exported, largest_slots, links_lds_bytes, up16)
+from ensemble_support import LINKED_N_FLOATS as N_FLOATS
+from ensemble_support import links_binding as binding
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble_links.so")
-MODELS = ["links", "links4", "springs_links", "relu_links", "relu_po_links"]
-N_FLOATS = {"links": 3, "links4": 4, "springs_links": 3, "relu_links": 3, "relu_po_links": 5}
 LANES = [1, 4, 16, 64]
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ya_[A-Za-z0-9_]+)\s*\(", text)))
-
-
-def built(path):
-    if not os.path.exists(path):
-        import __graft_entry__
-        __graft_entry__.build()
-    return path
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", built(path)], capture_output=True, text=True, check=True).stdout
-    return [(line.split()[-2], line.split()[-1]) for line in out.splitlines() if line.strip()]
 
 
 def test_header_table_and_library_agree():
     from yalla_amd import _ffi
-    names = declared_functions("yalla_ensemble_links.h")
-    assert len(names) == 22 and all(n.startswith("ya_lens_") for n in names)
-    shared = {n.replace("ya_ens_", "ya_lens_") for n in declared_functions("yalla_ensemble.h")}
-    assert shared < set(names), "the shared entry points of the other harnesses"
-    assert set(names) - shared == {"ya_lens_h_link", "ya_lens_set_n_links", "ya_lens_get_n_links",
-                                   "ya_lens_whole_step_lanes_used", "ya_lens_lds_bytes"}
-    assert set(names) == set(_ffi.LINKED_ENSEMBLE_ABI), "ctypes table and header disagree"
-    functions = {sym for kind, sym in exported(LIB) if kind == "T" and sym.startswith("ya_")}
-    assert functions == set(names), "library and header disagree"
-    lib = _ffi.linked_ensemble_lib()  # types every entry point; AttributeError if one is missing
-    assert lib is _ffi.linked_ensemble_lib()
+    check_abi("yalla_ensemble_links.h", "ya_lens_", _ffi.LINKED_ENSEMBLE_ABI, LIB, _ffi.linked_ensemble_lib, 22,
+              {"ya_lens_h_link", "ya_lens_set_n_links", "ya_lens_get_n_links", "ya_lens_whole_step_lanes_used",
+               "ya_lens_lds_bytes"})
     assert _ffi.LINKED_ENSEMBLE_LIB == LIB
 
 
 def test_only_the_c_abi_is_exported():
-    for kind, sym in exported(LIB):
-        if sym.startswith("ya_lens_") or sym.startswith("__hip") or kind in ("V", "D", "B", "R"):
-            continue
-        raise AssertionError(f"{kind} {sym}")
-    assert not [sym for _, sym in exported(LIB) if sym.startswith("ya_") and not sym.startswith("ya_lens_")]
+    check_only_the_c_abi_is_exported(LIB, "ya_lens_")
 
 
 def test_the_model_table():
     from yalla_amd import ensemble
     names = ensemble.linked_models()
-    assert names == MODELS
-    lib = ensemble._ffi.linked_ensemble_lib()
-    assert lib.ya_lens_models_name(-1) is None and lib.ya_lens_models_name(len(names)) is None
+    assert names == ["links", "links4", "springs_links", "relu_links", "relu_po_links"] == LINKED_MODELS
+    check_models_name_bounds(ensemble._ffi.linked_ensemble_lib().ya_lens_models_name, len(names))
 
 
 def test_unknown_models_and_bad_arguments_are_refused_before_the_device_is_touched():
@@ -90,70 +58,7 @@ def test_unknown_models_and_bad_arguments_are_refused_before_the_device_is_touch
         LinkedEnsemble.lds_bytes("links", 100, 10, 2)
 
 
-# ---- ya::ens::whole_step_links_lds_bytes<Pt>(n_max, S, lanes), restated from the headers ---------------------------
-LDS, STATIC_LDS, MIN_TILE, MAX_TILE, BUDGET = 160 * 1024, 3 * 256 * 4, 16, 256, 32 * 1024
-
-
-def up16(x):
-    return -(-x // 16) * 16
-
-
-def part_base(n_floats, n_max, slots):
-    """Where the term buffer starts: the step's arrays (X, X1, dX, dX1, old_v; fold256's scratch; 4 partial sums),
-    16-byte aligned, then the incidence list of n_max + 1 offsets and 2 S entries, 16-byte aligned."""
-    whole = n_max * (4 * 4 * n_floats + 12) + n_floats * 256 * 4 + n_floats * 4 * 4
-    return up16(up16(whole) + 4 * (n_max + 1) + 8 * slots)
-
-
-def tile_of(n_floats, n_max, slots, lanes):
-    """(start, bytes per partner, tile length, which bound cut last) by the coop rule's statements, in their order,
-    behind that start: n_max rounded up to 4 (0); at most the longest tile (1); at most what the budget holds but no
-    less than the shortest tile where it cuts (2); at most the room left in the workgroup's LDS (3)."""
-    base = part_base(n_floats, n_max, slots)
-    per_partner = (256 // lanes) * (n_floats + 4) * 4
-    room = (LDS - STATIC_LDS - base) // per_partner // 4 * 4
-    budget = BUDGET // per_partner // 4 * 4
-    tile, which = -(-n_max // 4) * 4, 0
-    if tile > MAX_TILE:
-        tile, which = MAX_TILE, 1
-    if tile > budget:
-        tile, which = max(budget, MIN_TILE), 2
-    if tile > room:
-        tile, which = room, 3
-    return base, per_partner, tile, which
-
-
-def binding(n_floats, n_max, slots, lanes):
-    """What decides the answer: -2 = the list does not fit (0), -1 = the shortest tile does not fit beside it (0),
-    4 = one lane per cell (the list's end), 0 .. 3 = that bound of the tile length."""
-    base = part_base(n_floats, n_max, slots)
-    if base + STATIC_LDS > LDS:
-        return -2
-    if lanes == 1:
-        return 4
-    _, per_partner, _, which = tile_of(n_floats, n_max, slots, lanes)
-    if base + STATIC_LDS + MIN_TILE * per_partner > LDS:
-        return -1
-    return which
-
-
-def links_lds_bytes(n_floats, n_max, slots, lanes):
-    if binding(n_floats, n_max, slots, lanes) < 0:
-        return 0
-    base, per_partner, tile, _ = tile_of(n_floats, n_max, slots, lanes)
-    return base if lanes == 1 else base + tile * per_partner
-
-
-def largest_slots(n_floats, n_max, lanes=1):
-    """The largest S whose launch fits (the rule falls monotonically to 0 in S)."""
-    lo, hi = 0, LDS  # fits, does not
-    assert links_lds_bytes(n_floats, n_max, lo, lanes) > 0 and links_lds_bytes(n_floats, n_max, hi, lanes) == 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if links_lds_bytes(n_floats, n_max, mid, lanes) > 0 else (lo, mid)
-    return lo
-
-
+# ---- ya::ens::whole_step_links_lds_bytes<Pt>(n_max, S, lanes) against its restatement (ensemble_support) -------------
 def test_the_restated_rule():
     """What the header promises of the rule, on the restatement: 16-byte aligned, within the workgroup's LDS, the
     list's 4 (n_max + 1) + 8 S bytes behind the step's arrays, a tile of at least 4 partners where lanes fit."""

@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_ensemble_gpu import bits, seeded_rows  # noqa: E402
-from test_ensemble_links_abi import MODELS, N_FLOATS, largest_slots, links_lds_bytes  # noqa: E402
+from ensemble_support import DT, bits, largest_slots, links_lds_bytes, seeded_rows  # noqa: E402
+from ensemble_support import LINKED_MODELS as MODELS  # noqa: E402
+from ensemble_support import LINKED_N_FLOATS as N_FLOATS  # noqa: E402
 from test_reference_statement_numpy import f32, fma32  # noqa: E402
 
 from yalla_amd.ensemble import LinkedEnsemble, YallaError  # noqa: E402
@@ -23,7 +24,6 @@ from yalla_amd.solution import Solution  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DT = 0.05
 UNUSED = np.float32(-7.25)  # what unused rows hold, to be found again
 
 

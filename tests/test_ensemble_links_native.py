@@ -1,21 +1,8 @@
 """Ensemble<Pt, Tile_solver>::take_steps with ya::ens::Replica_links as a model program uses the header
-(tests/native_ensemble_links/test_links.cu, built by its own Makefile -- __graft_entry__.build() does it -- and run
+(tests/native_ensemble/test_links.cu, built by that directory's Makefile -- __graft_entry__.build() does it -- and run
 here on the GPU)."""
-import os
-import subprocess
-
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native_ensemble_links")
-
-
-def run(name, marker, args=(), cwd=None):
-    exe = os.path.join(NATIVE, name)
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", NATIVE, name], check=True, capture_output=True)
-    proc = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300, cwd=cwd)
-    assert proc.returncode == 0 and marker in proc.stdout, proc.stdout[-2000:] + proc.stderr[-2000:]
+from ensemble_support import run_native
 
 
 @pytest.mark.gpu
@@ -29,4 +16,4 @@ def test_a_protrusion_sweep_whole_against_the_six_launch_ordered_twin():
     modes.  Then replicas of at most 40 cells under the default lanes, where the rule gives a stateless functor 4
     lanes per cell: the counting functor keeps one lane and every counter, the same force declared stateless gets 4
     lanes, both with the twin's bits."""
-    run("test_links", "ALL LINKED WHOLE-STEP TESTS PASSED")
+    run_native("test_links", "ALL LINKED WHOLE-STEP TESTS PASSED")

@@ -1,20 +1,7 @@
 """Ensemble<Pt, Tile_solver> as a model program uses the header (tests/native_ensemble/test_ensemble.cu, built by
-its own Makefile -- __graft_entry__.build() does it -- and run here on the GPU)."""
-import os
-import subprocess
-
+that directory's Makefile -- __graft_entry__.build() does it -- and run here on the GPU)."""
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native_ensemble")
-
-
-def run(name, marker, args=(), cwd=None):
-    exe = os.path.join(NATIVE, name)
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", NATIVE, name], check=True, capture_output=True)
-    proc = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300, cwd=cwd)
-    assert proc.returncode == 0 and marker in proc.stdout, proc.stdout[-2000:] + proc.stderr[-2000:]
+from ensemble_support import run_native
 
 
 @pytest.mark.gpu
@@ -24,4 +11,4 @@ def test_a_parameter_sweep_written_against_the_header():
     by bumping d_n[r] on the device between steps, nothing is read back until the end -- every replica bit for
     bit a Solution<float3, Tile_solver> run of the same system, for 0 / 1 / 16 / 64 lanes per cell, with the
     centre of mass fixed and after set_fixed_xy."""
-    run("test_ensemble", "ALL ENSEMBLE TESTS PASSED")
+    run_native("test_ensemble", "ALL ENSEMBLE TESTS PASSED")

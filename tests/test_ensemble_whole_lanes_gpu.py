@@ -5,18 +5,14 @@ bits of the six-launch step.  THE REFERENCES are code this feature does not touc
 whole_steps = -1, a lone Solution("<model>_tile") per replica, and the CPU restatement -- and every comparison is of
 bit patterns (uint32, array_equal): no tolerance anywhere.  Every case checks `whole_step_launches`."""
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
+from ensemble_support import (DT, LDS, MIN_TILE, STATIC_LDS, WHOLE, Twins, bits, capacity, coop_lds_bytes,
+                              coop_rule_edges, coop_tile, seeded_rows)
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_ensemble_gpu import bits, seeded_rows  # noqa: E402
-from test_ensemble_whole_steps_gpu import DT, WHOLE, Twins, capacity, launches_of  # noqa: E402
-
-from yalla_amd.ensemble import Ensemble, YallaError  # noqa: E402
-from yalla_amd.solution import Solution  # noqa: E402
+from yalla_amd.ensemble import Ensemble, YallaError
+from yalla_amd.solution import Solution
 
 pytestmark = pytest.mark.gpu
 
@@ -27,48 +23,10 @@ RAGGED = [0, 1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65, 255, 256, 257, 511, 512, 513
 N_FLOATS = {"springs": 3, "clipped": 3, "fading": 3, "relu": 3, "relu_po": 5, "oscillator": 4}
 
 
-# ---- ya::ens::whole_step_coop_lds_bytes<Pt>(n_max, lanes), restated from the header -------------------------------
-LDS, STATIC_LDS, MIN_TILE, MAX_TILE, BUDGET = 160 * 1024, 3 * 256 * 4, 16, 256, 32 * 1024
-
-
-def coop_terms(n_floats, n_max, lanes):
-    """(where the term buffer starts, bytes per partner, [the rule's four bounds on the tile length])."""
-    whole = n_max * (4 * 4 * n_floats + 12) + n_floats * 256 * 4 + n_floats * 4 * 4
-    base = -(-whole // 16) * 16
-    per_partner = (256 // lanes) * (n_floats + 4) * 4
-    room = (LDS - STATIC_LDS - base) // per_partner // 4 * 4
-    budget = max(BUDGET // per_partner // 4 * 4, MIN_TILE)
-    return base, per_partner, [-(-n_max // 4) * 4, MAX_TILE, budget, room]
-
-
-def coop_tile(n_floats, n_max, lanes):
-    base, per_partner, bounds = coop_terms(n_floats, n_max, lanes)
-    if base + STATIC_LDS + MIN_TILE * per_partner > LDS:
-        return 0
-    return min(bounds)
-
-
-def coop_lds_bytes(n_floats, n_max, lanes):
-    base, per_partner, _ = coop_terms(n_floats, n_max, lanes)
-    tile = coop_tile(n_floats, n_max, lanes)
-    return base + tile * per_partner if tile else 0
-
-
-def binding(n_floats, n_max, lanes):
-    """Which of the rule's terms decides the tile length: 0 = n_max, 1 = the longest tile, 2 = the budget, 3 = the
-    room left in the LDS, -1 = no room at all (one lane per cell)."""
-    bounds = coop_terms(n_floats, n_max, lanes)[2]
-    return bounds.index(min(bounds)) if coop_tile(n_floats, n_max, lanes) else -1
-
-
 def rule_edges(n_floats, n_max_up_to):
-    """Every n_max either side of a point where another term of the rule starts to decide, for any lanes."""
-    edges = set()
-    for lanes in LANES:
-        for n_max in range(2, n_max_up_to + 1):
-            if binding(n_floats, n_max, lanes) != binding(n_floats, n_max - 1, lanes):
-                edges |= {n_max - 1, n_max}
-    return sorted(edges)
+    """Every n_max either side of a point where another term of ya::ens::whole_step_coop_lds_bytes' rule (restated in
+    ensemble_support) starts to decide, for any of LANES."""
+    return coop_rule_edges(n_floats, n_max_up_to, LANES)
 
 
 def test_the_restated_rule():

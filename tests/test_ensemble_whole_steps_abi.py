@@ -22,7 +22,7 @@ def test_the_header_documents_the_settings_and_the_count():
         assert name in header, name
     comment_before_take_steps = header[:header.index("int ya_ens_take_steps(")].rsplit("/*", 1)[1]
     assert "Returns the number of whole-step launches" in comment_before_take_steps
-    harness = text("yalla_amd", "csrc", "ensemble.hip")
+    harness = text("yalla_amd", "csrc", "ensemble.hip") + text("yalla_amd", "csrc", "ensemble_harness.h")
     assert '"whole_steps"' in harness and '"steps_per_launch"' in harness
     assert re.search(r"cells\.whole_steps = -1", harness), "the harness keeps the six-launch step as its default"
     grid_harness = text("yalla_amd", "csrc", "ensemble_grid.hip") + text("include", "yalla_ensemble_grid.h")

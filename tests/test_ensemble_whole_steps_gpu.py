@@ -4,91 +4,18 @@ of the six-launch step.  THE REFERENCES are the existing paths -- the same Ensem
 Solution("<model>_tile") per replica, and the CPU restatement (the one comparison that does not pass through the
 device functions the kernels share) -- and every comparison is of bit patterns (uint32, array_equal): no tolerance
 anywhere.  Every case says which path it expects and checks `whole_step_launches` for it."""
-import os
-import sys
-
 import numpy as np
 import pytest
+from ensemble_support import DT, WHOLE, Twins, bits, capacity, launches_of, seeded_rows
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_ensemble_gpu import Lockstep, bits, seeded_rows  # noqa: E402
-
-from yalla_amd.ensemble import Ensemble, GridEnsemble, YallaError  # noqa: E402
-from yalla_amd.solution import Solution  # noqa: E402
+from yalla_amd.ensemble import Ensemble, GridEnsemble, YallaError
+from yalla_amd.solution import Solution
 
 pytestmark = pytest.mark.gpu
 
-DT = 0.05
-# the models whose steps can run whole (no generic forces); `push` must fall back
-WHOLE = ["springs", "clipped", "fading", "relu", "relu_po", "oscillator"]
 # a lone cell, partial wavefronts, 1 / 2 / 3 / 4 cells per thread, B_r = 1 ... 4 partial-sum blocks, both sides of
 # every boundary
 COUNTS = [0, 1, 2, 63, 64, 65, 255, 256, 257, 511, 512, 513, 767, 768, 769, 1023, 1024]
-
-
-def capacity(n_floats):
-    """ya::ens::whole_step_capacity<Pt>() restated from the header's formula: four point arrays and old_v per row,
-    fold256's scratch, <= 4 partial sums, and the 3 x 256 floats ya::fixed_velocity_from_partials folds in, within a
-    workgroup's 160 KiB; at most 1024 rows."""
-    fixed = n_floats * 256 * 4 + n_floats * 4 * 4 + 3 * 256 * 4
-    return min((160 * 1024 - fixed) // (4 * 4 * n_floats + 12), 1024)
-
-
-def launches_of(model, steps, steps_per_launch=256):
-    return 0 if model == "push" else -(-steps // steps_per_launch)
-
-
-class Twins(Lockstep):
-    """Lockstep's Ensemble with whole_steps = 1, its lone Solutions, and a second Ensemble of the same rows that keeps
-    the six launches (whole_steps = -1).  Unused rows hold a pattern of their own, to be found again."""
-
-    def __init__(self, model, counts, n_max, seed=0, singles=None):
-        super().__init__(model, counts, n_max, seed=seed, singles=singles)
-        self.ens.set_param("whole_steps", 1)
-        self.six = Ensemble(model, len(counts), n_max)
-        self.six.set_param("whole_steps", -1)
-        unused = np.arange(n_max)[None, :] >= np.asarray(counts)[:, None]
-        self.ens.h_X[unused] = np.float32(-7.25)
-        self.six.h_X[:] = self.ens.h_X
-        self.six.h_n[:] = counts
-        self.ens.copy_to_device()
-        self.six.copy_to_device()
-        self.seen = 0
-
-    def each(self, call):
-        super().each(call)
-        call(self.six)
-
-    def set_old_v(self, v):
-        super().set_old_v(v)
-        self.six.set_old_v(v)
-
-    def set_counts(self, new):
-        old = list(self.counts)
-        self.six.copy_to_host()
-        super().set_counts(new)
-        for r, n in new.items():
-            self.six.h_X[r, old[r]:n] = self.ens.h_X[r, old[r]:n]
-            self.six.h_n[r] = n
-        self.six.copy_to_device()
-
-    def expect_launches(self, n, what=""):
-        """whole_step_launches rose by n since the last look; the six-launch twin never made one."""
-        assert self.ens.whole_step_launches - self.seen == n, (what, self.ens.whole_step_launches, self.seen, n)
-        self.seen = self.ens.whole_step_launches
-        assert self.six.whole_step_launches == 0
-
-    def check(self, what=""):
-        """Against the lone Solutions (used rows), and against the six-launch Ensemble: EVERY row, used or not."""
-        super().check(what)
-        self.six.copy_to_host()
-        assert list(self.six.h_n) == list(self.ens.h_n), what
-        assert np.array_equal(bits(self.six.h_X), bits(self.ens.h_X)), (what, self.model, "positions")
-        assert np.array_equal(bits(self.six.old_v()), bits(self.ens.old_v())), (what, self.model, "old_v")
-
-    def close(self):
-        super().close()
-        self.six.close()
 
 
 @pytest.mark.parametrize("case", ["1 step", "5 steps", "5 steps from a non-zero old_v"])

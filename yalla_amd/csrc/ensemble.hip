@@ -17,18 +17,11 @@
 #include "model_functors.h"
 
 #include "yalla_ensemble.h"
-#include "ensemble_harness.h"  // No_gen, Push_gen, Replicas, Replicas_of, Model, the entry points' bodies
+#include "ensemble_harness.h"  // No_gen, Push_gen, Tile_replicas(_of), Model, the entry points' bodies
 
 namespace ens_harness {
 
-// What the all-pairs form adds to the shared interface.
-struct Base : public Replicas {
-    virtual long take_steps(float dt, int n_steps) = 0;  // returns the whole-step launches it made
-    virtual void set_lanes(int lanes) = 0;
-    virtual void set_whole_steps(int mode) = 0;
-    virtual void set_steps_per_launch(int steps) = 0;
-    virtual void set_whole_step_lanes(int lanes) = 0;
-};
+using Base = Tile_replicas;  // (the all-pairs form adds nothing to it)
 
 // models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
 // (i = r * n_max + local), so the ensemble's model hands the functor the local ones: the same statements, hence
@@ -48,13 +41,13 @@ struct Oscillator_ids : public No_gen<float4> {
     }
 };
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
-struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
-    using Replicas_of<Ensemble<Pt>, Base>::cells;
+struct Sim : public Tile_replicas_of<Ensemble<Pt>, Base> {
+    using Tile_replicas_of<Ensemble<Pt>, Base>::cells;
     // The harness's own default is the six-launch step (whole_steps = -1): what its callers ran before the
     // whole-step launches existed; set_param("whole_steps", 0 | 1) opts in.  Likewise one lane per cell inside a
     // whole-step launch (whole_step_lanes = 1): the kernel its callers ran before there was a choice;
     // set_param("whole_step_lanes", 0 | 4 | 16 | 64) changes it.
-    Sim(int n_replicas, int n_max) : Replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max}
+    Sim(int n_replicas, int n_max) : Tile_replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max}
     {
         cells.whole_steps = -1;
         cells.whole_step_lanes = 1;
@@ -67,10 +60,6 @@ struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
         cells.template take_steps<pw_int, pw_friction>(dt, n_steps, gen);  // (push's generic force: never whole steps)
         return cells.whole_step_launches - launches_before;
     }
-    void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
-    void set_whole_steps(int mode) override { cells.whole_steps = mode; }
-    void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
-    void set_whole_step_lanes(int lanes) override { cells.whole_step_lanes = lanes; }
 };
 
 static const Model<Base* (*)(int, int)> model_table[] = {
@@ -121,31 +110,6 @@ int ya_ens_synchronize(ya_ens*) { return ens_harness::synchronize(); }
 int ya_ens_set_fixed(ya_ens* e, int mode, int local_point) { return ens_harness::set_fixed(*e->p, mode, local_point); }
 int ya_ens_get_old_v(ya_ens* e, float* out) { return ens_harness::get_old_v(*e->p, out); }
 int ya_ens_set_old_v(ya_ens* e, const float* in) { return ens_harness::set_old_v(*e->p, in); }
-int ya_ens_set_param(ya_ens* e, const char* name, double v)
-{
-    if (!name) return -3;
-    if (std::string(name) == "tile_lanes") {
-        const int lanes = (int)v;
-        if (lanes != 0 && lanes != 1 && lanes != 16 && lanes != 64) return -3;
-        e->p->set_lanes(lanes);
-        return 0;
-    }
-    if (std::string(name) == "whole_steps") {
-        if (v != -1 && v != 0 && v != 1) return -3;
-        e->p->set_whole_steps((int)v);
-        return 0;
-    }
-    if (std::string(name) == "steps_per_launch") {
-        if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
-        e->p->set_steps_per_launch((int)v);
-        return 0;
-    }
-    if (std::string(name) == "whole_step_lanes") {
-        if (v != 0 && v != 1 && v != 4 && v != 16 && v != 64) return -3;
-        e->p->set_whole_step_lanes((int)v);
-        return 0;
-    }
-    return -2;
-}
+int ya_ens_set_param(ya_ens* e, const char* name, double v) { return ens_harness::set_tile_param(*e->p, name, v); }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// What the three ensemble harnesses (ensemble.hip, ensemble_grid.hip, ensemble_gabriel.hip) share: the generic-force
+// What the ensemble harnesses (ensemble.hip, ensemble_links.hip, ensemble_grid.hip, ensemble_gabriel.hip) share: the generic-force
 // policies of their model tables, the interfaces their C handles hold, the overrides that forward to an Ensemble,
 // the model table, and the bodies of the C entry points that are the same but for the prefix.  Each .hip writes its
 // own table, what its form adds, create's checks, set_param, and its exported functions as one-line forwards.
@@ -39,8 +39,9 @@ struct Push_gen {
     static void before_steps(int) {}
 };
 
-// THE INTERFACES.  What every form exposes to its C functions, and what the two grid forms add.  take_steps and a
-// form's own setters are declared by the interface each .hip derives from one of these.
+// THE INTERFACES.  What every form exposes to its C functions, and what the two all-pairs and the two grid forms
+// add.  A grid form's take_steps and a form's own setters are declared by the interface each .hip derives from one
+// of these.
 struct Replicas {
     virtual ~Replicas() {}
     virtual int n_floats() = 0;
@@ -54,6 +55,13 @@ struct Replicas {
     virtual void set_fixed(int mode, int point) = 0;
     virtual float3* d_old_v() = 0;
 };
+struct Tile_replicas : public Replicas {
+    virtual long take_steps(float dt, int n_steps) = 0;  // returns the whole-step launches it made
+    virtual void set_lanes(int lanes) = 0;
+    virtual void set_whole_steps(int mode) = 0;
+    virtual void set_steps_per_launch(int steps) = 0;
+    virtual void set_whole_step_lanes(int lanes) = 0;
+};
 struct Grid_replicas : public Replicas {
     virtual int n_cubes() = 0;
     virtual void set_cube_size(float cube_size) = 0;
@@ -63,8 +71,8 @@ struct Grid_replicas : public Replicas {
     virtual const int* d_offs() = 0;
 };
 
-// THE OVERRIDES.  Cells is an Ensemble<Pt, Solver>, Interface what the .hip derived from Replicas or Grid_replicas;
-// the .hip's Sim derives from one of these two and overrides what is left.
+// THE OVERRIDES.  Cells is an Ensemble<Pt, Solver>, Interface is or derives from Replicas, Tile_replicas or
+// Grid_replicas; the .hip's Sim derives from one of these three and overrides what is left.
 template<typename Cells, typename Interface_>
 struct Replicas_of : public Interface_ {
     using Interface = Interface_;
@@ -88,6 +96,15 @@ struct Replicas_of : public Interface_ {
         if (mode == 2) cells.set_fixed_xy(point);
     }
     float3* d_old_v() override { return cells.d_old_v; }
+};
+template<typename Cells, typename Interface>
+struct Tile_replicas_of : public Replicas_of<Cells, Interface> {
+    using Replicas_of<Cells, Interface>::Replicas_of;
+    using Replicas_of<Cells, Interface>::cells;
+    void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
+    void set_whole_steps(int mode) override { cells.whole_steps = mode; }
+    void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
+    void set_whole_step_lanes(int lanes) override { cells.whole_step_lanes = lanes; }
 };
 template<typename Cells, typename Interface>
 struct Grid_replicas_of : public Replicas_of<Cells, Interface> {
@@ -208,6 +225,33 @@ inline int set_old_v(Replicas& s, const float* in)
     YA_CHECK(ya_device_synchronize());
     YA_CHECK(ya_memcpy_h2d(s.d_old_v(), in, (size_t)s.n_replicas() * s.n_max() * 3 * sizeof(float)));
     return 0;
+}
+// The two all-pairs forms' set_param: -2 for a name that is none of the four.
+inline int set_tile_param(Tile_replicas& s, const char* name, double v)
+{
+    if (!name) return -3;
+    if (std::string(name) == "tile_lanes") {
+        const int lanes = (int)v;
+        if (lanes != 0 && lanes != 1 && lanes != 16 && lanes != 64) return -3;
+        s.set_lanes(lanes);
+        return 0;
+    }
+    if (std::string(name) == "whole_steps") {
+        if (v != -1 && v != 0 && v != 1) return -3;
+        s.set_whole_steps((int)v);
+        return 0;
+    }
+    if (std::string(name) == "steps_per_launch") {
+        if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
+        s.set_steps_per_launch((int)v);
+        return 0;
+    }
+    if (std::string(name) == "whole_step_lanes") {
+        if (v != 0 && v != 1 && v != 4 && v != 16 && v != 64) return -3;
+        s.set_whole_step_lanes((int)v);
+        return 0;
+    }
+    return -2;
 }
 inline int set_cube_size(Grid_replicas& s, float cube_size)
 {

@@ -20,20 +20,15 @@
 #include "model_functors.h"
 
 #include "yalla_ensemble_links.h"
-#include "ensemble_harness.h"  // Replicas, Replicas_of, Model, the entry points' bodies
+#include "ensemble_harness.h"  // Tile_replicas(_of), Model, the entry points' bodies
 
 namespace lens_harness {
 using ens_harness::Model;
-using ens_harness::Replicas;
-using ens_harness::Replicas_of;
+using ens_harness::Tile_replicas;
+using ens_harness::Tile_replicas_of;
 
 // What the linked all-pairs form adds to the shared interface.
-struct Base : public Replicas {
-    virtual long take_steps(float dt, int n_steps) = 0;  // returns the whole-step launches it made
-    virtual void set_lanes(int lanes) = 0;
-    virtual void set_whole_steps(int mode) = 0;
-    virtual void set_steps_per_launch(int steps) = 0;
-    virtual void set_whole_step_lanes(int lanes) = 0;
+struct Base : public Tile_replicas {
     virtual int whole_step_lanes_used() = 0;
     virtual void set_links_path(int path) = 0;
     virtual int* h_link() = 0;
@@ -44,14 +39,14 @@ struct Base : public Replicas {
 // (Policy is unused, always void: the parameter list is the one YA_ENSEMBLE_MODEL instantiates; the generic force
 // here is the links, chosen by links_path.)
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
-struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
-    using Replicas_of<Ensemble<Pt>, Base>::cells;
+struct Sim : public Tile_replicas_of<Ensemble<Pt>, Base> {
+    using Tile_replicas_of<Ensemble<Pt>, Base>::cells;
     const int slots_per_replica;
     Links links;  // (at least one slot: an object of no slots has nothing to allocate or launch)
     int links_path = 0;
     // The defaults of the all-pairs harness: the six-launch step, one lane per cell inside a whole-step launch.
     Sim(int n_replicas, int n_max, int slots_per_replica, float strength)
-        : Replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max}, slots_per_replica{slots_per_replica},
+        : Tile_replicas_of<Ensemble<Pt>, Base>{n_replicas, n_max}, slots_per_replica{slots_per_replica},
           links{n_replicas * slots_per_replica > 0 ? n_replicas * slots_per_replica : 1, strength}
     {
         static_assert(sizeof(Link) == 2 * sizeof(int), "h_link is handed out as pairs of ints");
@@ -79,10 +74,6 @@ struct Sim : public Replicas_of<Ensemble<Pt>, Base> {
         cells.copy_to_device();
         links.copy_to_device();
     }
-    void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
-    void set_whole_steps(int mode) override { cells.whole_steps = mode; }
-    void set_steps_per_launch(int steps) override { cells.steps_per_launch = steps; }
-    void set_whole_step_lanes(int lanes) override { cells.whole_step_lanes = lanes; }
     int whole_step_lanes_used() override { return cells.whole_step_lanes_used; }
     void set_links_path(int path) override { links_path = path; }
     int* h_link() override { return reinterpret_cast<int*>(links.h_link); }
@@ -162,33 +153,12 @@ int ya_lens_set_old_v(ya_lens* e, const float* in) { return ens_harness::set_old
 int ya_lens_set_param(ya_lens* e, const char* name, double v)
 {
     if (!name) return -3;
-    if (std::string(name) == "tile_lanes") {
-        const int lanes = (int)v;
-        if (lanes != 0 && lanes != 1 && lanes != 16 && lanes != 64) return -3;
-        e->p->set_lanes(lanes);
-        return 0;
-    }
-    if (std::string(name) == "whole_steps") {
-        if (v != -1 && v != 0 && v != 1) return -3;
-        e->p->set_whole_steps((int)v);
-        return 0;
-    }
-    if (std::string(name) == "steps_per_launch") {
-        if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
-        e->p->set_steps_per_launch((int)v);
-        return 0;
-    }
-    if (std::string(name) == "whole_step_lanes") {
-        if (v != 0 && v != 1 && v != 4 && v != 16 && v != 64) return -3;
-        e->p->set_whole_step_lanes((int)v);
-        return 0;
-    }
     if (std::string(name) == "links_path") {
         if (v != 0 && v != 1) return -3;
         e->p->set_links_path((int)v);
         return 0;
     }
-    return -2;
+    return ens_harness::set_tile_param(*e->p, name, v);
 }
 int ya_lens_whole_step_lanes_used(ya_lens* e) { return e->p->whole_step_lanes_used(); }
 
