@@ -39,12 +39,12 @@ def system(n=260, seed=3):
     return X
 
 
-def reference_forces(X, by_plane, old_v=None, gs=GS, functor="spring"):
+def reference_forces(X, by_plane, old_v=None, gs=GS, functor="spring", cube_size=1.0):
     """F[i] exactly as the reference's thread accumulates it (or in the two partial sums of YA_SUM_BY_PLANE).
     With old_v: the stage's whole right-hand side, F + sum_v / sum_friction (solvers.cuh:453-461 and add_rhs
     :146-161) -- sum_friction += friction and sum_v += friction * old_v[k] run in the same loop, the same order."""
     n = len(X)
-    cube3 = np.floor(X).astype(np.int64) + gs // 2             # cube_size 1 (solvers.cuh:357-360; exact below 2^24)
+    cube3 = np.floor(X / f32(cube_size)).astype(np.int64) + gs // 2   # solvers.cuh:357-360 (exact below 2^24)
     cube = cube3[:, 0] + cube3[:, 1] * gs + cube3[:, 2] * gs * gs
     members = {}
     for i in np.argsort(cube, kind="stable"):                  # stable sort: ascending id inside a cube
@@ -67,13 +67,14 @@ def reference_forces(X, by_plane, old_v=None, gs=GS, functor="spring"):
                 r = X[i] - X[k]                                 # a += -1 * b, componentwise binary32
                 d2 = fma32(r[2], r[2], fma32(r[1], r[1], f32(r[0] * r[0])))
                 dist = np.sqrt(d2)                              # correctly rounded binary32
-                if dist >= f32(1.0):                            # :450
+                if dist >= f32(cube_size):                      # :450
                     continue
                 if k == i:                                      # springs.cu:17; friction_w_neighbour: 0 (solvers.cuh:30)
                     continue
-                if old_v is not None:                           # friction_w_neighbour: 1 inside dist < 1 (:32)
-                    sf = sf + f32(1)
-                    sv = sv + f32(1) * old_v[k]
+                if old_v is not None:                           # friction_w_neighbour: 1 inside dist < 1 (:32),
+                    friction = f32(1) if dist < f32(1.0) else f32(0)   # 0 beyond it (cube sizes above 1)
+                    sf = sf + friction
+                    sv = sv + friction * old_v[k]
                 if functor == "spring":
                     s = f32(0.5) - dist
                     inv = f32(np.float64(1.0) / np.float64(dist))   # `a *= 1. / b` (dtypes.cuh:204-208)
