@@ -2033,9 +2033,19 @@ __device__ __forceinline__ Pt minus_fix(Pt dX, const float3 fix)
     dX.z -= fix.z;
     return dX;
 }
-// Row i of the corrector X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v (solvers.cuh:127-144), fix = d_fix[0..2]
-// as the predictor left it; returns the new X.  zero_dX: the row of d_dX, dead after this, is left zeroed for
-// the next step's generic forces.
+// The corrector's arithmetic for one cell, X += ((dX - fix) + (dX1 - fix1)) / 2 dt (solvers.cuh:127-144), from the
+// two stages' raw right-hand sides; returns the cell's new old_v.  Every corrector kernel goes through here.
+template<typename Pt>
+__device__ __forceinline__ float3 heun_update(Pt& X, const Pt dX_raw, const Pt dX1_raw, const float3 fix,
+    const float3 fix1, const float dt)
+{
+    const Pt dX = minus_fix(dX_raw, fix);
+    const Pt dX1 = minus_fix(dX1_raw, fix1);
+    X += (dX + dX1) * 0.5 * dt;
+    return float3{(dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
+}
+// Row i of the corrector and old_v, fix = d_fix[0..2] as the predictor left it; returns the new X.  zero_dX: the
+// row of d_dX, dead after this, is left zeroed for the next step's generic forces.
 template<typename Pt>
 __device__ __forceinline__ Pt heun_row(const int i, const float dt, const float* __restrict__ d_fix, const float3 fix1,
     Pt* __restrict__ d_dX, const Pt* __restrict__ d_dX1, Pt* __restrict__ d_X, float3* __restrict__ d_old_v,
@@ -2043,12 +2053,9 @@ __device__ __forceinline__ Pt heun_row(const int i, const float dt, const float*
 {
     const Pt dX_raw = d_dX[i];
     if (zero_dX) d_dX[i] = ya::zero<Pt>();  // (straight after the load: no address kept live)
-    const Pt dX = minus_fix(dX_raw, float3{d_fix[0], d_fix[1], d_fix[2]});
-    const Pt dX1 = minus_fix(d_dX1[i], fix1);
     Pt X = d_X[i];
-    X += (dX + dX1) * 0.5 * dt;
+    d_old_v[i] = heun_update(X, dX_raw, d_dX1[i], float3{d_fix[0], d_fix[1], d_fix[2]}, fix1, dt);
     d_X[i] = X;
-    d_old_v[i] = float3{(dX.x + dX1.x) * 0.5f, (dX.y + dX1.y) * 0.5f, (dX.z + dX1.z) * 0.5f};
     return X;
 }
 }  // namespace ya
@@ -2063,7 +2070,8 @@ __device__ __forceinline__ Pt heun_row(const int i, const float dt, const float*
 // launch.  All pointers but d_dX may be NULL:
 //   d_X0 -> d_X1  the cells in id order (what the generic forces are handed, and stage 2's input without a
 //                 sorted copy)
-//   d_sorted      the cube-sorted copy of Grid_solver, moved in place, from which stage 2's grid build starts:
+//   d_sorted      the cube-sorted copy of Grid_solver, moved in place (or, d_sorted_out given, written there
+//                 and left as it is: Heun_solver::take_steps), from which stage 2's grid build starts:
 //                 a cell's right-hand side is d_dX_sorted[slot], or (totals source) d_dX[id] for a z-slab's
 //                 mirrored cell (id >= n_active), which arrived by message in id order; the copy holds X[id] bit
 //                 for bit, so both give the bits of d_X1[id]
@@ -2075,7 +2083,7 @@ template<typename Pt, ya::Fix_src S>
 __global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step(const int n, const float dt, const ya::Fix_args fix_args,
     const Pt* __restrict__ d_dX, const Pt* __restrict__ d_X0, Pt* __restrict__ d_X1, const Pt* __restrict__ d_dX_sorted,
     ya::Entry<Pt>* __restrict__ d_sorted, const int n_active, Pt* __restrict__ d_zero, float* __restrict__ pred_partial,
-    const ya::Guard_band band)
+    const ya::Guard_band band, ya::Entry<Pt>* __restrict__ d_sorted_out = nullptr)
 {
     const float3 fix = ya::resolve_fix<S, Pt>(fix_args, n);
     const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
@@ -2099,7 +2107,7 @@ __global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step(const int n, cons
                 if (e.id >= n_active) dX = d_dX[e.id];
             const float z0 = e.X.z;
             e.X = e.X + ya::minus_fix(dX, fix) * dt;
-            d_sorted[i] = e;
+            (d_sorted_out ? d_sorted_out : d_sorted)[i] = e;
             moved = fabsf(e.X.z - z0) * band.weight(z0);
         }
         if (d_zero) d_zero[i] = ya::zero<Pt>();
@@ -2132,6 +2140,31 @@ __global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step(const int n, const
             votes_out[1] = fix1_args.src[ya::N_floats<Pt>::value + 3];
         }
         if (moved_partial) ya::block_max_to(moved, moved_partial);
+    }
+}
+
+// The corrector of a carried step (Heun_solver::take_steps), one thread per slot of the step's FIRST build: the
+// cell and its id from d_sorted[s], still at the step's start; stage 1's right-hand side in that order; stage 2's
+// at d_slot2[s], where the second build put the cell (near s: cells move little).  Same operands and statements
+// as heun_step (ya::heun_update).  Leaves {X, id} and {old_v, 0} in slot s of d_out / d_out_v, from which the
+// next step's first build starts, and -- the call's last step: d_X, d_old_v given -- the id-ordered arrays.
+template<typename Pt>
+__global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_sorted(const int n, const float dt,
+    const float* __restrict__ d_fix, const ya::Fix_args fix1_args, const ya::Entry<Pt>* __restrict__ d_sorted,
+    const Pt* __restrict__ d_dX_sorted, const int* __restrict__ d_slot2, const Pt* __restrict__ d_dX1_sorted,
+    ya::Entry<Pt>* __restrict__ d_out, float4* __restrict__ d_out_v, Pt* __restrict__ d_X, float3* __restrict__ d_old_v)
+{
+    const float3 fix1 = ya::resolve_fix<ya::Fix_src::partials, Pt>(fix1_args, n);
+    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
+    if (s >= n) return;
+    ya::Entry<Pt> e = d_sorted[s];
+    const float3 v = ya::heun_update(e.X, d_dX_sorted[s], d_dX1_sorted[d_slot2[s]],
+        float3{d_fix[0], d_fix[1], d_fix[2]}, fix1, dt);
+    d_out[s] = e;
+    d_out_v[s] = make_float4(v.x, v.y, v.z, 0.f);
+    if (d_X) {
+        d_X[e.id] = e.X;
+        d_old_v[e.id] = v;
     }
 }
 
@@ -2222,6 +2255,17 @@ public:
 
 private:
     bool h_X_locked = false;
+    // a z-slab decomposition (Slab_grid_solver, slab.on) steps through its own take_step
+    template<typename S>
+    static auto decomposed(const S& solver, int) -> decltype((bool)solver.slab.on)
+    {
+        return solver.slab.on;
+    }
+    template<typename S>
+    static bool decomposed(const S&, long)
+    {
+        return false;
+    }
 
 public:
     void copy_to_device()
@@ -2248,6 +2292,21 @@ public:
     void take_step(float dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
         return Solver<Pt>::template take_step<pw_int, pw_friction>(dt, gen_forces);
+    }
+    // k steps in one call (not in the reference): bit for bit what k calls of take_step leave, with the
+    // same generic force in each.  Between the steps of one call nothing outside the engine sees or
+    // changes the cells, which lets Grid_solver keep them in cube order from step to step
+    // (Heun_solver::take_steps).
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(float dt, int k, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, k, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(float dt, int k, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        if (!decomposed(*this, 0)) return Solver<Pt>::template take_steps<pw_int, pw_friction>(dt, k, gen_forces);
+        for (int s = 0; s < k; s++) Solver<Pt>::template take_step<pw_int, pw_friction>(dt, gen_forces);
     }
     // The former two-argument generic force `(const Pt* d_X, Pt* d_dX)`, which the
     // reference's own tests still use (tests/test_solvers.cu:141, test_links.cu:19).
@@ -2400,6 +2459,9 @@ public:
     // cannot keep ~10^5 launches per second up.
     int graph_steps = 0;
     long graph_launches = 0;  // read-only: steps that ran as a hipGraphLaunch (tests: replay really happened)
+    // take_steps: false = always the loop of take_step (A/B, tests; same results)
+    bool carry_sorted = true;
+    long carried_steps = 0;  // read-only: steps whose first build started from the step before's cube-sorted cells
 
 protected:
 #ifndef YA_GRAPH_MAX_CELLS
@@ -2722,6 +2784,71 @@ protected:
         heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
         last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};  // (after the launches, as above)
     }
+
+    // k steps in one call, bit for bit what k calls of take_step leave in d_X, d_old_v, d_n, d_dX, d_dX1 and
+    // the grid's public arrays.  No model code runs between the steps of one call, so the id-ordered
+    // arrays d_X / d_old_v -- the reference's contract BETWEEN two take_step calls -- need not exist in
+    // between: Grid_solver's plain step (set_fixed(), no generic force) carries the cells in cube order.
+    //   step 1, stage 1   the build by id, as take_step (n is read here, once)
+    //   predictor         euler_step into a second entry buffer: d_sorted keeps {X0, id} in stage-1 order
+    //   stage 2           rebuild from the predicted entries; the force kernel also leaves its right-hand
+    //                     sides in ITS sorted order, k_order_from where each stage-1 slot went
+    //   corrector         heun_step_sorted, per stage-1 slot -> {X, id}, {old_v, 0} in that order
+    //   steps 2 .. k      stage 1 = rebuild from the corrector's output: k_order_from's rank count by id
+    //                     restores ascending ids inside every cube, hence every sum's order
+    //   step k            the corrector also stores d_X[id], d_old_v[id]
+    // The centre-of-mass partial sums read d_dX / d_dX1 by id as ever (the force kernels' stores by id stay).
+    // Nothing is remembered across calls: the next call's first build is by id again, so whatever a model
+    // does between calls (copy_to_device, a kernel on d_X, another n) needs no invalidation.  Every
+    // other configuration -- and k < 2 -- IS the loop of take_step.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(const float dt, const int k, Generic_forces<Pt> gen_forces)
+    {
+        if (take_steps_carried<pw_int, pw_friction>(dt, k, gen_forces)) return;
+        for (int s = 0; s < k; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
+    }
+    // false: does not qualify, nothing was done
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    bool take_steps_carried(const float dt, const int k, Generic_forces<Pt>& gen_forces)
+    {
+        if (!carry_sorted || k < 2 || graph_steps != 0 || keep_order) return false;
+        if (!(fix_com and !fix_com_z and fold_in_update) || !ya::is_no_gen_forces<Pt>(gen_forces)) return false;
+        if (!Computer<Pt>::carry_ready(n_max)) return false;  // (may allocate: before anything is queued)
+        int n;
+        Computer<Pt>::begin_build(d_X, d_n, n_max, n_reader);
+        YA_CHECK(ya_n_read_end(n_reader, &n));
+        assert(n <= n_max);
+        if (n <= 0) {  // nothing is carried, nothing is stale: the rest of the loop as it is
+            Computer<Pt>::cancel_build();
+            for (int s = 1; s < k; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
+            return true;
+        }
+        const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
+        for (int s = 0; s < k; s++) {
+            int n_partials = 0;
+            if (s == 0)
+                Computer<Pt>::template pwints<pw_int, pw_friction>(n, d_X, d_old_v, d_dX, false, n, true);
+            else
+                Computer<Pt>::template pwints_carried<pw_int, pw_friction>(1, n, d_dX);
+            YA_CHECK(ya_reduce_partials(d_dX, n_floats, n, d_workspace, &n_partials, this->stream));
+            euler_step<Pt, Fix::partials><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt,
+                ya::Fix_args{d_workspace, n_partials, d_mean_first}, d_dX, d_X, nullptr, Computer<Pt>::sorted_rhs(),
+                Computer<Pt>::sorted_cells(), n, nullptr, nullptr, ya::Guard_band{}, Computer<Pt>::carried_cells());
+            Computer<Pt>::template pwints_carried<pw_int, pw_friction>(2, n, d_dX1);
+            YA_CHECK(ya_reduce_partials(d_dX1, n_floats, n, d_workspace, &n_partials, this->stream));
+            const bool last = s == k - 1;
+            heun_step_sorted<Pt><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, d_mean_first,
+                ya::Fix_args{d_workspace, n_partials}, Computer<Pt>::sorted_cells(), Computer<Pt>::sorted_rhs(),
+                Computer<Pt>::carried_slots(), Computer<Pt>::carried_rhs(), Computer<Pt>::carried_cells(),
+                Computer<Pt>::carried_v(), last ? d_X : nullptr, last ? d_old_v : nullptr);
+        }
+        stage1_fix = d_mean_first;
+        sorted_stage_cells = -1;
+        rhs_zeroed[0] = rhs_zeroed[1] = 0;
+        last_key = key_of<pw_int, pw_friction>(n, dt);
+        carried_steps += k - 1;
+        return true;
+    }
 };
 
 
@@ -2758,6 +2885,14 @@ protected:
     ya::Entry<Pt>* sorted_cells() { return nullptr; }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints_from_sorted(int, Pt*, int, bool) {}
+    // no cube order to carry from step to step (Heun_solver::take_steps)
+    bool carry_ready(int) { return false; }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void pwints_carried(int, int, Pt*) {}
+    ya::Entry<Pt>* carried_cells() { return nullptr; }
+    float4* carried_v() { return nullptr; }
+    const Pt* carried_rhs() const { return nullptr; }
+    const int* carried_slots() const { return nullptr; }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints(const int n, const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v,
         Pt* d_dX, const bool has_gen, const int n_active, const bool keep_sorted)
@@ -2846,10 +2981,10 @@ public:
     template<typename Pt>
     void rebuild_sorted(const int n, const ya::Entry<Pt>* d_prev, const float4* d_prev_v,
         const float cube_size, ya::Entry<Pt>* d_sorted, float4* d_sorted_v,
-        hipStream_t stream = nullptr)
+        hipStream_t stream = nullptr, int* d_slot_of_prev = nullptr)
     {
-        YA_CHECK(ya_grid_rebuild_sorted(handle, d_prev, sizeof(ya::Entry<Pt>), sizeof(Pt),
-            d_prev_v, n, cube_size, d_sorted, d_sorted_v, stream));
+        YA_CHECK(ya_grid_rebuild_sorted_map(handle, d_prev, sizeof(ya::Entry<Pt>), sizeof(Pt),
+            d_prev_v, n, cube_size, d_sorted, d_sorted_v, d_slot_of_prev, stream));
     }
     const int* offsets() const { return d_offs; }
     // The ids the last build saw mean other cells now (Solution::renumber): the next build visits
@@ -2950,6 +3085,7 @@ public:
         ya_free(d_resorted);
         ya_free(d_resorted_v);
         ya_free(d_dX_sorted);
+        if (d_carried) ya_free(d_carried), ya_free(d_carried_rhs), ya_free(d_carried_slots);
         for (int p = 0; p < 3; p++) ya_free(d_tail_exchange[p]), ya_free(d_tail_tickets[p]);
         if (interior_stream && interior_stream_owned) (void)hipStreamDestroy(interior_stream);
         if (grid_built) {
@@ -3295,6 +3431,53 @@ protected:
         grid.rebuild_sorted(n, d_sorted, d_sorted_v, cube_size, d_resorted, d_resorted_v, stream);
         forces<pw_int, pw_friction>(n, d_resorted, d_resorted_v, d_dX, has_gen, n_active, nullptr);
     }
+    // ---- cells carried in cube order from step to step (Heun_solver::take_steps) ----
+    // Buffers beyond a plain step's, ~32 bytes per cell, made by the first call that carries:
+    //   d_carried        entries: the predictor's output, then -- dead once stage 2 is built -- the corrector's
+    //   d_carried_rhs    stage 2's right-hand sides in stage 2's sorted order
+    //   d_carried_slots  stage-1 slot -> stage-2 slot
+    // (the corrector's {old_v, 0} go to d_resorted_v, dead after stage 2's force launch)
+    ya::Entry<Pt>* d_carried = nullptr;
+    Pt* d_carried_rhs = nullptr;
+    int* d_carried_slots = nullptr;
+    // Does this computer carry right now (undivided, local ids = global ids), and has it the memory?  Called
+    // outside any stream capture, before the call's first launch; false = the plain loop.
+    bool carry_ready(const int n_max)
+    {
+        if (!use_sorted_pipeline() || d_global_id || force_part != 0) return false;
+        if (d_carried) return true;
+        if (carry_refused) return false;
+        const int rc[3] = {ya_malloc((void**)&d_carried, (size_t)n_max * sizeof(ya::Entry<Pt>)),
+            ya_malloc((void**)&d_carried_rhs, (size_t)n_max * sizeof(Pt)),
+            ya_malloc((void**)&d_carried_slots, (size_t)n_max * sizeof(int))};
+        if (rc[0] == 0 && rc[1] == 0 && rc[2] == 0) return true;
+        // out of memory: the plain loop needs none of it (and the runtime's sticky-free error is taken off)
+        if (rc[0] == 0) ya_free(d_carried);
+        if (rc[1] == 0) ya_free(d_carried_rhs);
+        if (rc[2] == 0) ya_free(d_carried_slots);
+        d_carried = nullptr, d_carried_rhs = nullptr, d_carried_slots = nullptr;
+        (void)hipGetLastError();
+        carry_refused = true;  // (not asked for again at every call)
+        return false;
+    }
+    bool carry_refused = false;
+    // stage 1 of a carried step after the call's first: from the corrector's output, as stage 2 starts from
+    // the predictor's; stage 2: from the predicted entries, with the slot map and the sorted right-hand sides
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void pwints_carried(const int stage, const int n, Pt* d_dX)
+    {
+        if (stage == 1) {
+            grid.rebuild_sorted(n, d_carried, d_resorted_v, cube_size, d_sorted, d_sorted_v, stream);
+            forces<pw_int, pw_friction>(n, d_sorted, d_sorted_v, d_dX, false, n, d_dX_sorted);
+        } else {
+            grid.rebuild_sorted(n, d_carried, d_sorted_v, cube_size, d_resorted, d_resorted_v, stream, d_carried_slots);
+            forces<pw_int, pw_friction>(n, d_resorted, d_resorted_v, d_dX, false, n, d_carried_rhs);
+        }
+    }
+    ya::Entry<Pt>* carried_cells() { return d_carried; }
+    float4* carried_v() { return d_resorted_v; }
+    const Pt* carried_rhs() const { return d_carried_rhs; }
+    const int* carried_slots() const { return d_carried_slots; }
 };
 
 template<typename Pt>
@@ -3323,6 +3506,7 @@ public:
     }
     Gabriel_computer(const Gabriel_computer&) = delete;
     bool use_sorted_pipeline() const { return false; }
+    bool carry_ready(int) { return false; }  // (d_X pipeline only: Heun_solver::take_steps is the loop)
 
 protected:
     int* d_dense = nullptr;  // [0] cells left to gabriel_force_dense, [1] their largest count, then the cells

@@ -153,6 +153,12 @@ int ya_grid_build_sorted_begin_publish(ya_grid* g, const void* d_X, size_t strid
 int ya_grid_rebuild_sorted(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
     size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
     void* d_sorted_v_out, void* stream);
+/* ... and, if d_slot_of_prev is not NULL, where every cell went: d_slot_of_prev[s] = the slot in the
+ * outputs of the cell that sat in entry s of d_prev_sorted (n ints; Heun_solver::take_steps reads the
+ * second stage's right-hand sides through it in the first stage's order). */
+int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
+    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
+    void* d_sorted_v_out, int* d_slot_of_prev, void* stream);
 
 /* A build visits the cells in the previous build's sorted order (they move little between builds:
  * neighbouring lanes then bin into neighbouring counters).  After the caller has given the cells

@@ -56,7 +56,11 @@ int ya_sim_copy_to_host(ya_sim* sim);   /* solvers.cuh:86-91 */
 int ya_sim_get_d_n(ya_sim* sim);        /* solvers.cuh:92 */
 
 /* n_steps calls of take_step<pw_int, pw_friction>(dt, gen_forces) followed by
- * the model's post-step kernel if it has one (e.g. proliferation). */
+ * the model's post-step kernel if it has one (e.g. proliferation).  Device build: a model with nothing between
+ * its steps and no generic force goes through Solution::take_steps (include/solvers.cuh) -- the same bits; a
+ * Grid_solver model keeps its cells cube-sorted between the steps of the call.  set_param "carry_sorted" 0 / 1
+ * (device build only) is its A/B switch, and libyalla_models.so alone also exports the test hook
+ * `long carried_steps(ya_sim*)` under the ya_sim_ prefix: steps so far that started from carried cells. */
 int ya_sim_take_steps(ya_sim* sim, float dt, int n_steps);
 /* Block until the device is idle (no-op on the oracle). */
 int ya_sim_synchronize(ya_sim* sim);
@@ -85,7 +89,7 @@ int ya_sim_build_grid(ya_sim* sim, int grid_size, float cube_size, int* cube_id,
  * result: "force_variant", "coop_lanes", "stage_v_max", "tail_tiles" (grid_force_bits: -1 the engine's choice,
  * 0 whole tiles only, k the last k tiles of a launch as half tiles, the launch's tile count or more: all),
  * "gather_offset_bits" (grid_force_bits: 0 = old_v through 32-bit byte offsets while 16 n fits them, 64 = 64-bit
- * addresses at any size), "sorted_pipeline", "graph", "tile_lanes". */
+ * addresses at any size), "sorted_pipeline", "graph", "tile_lanes", "carry_sorted" (device build only). */
 int ya_sim_set_param(ya_sim* sim, const char* name, double value);
 /* Integer per-cell properties of a model ("type", "mes_nbs", "epi_nbs"). */
 int ya_sim_set_prop(ya_sim* sim, const char* name, const int* values, int n);

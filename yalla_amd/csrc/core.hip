@@ -316,13 +316,14 @@ __global__ __launch_bounds__(BLOCK) void k_order(const int* __restrict__ arrival
 // input, so every read is coalesced or local and nothing is gathered from the
 // original-order arrays.  arrival_src[slot] = index of the cell in the previous
 // sorted arrays, arrival_pid[slot] = its id (k_scatter copied it from the entry).
+// slot_of_src (may be NULL): where each cell of the previous arrays went, slot_of_src[src] = dst.
 template<int EW>
 __global__ __launch_bounds__(BLOCK) void k_order_from(const int* __restrict__ arrival_pid,
     const int* __restrict__ arrival_src, const int* __restrict__ cube_id_sorted,
     const int* __restrict__ offs, int n,
     const unsigned* __restrict__ prev_entries, const float4* __restrict__ prev_v,
     int* __restrict__ point_id, int* __restrict__ next_prev_pid, unsigned* __restrict__ sorted_out,
-    float4* __restrict__ sorted_v_out)
+    float4* __restrict__ sorted_v_out, int* __restrict__ slot_of_src)
 {
     int s = blockIdx.x * BLOCK + threadIdx.x;
     if (s >= n) return;
@@ -343,6 +344,7 @@ __global__ __launch_bounds__(BLOCK) void k_order_from(const int* __restrict__ ar
 #pragma unroll
     for (int k = 0; k < EW; k++) out[k] = w[k];
     sorted_v_out[dst] = prev_v[src];
+    if (slot_of_src) slot_of_src[src] = dst;
 }
 
 // --- deterministic reduction -----------------------------------------------
@@ -1185,6 +1187,14 @@ int ya_grid_rebuild_sorted(ya_grid* g, const void* d_prev_sorted, size_t entry_b
     size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
     void* d_sorted_v_out, void* stream)
 {
+    return ya_grid_rebuild_sorted_map(g, d_prev_sorted, entry_bytes, point_bytes, d_prev_sorted_v, n, cube_size,
+        d_sorted_out, d_sorted_v_out, nullptr, stream);
+}
+
+int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
+    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
+    void* d_sorted_v_out, int* d_slot_of_prev, void* stream)
+{
     if (!g || n < 0 || n > g->n_max || point_bytes < 12 || entry_bytes < point_bytes + 4 ||
         entry_bytes % 4 || point_bytes % 4 || !d_prev_sorted || !d_prev_sorted_v || !d_sorted_out ||
         !d_sorted_v_out)
@@ -1207,7 +1217,8 @@ int ya_grid_rebuild_sorted(ya_grid* g, const void* d_prev_sorted, size_t entry_b
     case EW:                                                                                 \
         k_order_from<EW><<<nb, BLOCK, 0, st>>>(g->d_arrival, g->d_arrival_src, g->d_cube_id, \
             g->d_offs, n, (const unsigned*)d_prev_sorted, (const float4*)d_prev_sorted_v,    \
-            g->d_point_id, g->d_prev_pid, (unsigned*)d_sorted_out, (float4*)d_sorted_v_out); \
+            g->d_point_id, g->d_prev_pid, (unsigned*)d_sorted_out, (float4*)d_sorted_v_out,  \
+            d_slot_of_prev);                                                                 \
         break;
         switch (entry_f) {
             YA_ORDER_FROM(4)

@@ -51,6 +51,9 @@ struct Sim_base {
     virtual int profile(int) { return -1; }
     virtual int profile_read(double*, int*) { return -1; }
     virtual long graph_launches() { return -1; }
+#if YA_IS_DEVICE
+    virtual long carried_steps() = 0;
+#endif
     // z-slab decomposition (Grid_solver models only)
     virtual int slab_init(float, float, float, const int*) { return -2; }
     virtual int slab_decompose(const float*, int, int, int, float) { return -2; }
@@ -307,6 +310,10 @@ struct No_gen {
     // what a model adds to its loop to keep its cells in cube order (opt-in: Solution::renumber)
     template<typename C>
     void post_step(C&, float) {}
+#if YA_IS_DEVICE
+    // pre_step and post_step do nothing: n steps may go to the solver as ONE take_steps call (Sim::take_steps)
+    static constexpr bool steps_alone = true;
+#endif
     template<typename C>
     int keep_in_cube_order(C& cells, int every)
     {
@@ -493,6 +500,9 @@ struct Growth_policy : public No_gen<typename Rule::Pt> {
     double mean_dist = 0.75;
     unsigned seed = 1, step = 0;
     bool reset_nbs = true;  // false: take_step without the generic force (:117)
+#if YA_IS_DEVICE
+    static constexpr bool steps_alone = false;  // (cells divide between the steps)
+#endif
     template<typename C>
     void ensure(C& cells)
     {
@@ -632,6 +642,17 @@ struct Sim : public Sim_base {
     int get_d_n() override { return cells.get_d_n(); }
     void take_steps(float dt, int n_steps) override
     {
+#if YA_IS_DEVICE
+        // a model loop without anything between its steps and without a generic force: one call, in which
+        // Grid_solver keeps the cells in cube order from step to step (Solution::take_steps; the same bits)
+        if (Policy::steps_alone) {
+            Generic_forces<Pt> gen = policy.gen(cells);
+            if (ya::is_no_gen_forces<Pt>(gen)) {
+                cells.template take_steps<pw_int, pw_friction>(dt, n_steps, gen);
+                return;
+            }
+        }
+#endif
         for (int s = 0; s < n_steps; s++) {
             policy.pre_step(cells);
             cells.template take_step<pw_int, pw_friction>(dt, policy.gen(cells));
@@ -690,6 +711,12 @@ struct Sim : public Sim_base {
         if (std::string(name) == "slab_guard") return cells.set_slab_guard((int)v);
         if (std::string(name) == "slab_guard_lag") return cells.set_slab_guard_lag((float)v);
         if (std::string(name) == "slab_local_order") return cells.set_slab_local_order((int)v);
+#if YA_IS_DEVICE
+        if (std::string(name) == "carry_sorted") {  // Heun_solver::carry_sorted (A/B, tests; same results)
+            cells.carry_sorted = v != 0;
+            return 0;
+        }
+#endif
 #ifndef YA_ORACLE
         if (std::string(name) == "links_segmented_min") {  // ya::links_segmented_min(), process-wide
             ya::links_segmented_min() = (int)v;
@@ -742,6 +769,9 @@ struct Sim : public Sim_base {
         return cells.graph_launches_so_far();
 #endif
     }
+#if YA_IS_DEVICE
+    long carried_steps() override { return cells.carried_steps; }
+#endif
 #ifdef YA_ORACLE
     int set_reduce_order(int order) override
     {
@@ -1003,5 +1033,11 @@ long ya_check_reciprocal(unsigned first_bits, unsigned last_bits)
 int ya_sim_profile(ya_sim* s, int enable) { return s->p->profile(enable); }
 int ya_sim_profile_read(ya_sim* s, double* ms, int* launches) { return s->p->profile_read(ms, launches); }
 long ya_sim_graph_launches(ya_sim* s) { return s->p->graph_launches(); }
+#if YA_IS_DEVICE
+// Device build only, read-only (test hook, beside ya_sim_graph_launches): the steps of this system so far whose
+// first grid build started from the step before's cube-sorted cells (Heun_solver::carried_steps): k - 1 per
+// qualifying ya_sim_take_steps call of k steps, 0 for everything that ran as the loop of take_step.
+__attribute__((visibility("default"))) long ya_sim_carried_steps(ya_sim* s) { return s->p->carried_steps(); }
+#endif
 
 }  // extern "C"

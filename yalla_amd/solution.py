@@ -171,6 +171,16 @@ class Solution:
         """Steps so far that ran as a hipGraphLaunch (-1 oracle, -2 solvers without captured steps)."""
         return self.lib.ya_sim_graph_launches(self._h)
 
+    def carried_steps(self):
+        """Steps so far whose first grid build started from the step before's cube-sorted cells
+        (`take_step(dt, k)` on a qualifying Grid_solver model: k - 1 per call; -1 where the library has no
+        such counter, as the oracle)."""
+        fn = getattr(self.lib, "ya_sim_carried_steps", None)
+        if fn is None:
+            return -1
+        fn.restype, fn.argtypes = C.c_long, [C.c_void_p]
+        return fn(self._h)
+
     def profile(self, enable, every=1):
         """Time every `every`-th launch of the force kernel with HIP events."""
         return self.lib.ya_sim_profile(self._h, int(every) if enable else 0)
