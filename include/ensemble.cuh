@@ -53,7 +53,7 @@
 // on the grid form's build.
 //
 // Not here ("Ensembles"): the fast-arithmetic tier, graph capture, a per-replica dt or
-// gabriel_coefficient, slabs, whole steps for grid ensembles.
+// gabriel_coefficient, slabs.
 #pragma once
 
 #include "solvers.cuh"
@@ -440,44 +440,26 @@ __device__ __forceinline__ void whole_stage_forces(const int n, const int id_bas
         whole_stage_force_coop<Pt, pw_int, pw_friction, LANES, HAS_GEN>(n, id_base, sh_in, sh_v, sh_rhs, sh_part, tile);
 }
 
-// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
-// Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
-// end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
-// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
-// The body of the kernels below.  LANES = 1: a stage's forces are whole_stage_force; 4, 16 or 64:
-// whole_stage_force_coop with tiles of `tile` partners, everything else the same statements.
-// LINKED (whole_steps_linked below): once per launch the workgroup builds the replica's incidence list behind the
-// step's arrays (whole_links_build); every stage starts with the ordered link forces of its positions as the
-// right-hand sides (whole_stage_links), to which the stage's forces are added.  Links do not change during a launch.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED = false>
-__device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const int* __restrict__ d_n, const float dt,
+// THE STEP IN LDS, written once: n_steps Heun steps of a replica of n > 0 rows by ONE 256-thread workgroup whose
+// dynamic LDS starts with the arrays of whole_step_lds_bytes<Pt>(n_max).  Rows [0, n) of the replica's d_X and d_old_v
+// are read at the start and written at the end; in between, per stage: stage_forces(sh_in, sh_v, sh_rhs) -- every
+// thread calls it; it leaves the right-hand sides of the positions sh_in (X, then X1) in sh_rhs and may have barriers
+// of its own, the barrier after it is here -- then the mean or fixed point (whole_stage_fix), the predictor or
+// ya::heun_row.  What a stage's forces are is the caller's: the all-pairs loops (whole_steps_of_a_replica below) or a
+// grid's stencil walk (ya::ens::grid_lds_steps, ensemble_grid.cuh).  kind1 / kind2: the Fix_kind of stage 1 and 2.
+template<typename Pt, typename Stage_forces>
+__device__ __forceinline__ void whole_steps_in_lds(const int n_max, const int n, const int replica, const float dt,
     const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const int tile, const Links_view links = Links_view{})
+    float3* __restrict__ d_old_v_all, unsigned char* lds, const Stage_forces& stage_forces)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char whole_step_lds[];
     constexpr int NF = N_floats<Pt>::value;
-    const int replica = blockIdx.x;
-    const int n = count_of(d_n, replica, n_max);
-    if (n <= 0) return;  // (the whole workgroup; an empty replica is left alone)
-    Pt* sh_X = reinterpret_cast<Pt*>(whole_step_lds);
+    Pt* sh_X = reinterpret_cast<Pt*>(lds);
     Pt* sh_X1 = sh_X + n_max;
     Pt* sh_dX = sh_X1 + n_max;
     Pt* sh_dX1 = sh_dX + n_max;
     float3* sh_v = reinterpret_cast<float3*>(sh_dX1 + n_max);
     float* sh_fold = reinterpret_cast<float*>(sh_v + n_max);
     float* sh_partials = sh_fold + NF * UPDATE_BLOCK;
-    float* sh_part = nullptr;  // the term buffer of several lanes per cell
-    if constexpr (LANES > 1 && !LINKED) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
-    int* sh_off = nullptr;        // the incidence list: n_max + 1 offsets,
-    unsigned* sh_ent = nullptr;   // at most 2 slots_per_replica entries
-    if constexpr (LINKED) {
-        sh_off = reinterpret_cast<int*>(whole_step_lds + whole_step_links_base<Pt>(n_max));
-        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
-        if constexpr (LANES > 1)
-            sh_part = reinterpret_cast<float*>(
-                whole_step_lds + whole_step_links_part_base<Pt>(n_max, links.slots_per_replica));
-        whole_links_build(links, replica, n, n_max, sh_off, sh_ent, reinterpret_cast<int*>(sh_fold));
-    }
 
     const size_t base = (size_t)replica * n_max;
     Pt* __restrict__ d_X = d_X_all + base;
@@ -490,22 +472,14 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
 
     for (int step = 0; step < n_steps; step++) {
         // predictor: X1 = X + (dX - fix) dt (euler_step_batched)
-        if constexpr (LINKED) {
-            whole_stage_links<Pt>(n, sh_X, sh_dX, sh_off, sh_ent, links.strength);
-            if constexpr (LANES > 1) __syncthreads();  // (another thread adds the cell's forces to it)
-        }
-        whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_X, sh_v, sh_dX, sh_part, tile);
+        stage_forces(sh_X, sh_v, sh_dX);
         __syncthreads();
         const float3 fix = whole_stage_fix<Pt>(kind1, n, sh_dX, fix_point, sh_fold, sh_partials);
         for (int local = threadIdx.x; local < n; local += UPDATE_BLOCK)
             sh_X1[local] = sh_X[local] + ya::minus_fix(sh_dX[local], fix) * dt;
         __syncthreads();
         // corrector (heun_step_batched): old_v is written only after this barrier, when stage 2's forces have read it
-        if constexpr (LINKED) {
-            whole_stage_links<Pt>(n, sh_X1, sh_dX1, sh_off, sh_ent, links.strength);
-            if constexpr (LANES > 1) __syncthreads();
-        }
-        whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_X1, sh_v, sh_dX1, sh_part, tile);
+        stage_forces(sh_X1, sh_v, sh_dX1);
         __syncthreads();
         const float3 fix1 = whole_stage_fix<Pt>(kind2, n, sh_dX1, fix_point, sh_fold, sh_partials);
         const float fix_first[3] = {fix.x, fix.y, fix.z};  // stage 1's, as the predictor leaves it in d_fix_first
@@ -518,6 +492,50 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
         d_X[local] = sh_X[local];
         d_old_v[local] = sh_v[local];
     }
+}
+
+// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
+// Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
+// end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
+// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
+// The body of the kernels below: whole_steps_in_lds with the all-pairs forces of a stage.  LANES = 1: they are
+// whole_stage_force; 4, 16 or 64: whole_stage_force_coop with tiles of `tile` partners.
+// LINKED (whole_steps_linked below): once per launch the workgroup builds the replica's incidence list behind the
+// step's arrays (whole_links_build); every stage starts with the ordered link forces of its positions as the
+// right-hand sides (whole_stage_links), to which the stage's forces are added.  Links do not change during a launch.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED = false>
+__device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const int* __restrict__ d_n, const float dt,
+    const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const int tile, const Links_view links = Links_view{})
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char whole_step_lds[];
+    const int replica = blockIdx.x;
+    const int n = count_of(d_n, replica, n_max);
+    if (n <= 0) return;  // (the whole workgroup; an empty replica is left alone)
+    float* sh_part = nullptr;  // the term buffer of several lanes per cell
+    if constexpr (LANES > 1 && !LINKED) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
+    int* sh_off = nullptr;        // the incidence list: n_max + 1 offsets,
+    unsigned* sh_ent = nullptr;   // at most 2 slots_per_replica entries
+    if constexpr (LINKED) {
+        sh_off = reinterpret_cast<int*>(whole_step_lds + whole_step_links_base<Pt>(n_max));
+        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
+        if constexpr (LANES > 1)
+            sh_part = reinterpret_cast<float*>(
+                whole_step_lds + whole_step_links_part_base<Pt>(n_max, links.slots_per_replica));
+        // (its scratch is the fold's, behind the step's arrays)
+        whole_links_build(links, replica, n, n_max, sh_off, sh_ent,
+            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(whole_step_lds) + 4 * n_max) + n_max));
+    }
+
+    const size_t base = (size_t)replica * n_max;
+    whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, whole_step_lds,
+        [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
+            if constexpr (LINKED) {
+                whole_stage_links<Pt>(n, sh_in, sh_rhs, sh_off, sh_ent, links.strength);
+                if constexpr (LANES > 1) __syncthreads();  // (another thread adds the cell's forces to it)
+            }
+            whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_in, sh_v, sh_rhs, sh_part, tile);
+        });
 }
 // One thread per cell: dynamic LDS of whole_step_lds_bytes<Pt>(n_max).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>

@@ -21,6 +21,14 @@
 // They are valid after a step for the LAST build (stage 2: the predictor's positions), as a lone Solution's are.
 // A replica with n_r = 0 gets an empty grid (every cube empty), as an empty Solution's step leaves its Grid.
 //
+// WHOLE STEPS FROM LDS  cells.take_steps<my_force>(dt, 100) is 100 calls of take_step, bit for bit (positions, old_v,
+// d_status, the public grid arrays); where a replica fits one workgroup's LDS (n_max <= ya::ens::grid_lds_capacity<Pt>(),
+// 1024 for the usual point types), there are no generic forces and `lds_steps` allows it, it runs as ONE launch per
+// lds_steps_max steps: a workgroup per replica sorts the replica's (cube, id) keys in LDS, finds the stencil rows by
+// searching that order and steps from LDS (ya::ens::grid_lds_steps) -- no counters, nothing of size grid_size^3 touched
+// in between.  The step itself is ya::ens::whole_steps_in_lds (ensemble.cuh), which the all-pairs whole steps call too.
+// Not built for these launches: several lanes per cell, Replica_links, the Gabriel form, the fast tier, graph capture.
+//
 // COST  Every stage scans n_replicas * grid_size^3 counters (one workgroup per replica walks its cubes) whatever
 // the replicas hold: a sweep picks grid_size to fit its replicas, not the single system's default of 50.
 //
@@ -210,6 +218,216 @@ inline int grid_lanes_for(const int n_replicas, const int n_max)
     return cells > 120000 ? 1 : coop::lanes_for((int)cells);
 }
 
+// ---- whole Heun steps of a replica from LDS (Ensemble<Pt, Grid_solver>::take_steps, lds_steps) ---------------------
+// A replica that fits one workgroup's LDS needs no counters: the workgroup sorts the replica's (cube, id) keys in
+// LDS, which IS the order count + scan + scatter + grid_order_batched produce (cubes ascending, ids ascending inside
+// a cube), and offs[k] -- the number of cells in cubes below k -- is a binary search of that order.  Nothing of size
+// grid_size^3 is touched between the launch's first load and its last stores.
+//
+// THE LDS RULE  The step's own arrays (whole_step_lds_bytes<Pt>(n_max), ensemble.cuh), 8-byte aligned, then ONE 64-bit
+// key per row: cube id in the high word, local id in the low word; after the sort, slot s holds the cube of the
+// cell in sorted slot s and the slot -> id map at once, 8 bytes per row and no sorted copy of the entries.  The
+// bitonic sort needs a power of two of keys, so the array is laid out for n_max rounded up to one.
+constexpr int grid_lds_key_rows(const int n_max)
+{
+    int p = 1;
+    while (p < n_max) p <<= 1;
+    return p;
+}
+template<typename Pt>
+constexpr size_t grid_lds_keys_base(const int n_max)  // where the keys start
+{
+    return (whole_step_lds_bytes<Pt>(n_max) + 7) / 8 * 8;
+}
+template<typename Pt>
+constexpr size_t grid_lds_bytes(const int n_max)
+{
+    return grid_lds_keys_base<Pt>(n_max) + (size_t)grid_lds_key_rows(n_max) * sizeof(unsigned long long);
+}
+// The largest n_max whose launch fits one workgroup, ya::fixed_velocity_from_partials' static fold scratch included;
+// at most WHOLE_STEP_MAX_ROWS (1024 for every point type up to 8 floats: an 8-float point's 1024 rows leave 896 bytes).
+template<typename Pt>
+constexpr int grid_lds_capacity()
+{
+    int rows = 0;
+    for (int n = 1; n <= WHOLE_STEP_MAX_ROWS; n++)
+        if (grid_lds_bytes<Pt>(n) + WHOLE_STEP_STATIC_LDS <= LDS_PER_WORKGROUP) rows = n;  // (the rule never falls)
+    return rows;
+}
+
+// The replica's cube ids (ya::cube_id_of, clamped as grid_count_batched clamps it) and THE ORDER: sh_key[0 .. n)
+// ascending in (cube, id), by a bitonic sort of P = the power of two from n up keys (the padding sorts last).  Every
+// thread calls it; its barriers are log2(P) (log2(P) + 1) / 2 + 1, a function of n.  Returns whether one of THIS
+// thread's cells lay outside the grid.
+template<typename Pt>
+__device__ __forceinline__ bool grid_lds_order(const int n, const Pt* sh_in, const float cs, const int gs,
+    const int n_cubes, unsigned long long* sh_key)
+{
+    int P = 1;
+    while (P < n) P <<= 1;
+    bool outside = false;
+    // (the walk of the stage before has read the keys: the step's barriers lie in between)
+    for (int local = threadIdx.x; local < P; local += UPDATE_BLOCK) {
+        unsigned long long key = ~0ull;
+        if (local < n) {
+            const Pt p = sh_in[local];
+            int id = cube_id_of(p.x, p.y, p.z, cs, gs);
+            if (id < 0 || id >= n_cubes) {
+                outside = true;
+                id = id < 0 ? 0 : n_cubes - 1;
+            }
+            key = ((unsigned long long)(unsigned)id << 32) | (unsigned)local;
+        }
+        sh_key[local] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            // thread t's pair(s): a = the t-th index with bit j clear, its partner a + j; ascending where (a & k) == 0
+            for (int t = threadIdx.x; t < (P >> 1); t += UPDATE_BLOCK) {
+                const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const unsigned long long lo = sh_key[a], hi = sh_key[a + j];
+                if ((lo > hi) == ((a & k) == 0)) {
+                    sh_key[a] = hi;
+                    sh_key[a + j] = lo;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    return outside;
+}
+
+// offs[k] of the order: the number of cells whose cube is below k (the first slot of cube k), k in [0, n_cubes].
+__device__ __forceinline__ int grid_lds_lower_bound(const unsigned long long* sh_key, const int n, const int k)
+{
+    const unsigned long long first = (unsigned long long)(unsigned)k << 32;
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sh_key[mid] < first)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// build + grid_force_bits_batched for the replica in LDS: ONE thread per cell (the contract of `d_mes_nbs[i] += 1`;
+// thread t owns sorted slots t, t + 256, ...: a wavefront's lanes walk similar rows).  A cell in cube c walks the
+// stencil rows 0 .. 8 in ya::stencil_row_offset order, per row the slots [offs[clamp(c + off - 1)],
+// offs[clamp(c + off + 2)]) ascending, clamp(k) = min(max(k, 0), n_cubes) as in YA_ROW_BOUNDS; a candidate counts iff
+// dist2 < cut2, i == j included; a hit runs bits::pass' pair statements (the functors are inlined into kernels of
+// different shapes there and here, so the statements are written again rather than shared), the neighbour's old_v
+// from sh_v, ids ensemble-global.  by_plane: rows 0 - 2 and rows 3 - 8 each summed from +0, then added
+// (grid_force_bits_tile's whole-tile arithmetic).  No barrier in here.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
+    Pt* sh_rhs, const unsigned long long* sh_key, const int gs, const int n_cubes, const float cut2, const bool by_plane)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int NC = NF + 4;
+    for (int s = threadIdx.x; s < n; s += UPDATE_BLOCK) {
+        const unsigned long long mine = sh_key[s];
+        const int c = (int)(mine >> 32), local = (int)(unsigned)mine;
+        const int i = id_base + local;
+        const Pt Xi = sh_in[local];
+        Pt F = ya::zero<Pt>();
+        float3 sum_v{0.f, 0.f, 0.f};
+        float sum_friction = 0;
+        float own[NC];
+#pragma unroll
+        for (int k = 0; k < NC; k++) own[k] = 0.f;
+#pragma unroll 1
+        for (int row = 0; row < 9; row++) {
+            if (by_plane && row == 3) {  // the own plane's sums aside, the other two planes from +0
+#pragma unroll
+                for (int k = 0; k < NF; k++) own[k] = field(F, k);
+                own[NF] = sum_v.x, own[NF + 1] = sum_v.y, own[NF + 2] = sum_v.z, own[NF + 3] = sum_friction;
+                F = ya::zero<Pt>(), sum_v = float3{0.f, 0.f, 0.f}, sum_friction = 0;
+            }
+            const int off = stencil_row_offset(row, gs);
+            const int begin = grid_lds_lower_bound(sh_key, n, min(max(c + off - 1, 0), n_cubes));
+            const int end = grid_lds_lower_bound(sh_key, n, min(max(c + off + 2, 0), n_cubes));
+            for (int t = begin; t < end; t++) {
+                const int other = (int)(unsigned)sh_key[t];
+                const Pt Xj = sh_in[other];
+                if (dist2(Xi, Xj) < cut2) {
+                    const float3 vj = sh_v[other];
+                    const float4 v{vj.x, vj.y, vj.z, 0.f};
+                    Pt r = Xi - Xj;
+                    float dist = dist3(r.x, r.y, r.z);
+                    const int j = id_base + other;
+                    YA_CALL_INLINED F += pw_int(Xi, r, dist, i, j);
+                    pair_friction<Pt, pw_friction>(Xi, r, dist, i, j, v, sum_v, sum_friction);
+                }
+            }
+        }
+        if (by_plane) {  // S[dz = 0] + S[dz = -1, +1]
+#pragma unroll
+            for (int k = 0; k < NF; k++) field(F, k) = own[k] + field(F, k);
+            sum_v.x = own[NF] + sum_v.x, sum_v.y = own[NF + 1] + sum_v.y, sum_v.z = own[NF + 2] + sum_v.z;
+            sum_friction = own[NF + 3] + sum_friction;
+        }
+        store_rhs(sh_rhs, local, false, F, sum_v, sum_friction);
+    }
+}
+
+// n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS (dynamic LDS of
+// grid_lds_bytes<Pt>(n_max)): ya::ens::whole_steps_in_lds (ensemble.cuh) with a stage's forces = grid_lds_order +
+// grid_lds_walk of the stage's positions.  Bit for bit n_steps of the 14-launch take_step without generic forces.
+// Global memory: d_n[r] is read once; rows [0, n_r) of d_X and d_old_v are read at the start and written at the end;
+// at the end the grid arrays of the LAST stage's order, as the 14-launch path leaves them -- d_cube_id and d_point_id
+// for slots < n_r, all n_cubes + 1 of the replica's d_offs (threads stride over the cubes and search the order) -- and
+// YA_STATUS_OUT_OF_GRID in d_status[r] if a cell of any stage lay outside the grid (one atomic).  A replica with
+// n_r <= 0 gets the empty grid (offs all 0) and nothing else.  Nothing else is written: not the unused rows, not
+// d_n, not the right-hand-side arrays, not the build's private arrays (d_count stays zeroed for the next take_step).
+// Every barrier is reached by all 256 threads; the trip counts around them depend on n_r and n_steps only.
+// Not here: several lanes per cell (lanes_per_cell plays no part), Replica_links, the Gabriel form, the fast tier,
+// graph capture.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,
+    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
+    const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
+    int* __restrict__ d_status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char grid_step_lds[];
+    const int replica = blockIdx.x;
+    const int n = count_of(d_n, replica, n_max);
+    int* __restrict__ d_offs = d_offs_all + (size_t)replica * (n_cubes + 1);
+    if (n <= 0) {  // (the whole workgroup)
+        for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = 0;
+        return;
+    }
+    unsigned long long* sh_key = reinterpret_cast<unsigned long long*>(grid_step_lds + grid_lds_keys_base<Pt>(n_max));
+    const int id_base = replica * n_max;
+    bool outside = false;
+    whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
+        [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
+            outside |= grid_lds_order<Pt>(n, sh_in, cs, gs, n_cubes, sh_key);
+            grid_lds_walk<Pt, pw_int, pw_friction>(n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane);
+        });
+    // (the keys are the last stage's: its walk was followed by barriers, and nothing has written them since)
+    const size_t base = (size_t)replica * n_max;
+    for (int s = threadIdx.x; s < n; s += UPDATE_BLOCK) {
+        const unsigned long long key = sh_key[s];
+        d_cube_id_all[base + s] = (int)(key >> 32);
+        d_point_id_all[base + s] = (int)(unsigned)key;
+    }
+    for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = grid_lds_lower_bound(sh_key, n, c);
+    if (__syncthreads_or(outside) && threadIdx.x == 0) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
+}
+
+// Whether these launches beat the 14-launch step when the model leaves the choice to the engine
+// (Ensemble<Pt, Grid_solver>::lds_steps == 0).  THIS RULE IS A PLACEHOLDER until measured
+// (profiles/ensemble_grid_lds_steps_bench.json, tools/ensemble_bench.py --solver grid --lds-steps): one workgroup per
+// CU; below that the 14-launch path spreads a replica over more CUs.  (the two shapes probed so far lose.)
+inline bool lds_steps_pay(const int n_replicas, const int n_max, const int n_cubes)
+{
+    return n_replicas >= 256;
+}
+
 
 // What the ensembles of the grid-based solvers share (CRTP, between Stepper and Ensemble<Pt, Grid_solver> /
 // Ensemble<Pt, Gabriel_solver>): the per-replica grid arrays of this file's header, their build in four launches,
@@ -358,9 +576,64 @@ public:
     // (Grid_computer::stage_v_max: is the launch big enough to hide the L2's latency?)
     int stage_v_max = 130000;
 
+    // take_steps as launches that step from LDS (ya::ens::grid_lds_steps: one workgroup per replica): -1 = never,
+    // 1 = whenever the call is eligible, 0 (default) = the engine's choice, eligible and
+    // ya::ens::lds_steps_pay(n_replicas, n_max, n_cubes).  Eligible: no generic forces and
+    // n_max <= ya::ens::grid_lds_capacity<Pt>().  Any choice gives the same bits.
+    int lds_steps = 0;
+    // Such a launch runs at most this many steps (no single kernel runs unboundedly long); take_steps splits longer
+    // requests.
+    int lds_steps_max = 256;
+    // such launches made so far (which path ran)
+    long lds_step_launches = 0;
+
     Ensemble(int n_replicas, int n_max, int grid_size = 50, float cube_size = 1)
         : Base{"Grid_solver", n_replicas, n_max, grid_size, cube_size}
     {
+    }
+
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
+    }
+    // n_steps Heun steps of every replica, bit for bit n_steps calls of take_step: as launches of at most lds_steps_max
+    // steps each that step from LDS where the call is eligible and lds_steps allows it, as that loop otherwise.  After
+    // such launches the public grid arrays and d_status hold what the loop would have left; d_dX / d_X1 / d_dX1 and
+    // the build's private arrays are left as they were.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        const int n_max = this->n_max;
+        const bool eligible = ya::is_no_gen_forces<Pt>(gen_forces) && n_max <= ya::ens::grid_lds_capacity<Pt>();
+        const bool from_lds = eligible && (lds_steps > 0 || (lds_steps == 0 && ya::ens::lds_steps_pay(
+                                                                                  this->n_replicas, n_max, this->n_cubes)));
+        if (!from_lds) {
+            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
+            return;
+        }
+        assert(lds_steps_max >= 1);
+        const auto kernel = &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction>;
+        const size_t lds = ya::ens::grid_lds_bytes<Pt>(n_max);
+        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
+        static size_t lds_allowed = 64 * 1024;
+        if (lds > lds_allowed) {
+            YA_CHECK((int)hipFuncSetAttribute(
+                reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_allowed = lds;
+        }
+        const float cut2 = ya::cutoff_squared(this->cube_size);
+        for (int done = 0; done < n_steps;) {
+            const int k = n_steps - done < lds_steps_max ? n_steps - done : lds_steps_max;
+            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(n_max, this->d_n, dt, k,
+                this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v, this->cube_size,
+                this->grid_size, this->n_cubes, cut2, sum_order == YA_SUM_BY_PLANE, this->d_cube_id, this->d_point_id,
+                this->d_offs, this->d_status);
+            lds_step_launches++;
+            done += k;
+        }
+        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
+        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
     }
 
 protected:

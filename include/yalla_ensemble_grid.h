@@ -45,7 +45,10 @@ int ya_gens_copy_to_device(ya_gens* ens);       /* every row and every count */
  * with clear = 1 beforehand forgives it). */
 int ya_gens_copy_to_host(ya_gens* ens);
 
-/* n_steps calls of take_step<pw_int, pw_friction>(dt[, gen_forces]): queued, not waited for. */
+/* take_steps<pw_int, pw_friction>(dt, n_steps[, gen_forces]): n_steps calls of take_step, bit for bit; queued, not
+ * waited for.  Returns the number of launches that stepped from LDS (Ensemble<Pt, Grid_solver>::lds_step_launches
+ * rose by it): 0 unless "lds_steps" allows them and the call is eligible -- the model has no generic forces and
+ * n_max <= ya::ens::grid_lds_capacity<Pt>() (1024) -- else ceil(n_steps / "lds_steps_max"). */
 int ya_gens_take_steps(ya_gens* ens, float dt, int n_steps);
 int ya_gens_synchronize(ya_gens* ens);
 
@@ -69,7 +72,12 @@ int ya_gens_status(ya_gens* ens, int replica, int clear);
 int ya_gens_get_grid(ya_gens* ens, int replica, int* cube_id, int* point_id, int* cube_start, int* cube_end);
 
 /* "lanes": lanes_per_cell (0 = the engine's choice, 1, 4, 8, 16); "sum_order": 0 = YA_SUM_REFERENCE,
- * 1 = YA_SUM_BY_PLANE.  Neither changes a result's bits against the single system with the same sum_order. */
+ * 1 = YA_SUM_BY_PLANE.  Neither changes a result's bits against the single system with the same sum_order.
+ * "lds_steps": -1 (this harness's default) = ya_gens_take_steps always runs the 14 launches per step, 1 = launches of
+ * one workgroup per replica that step from LDS (ya::ens::grid_lds_steps) whenever the call is eligible, 0 = the
+ * engine's choice (ya::ens::lds_steps_pay); "lds_steps_max" (>= 1, default 256): the steps of one such launch.
+ * Neither changes a bit of the positions, old_v, the grid arrays or the status.  Any other value of a known name, and
+ * a known name on a NULL handle, is -3; an unknown name -2. */
 int ya_gens_set_param(ya_gens* ens, const char* name, double value);
 
 #pragma GCC visibility pop

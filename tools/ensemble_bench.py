@@ -8,6 +8,7 @@
     python tools/ensemble_bench.py --solver gabriel [--out profiles/ensemble_gabriel_bench.json]
     python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
     python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
+    python tools/ensemble_bench.py --solver grid --lds-steps [--out profiles/ensemble_grid_lds_steps_bench.json]
     python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
@@ -71,6 +72,9 @@ GRID_SHAPES = [(m, n) for n in (500, 2000, 10000, 50000) for m in (1, 8, 64, 512
 GRID_LANES = (0, 1, 4, 8, 16)
 WHOLE_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
 WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), "whole_256_steps_per_launch": (1, 256)}
+# --solver grid --lds-steps: one GridEnsemble("relu", M, n), (lds_steps, lds_steps_max)
+LDS_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096)]
+LDS_SETTINGS = {"fourteen_launches": (-1, 256), "lds_1_step_per_launch": (1, 1), "lds_256_steps_per_launch": (1, 256)}
 WHOLE_LANES_SHAPES = [(m, n) for n in (4, 16, 32, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)
                       if m * n * n <= 2 ** 28]
 LINKS_SHAPES = [(m, n) for n in (32, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
@@ -134,6 +138,10 @@ class Together:
     def whole(self, whole_steps, steps_per_launch):
         self.ens.set_param("whole_steps", whole_steps)
         self.ens.set_param("steps_per_launch", steps_per_launch)
+
+    def lds(self, lds_steps, lds_steps_max):
+        self.ens.set_param("lds_steps", lds_steps)
+        self.ens.set_param("lds_steps_max", lds_steps_max)
 
     def whole_lanes(self, lanes):
         self.ens.set_param("whole_step_lanes", lanes)
@@ -226,29 +234,61 @@ def measure(m, n, window, repeats):
     return row
 
 
-def measure_whole(m, n, window, repeats):
+def measure_whole(m, n, window, repeats, settings=None, apply=Together.whole, counter="whole_step_launches"):
+    """One ensemble, every setting of `settings` (the first is the baseline of the ratios) alternated."""
+    settings = WHOLE_SETTINGS if settings is None else settings
     b = Together(m, n)
     try:
         ks = {}
-        for key, setting in WHOLE_SETTINGS.items():
-            b.whole(*setting)
+        for key, setting in settings.items():
+            apply(b, *setting)
             b.steps(3)
             ks[key] = calibrate(b, window)
         samples = {key: [] for key in ks}
         for _ in range(repeats):  # six, whole 1, whole 256, six, ...
-            for key, setting in WHOLE_SETTINGS.items():
-                b.whole(*setting)
+            for key, setting in settings.items():
+                apply(b, *setting)
                 samples[key].append(timed(b, ks[key]))
-        launches = b.ens.whole_step_launches
+        launches = getattr(b.ens, counter)
     finally:
         b.close()
-    row = {"n_replicas": m, "n": n, "whole_step_launches": launches}
-    for key in WHOLE_SETTINGS:
+    row = {"n_replicas": m, "n": n, counter: launches}
+    if GRID:
+        row["grid_size"] = grid_size_for(n)
+    for key in settings:
         row[key] = summary(samples[key], m * n, ks[key])
-    for key in list(WHOLE_SETTINGS)[1:]:
-        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row["six_launches"]["cell_updates_per_s"]
-    row["spread"] = max(row[key]["spread"] for key in WHOLE_SETTINGS)  # of the worst side
+    baseline = list(settings)[0]
+    for key in list(settings)[1:]:
+        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row[baseline]["cell_updates_per_s"]
+    row["spread"] = max(row[key]["spread"] for key in settings)  # of the worst side
     return row
+
+
+def main_lds(args):
+    """--solver grid --lds-steps: launches that step from LDS against the 14-launch step of the same GridEnsemble."""
+    shapes = LDS_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting
+        run = Together(m, n)
+        for setting in LDS_SETTINGS.values():
+            run.lds(*setting)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure_whole(m, n, args.window, args.repeats, LDS_SETTINGS, Together.lds, "lds_step_launches"))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:10.1f} us/step" for key in LDS_SETTINGS)
+              + f"   ratios {r['ratio_lds_1_step_per_launch']:.2f} {r['ratio_lds_256_steps_per_launch']:.2f}"
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --solver grid --lds-steps", "model": "relu", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio": min(r["ratio_lds_256_steps_per_launch"] for r in rows),
+                      "max_ratio": max(r["ratio_lds_256_steps_per_launch"] for r in rows)}))
 
 
 def main_whole(args):
@@ -401,7 +441,16 @@ def main():
                     help="with --whole-steps: these whole_step_lanes settings against lanes 1 of the same Ensemble")
     ap.add_argument("--links", action="store_true",
                     help="ordered link forces (six launches, whole steps) against link_forces with atomics")
+    ap.add_argument("--lds-steps", action="store_true",
+                    help="with --solver grid: launches that step from LDS against the 14-launch step of the same ensemble")
     args = ap.parse_args()
+    global GRID, GABRIEL, LANES, SHAPES
+    if args.lds_steps:
+        if args.solver != "grid" or args.trace_shape or args.whole_steps or args.links:
+            ap.error("--lds-steps measures the grid ensemble (--solver grid) on its own")
+        GRID = True
+        main_lds(args)
+        return
     if args.links:
         if args.solver != "tile" or args.trace_shape or args.whole_steps:
             ap.error("--links measures the linked all-pairs ensemble on its own")
@@ -419,7 +468,6 @@ def main():
         else:
             main_whole(args)
         return
-    global GRID, GABRIEL, LANES, SHAPES
     if args.solver == "grid":
         GRID, LANES, SHAPES = True, GRID_LANES, GRID_SHAPES
     if args.solver == "gabriel":

@@ -28,19 +28,31 @@ using ens_harness::Model;
 
 // What the grid form adds to the shared interface.
 struct Base : public Grid_replicas {
-    virtual void take_steps(float dt, int n_steps) = 0;
+    virtual long take_steps(float dt, int n_steps) = 0;  // returns the launches that stepped from LDS
     virtual void set_lanes(int lanes) = 0;
     virtual void set_sum_order(int order) = 0;
+    virtual void set_lds_steps(int mode) = 0;
+    virtual void set_lds_steps_max(int steps) = 0;
 };
 
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
 struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
-    using Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>::Grid_replicas_of;
     using Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>::cells;
-    void take_steps(float dt, int n_steps) override
+    // the harness's own default: the 14-launch step, so that every caller runs what it ran before "lds_steps" existed
+    template<typename... Args>
+    explicit Sim(Args... args) : Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>{args...}
     {
-        ens_harness::step_by_step<Pt, pw_int, pw_friction, Policy>(cells, dt, n_steps);
+        cells.lds_steps = -1;
     }
+    long take_steps(float dt, int n_steps) override
+    {
+        Policy::before_steps(cells.n_max);
+        const long before = cells.lds_step_launches;
+        cells.template take_steps<pw_int, pw_friction>(dt, n_steps, Policy::gen(cells.n_replicas, cells.n_max));
+        return cells.lds_step_launches - before;
+    }
+    void set_lds_steps(int mode) override { cells.lds_steps = mode; }
+    void set_lds_steps_max(int steps) override { cells.lds_steps_max = steps; }
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
     void set_sum_order(int order) override { cells.sum_order = order ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE; }
 };
@@ -88,7 +100,7 @@ int ya_gens_get_h_n(ya_gens* e, int r) { return ens_harness::get_h_n(*e->p, r); 
 int ya_gens_get_d_n(ya_gens* e, int r) { return ens_harness::get_d_n(*e->p, r); }
 int ya_gens_copy_to_device(ya_gens* e) { return ens_harness::copy_to_device(*e->p); }
 int ya_gens_copy_to_host(ya_gens* e) { return ens_harness::copy_to_host(*e->p); }
-int ya_gens_take_steps(ya_gens* e, float dt, int n_steps) { return ens_harness::take_steps(*e->p, dt, n_steps); }
+int ya_gens_take_steps(ya_gens* e, float dt, int n_steps) { return (int)e->p->take_steps(dt, n_steps); }
 int ya_gens_synchronize(ya_gens*) { return ens_harness::synchronize(); }
 int ya_gens_set_fixed(ya_gens* e, int mode, int local_point)
 {
@@ -105,19 +117,29 @@ int ya_gens_get_grid(ya_gens* e, int r, int* cube_id, int* point_id, int* cube_s
 int ya_gens_set_param(ya_gens* e, const char* name, double v)
 {
     if (!name) return -3;
-    if (std::string(name) == "lanes") {
+    const std::string which = name;
+    if (which != "lanes" && which != "sum_order" && which != "lds_steps" && which != "lds_steps_max") return -2;
+    if (!e) return -3;
+    if (which == "lds_steps") {
+        if (v != -1 && v != 0 && v != 1) return -3;
+        e->p->set_lds_steps((int)v);
+        return 0;
+    }
+    if (which == "lds_steps_max") {
+        if (!(v >= 1 && v <= 0x7fffffff) || v != (double)(int)v) return -3;
+        e->p->set_lds_steps_max((int)v);
+        return 0;
+    }
+    if (which == "lanes") {
         const int lanes = (int)v;
         if (lanes != 0 && lanes != 1 && lanes != 4 && lanes != 8 && lanes != 16) return -3;
         e->p->set_lanes(lanes);
         return 0;
     }
-    if (std::string(name) == "sum_order") {
-        const int order = (int)v;
-        if (order != 0 && order != 1) return -3;
-        e->p->set_sum_order(order);
-        return 0;
-    }
-    return -2;
+    const int order = (int)v;  // "sum_order"
+    if (order != 0 && order != 1) return -3;
+    e->p->set_sum_order(order);
+    return 0;
 }
 
 }  // extern "C"

@@ -117,7 +117,8 @@ struct Grid_replicas_of : public Replicas_of<Cells, Interface> {
     const int* d_point_id() override { return cells.d_point_id; }
     const int* d_offs() override { return cells.d_offs; }
 };
-// The two grid forms' take_steps: one take_step per step, the policy's generic force in each.
+// The Gabriel form's take_steps: one take_step per step, the policy's generic force in each (the grid form's goes
+// through Ensemble<Pt, Grid_solver>::take_steps, which is that loop unless "lds_steps" allows launches from LDS).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy,
     typename Cells>
 void step_by_step(Cells& cells, float dt, int n_steps)
@@ -193,7 +194,7 @@ inline int copy_to_host(Replicas& s)
     s.copy_to_host();
     return 0;
 }
-// (the two grid forms'; the all-pairs take_steps returns a count)
+// (the Gabriel form's; the all-pairs and the grid take_steps return a count)
 template<typename Interface>
 int take_steps(Interface& s, float dt, int n_steps)
 {

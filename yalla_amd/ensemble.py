@@ -25,7 +25,7 @@ otherwise), 0 leaves it to the engine: one lane unless the model's functors are 
 largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice gives the same bits.
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
-build per stage always; `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh);
+build per stage (or whole steps from LDS, `lds_steps`); `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh);
 `LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh).
 """
 import ctypes as C
@@ -195,6 +195,12 @@ class GridEnsemble(Ensemble):
     set_param("lanes", 0 | 1 | 4 | 8 | 16) / set_param("sum_order", 0 | 1).
 
     Every stage scans n_replicas * grid_size**3 counters: pick grid_size to fit the replicas, not 50.
+
+    `set_param("lds_steps", 1)` lets `take_step(dt, steps)` run as launches of one workgroup per replica that step
+    from LDS (ya::ens::grid_lds_steps: up to `set_param("lds_steps_max", k)` steps per launch, no counters, nothing of
+    size grid_size**3 touched in between) wherever the model has no generic forces and n_max is at most 1024; 0 leaves
+    the choice to the engine, -1 (this harness's default) never does.  The bits are the same either way, grid arrays
+    and status included; `lds_step_launches` counts the launches made.
     """
     _PREFIX, _LOADER, _NOUN = "ya_gens_", "grid_ensemble_lib", "grid ensemble"
 
@@ -213,6 +219,12 @@ class GridEnsemble(Ensemble):
     @property
     def whole_step_launches(self):
         raise AttributeError("a grid ensemble has no whole-step launches")
+
+    @property
+    def lds_step_launches(self):
+        """Launches that stepped from LDS so far (Ensemble<Pt, Grid_solver>::lds_step_launches): 0 unless
+        set_param("lds_steps", 0 | 1) allowed them and the call was eligible."""
+        return self._whole_step_launches
 
     def status(self, r, clear=True):
         bits = self._f("status")(self._h, int(r), int(bool(clear)))
@@ -251,6 +263,10 @@ class GabrielEnsemble(GridEnsemble):
     @gabriel_coefficient.setter
     def gabriel_coefficient(self, value):
         _check(self._f("set_param")(self._h, b"gabriel_coefficient", float(value)), "set gabriel_coefficient")
+
+    @property
+    def lds_step_launches(self):
+        raise AttributeError("a Gabriel ensemble has no launches that step from LDS")
 
     def dense_cells(self):
         """Blocking read: how many cells, over all replicas, the last force stage left to the dense kernel."""
