@@ -12,6 +12,7 @@ namespace ya {
 //   (floor(x/cs) + gs/2) + (floor(y/cs) + gs/2)*gs + (floor(z/cs) + gs/2)*gs*gs
 __device__ __forceinline__ int cube_id_of(float x, float y, float z, float cs, int gs)
 {
+#pragma clang fp contract(off)  // (also where the translation unit contracts: the fast tier's update kernels bin)
     const float half = (float)(gs / 2);
     const float fgs = (float)gs;
     float fx = floorf(x / cs) + half;

@@ -58,6 +58,7 @@
 #include "cudebug.cuh"
 #include "dtypes.cuh"
 #include "fold256.cuh"
+#include "grid_bin.cuh"
 #include "yalla_hip.h"
 
 // Model files use thrust::fill / reduce on their own arrays and rely on the
@@ -2079,41 +2080,54 @@ __device__ __forceinline__ Pt heun_row(const int i, const float dt, const float*
 //                 generic forces that will add to it (a memset launch less)
 //   pred_partial  (totals source) the largest |z moved| weighted by band, the drift guard of a z-slab
 //                 (ya::block_max_to)
-template<typename Pt, ya::Fix_src S>
+//   BIN           (a carried step, d_sorted given): the lane also bins the entry it stores, slot i, into the grid
+//                 `bin` names (ya::bin_entry), so that the rebuild from these entries needs no k_bin launch
+//                 (ya_grid_rebuild_sorted_binned); an instance without BIN holds none of that code
+//   TILES         (a carried step) the workgroup takes TILES x UPDATE_BLOCK consecutive slots, thread t the slots
+//                 base + UPDATE_BLOCK j + t, one round after the other: the fold of the partial sums, which every
+//                 workgroup repeats, then runs in 1 / TILES as many of them.  Launch ceil(n / (TILES UPDATE_BLOCK)).
+template<typename Pt, ya::Fix_src S, bool BIN = false, int TILES = 1>
 __global__ __launch_bounds__(ya::UPDATE_BLOCK) void euler_step(const int n, const float dt, const ya::Fix_args fix_args,
     const Pt* __restrict__ d_dX, const Pt* __restrict__ d_X0, Pt* __restrict__ d_X1, const Pt* __restrict__ d_dX_sorted,
     ya::Entry<Pt>* __restrict__ d_sorted, const int n_active, Pt* __restrict__ d_zero, float* __restrict__ pred_partial,
-    const ya::Guard_band band, ya::Entry<Pt>* __restrict__ d_sorted_out = nullptr)
+    const ya::Guard_band band, ya::Entry<Pt>* __restrict__ d_sorted_out = nullptr, const ya::Grid_bin bin = {})
 {
+    static_assert(TILES == 1 || S == ya::Fix_src::partials, "block_max_to is called once per workgroup");
     const float3 fix = ya::resolve_fix<S, Pt>(fix_args, n);
-    const int i = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (i == 0 && fix_args.out) {
-        fix_args.out[0] = fix.x;
-        fix_args.out[1] = fix.y;
-        fix_args.out[2] = fix.z;
-    }
-    float moved = 0.f;
-    if (i < n) {
-        if (d_X1) {
-            const Pt X0 = d_X0[i];
-            const Pt X1 = X0 + ya::minus_fix(d_dX[i], fix) * dt;
-            d_X1[i] = X1;
-            moved = fabsf(X1.z - X0.z) * band.weight(X0.z);
+#pragma unroll
+    for (int tile = 0; tile < TILES; tile++) {
+        const int i = (blockIdx.x * TILES + tile) * ya::UPDATE_BLOCK + threadIdx.x;
+        if (i == 0 && fix_args.out) {
+            fix_args.out[0] = fix.x;
+            fix_args.out[1] = fix.y;
+            fix_args.out[2] = fix.z;
         }
-        if (d_sorted) {
-            ya::Entry<Pt> e = d_sorted[i];
-            Pt dX = d_dX_sorted[i];
-            if constexpr (S == ya::Fix_src::totals)
-                if (e.id >= n_active) dX = d_dX[e.id];
-            const float z0 = e.X.z;
-            e.X = e.X + ya::minus_fix(dX, fix) * dt;
-            (d_sorted_out ? d_sorted_out : d_sorted)[i] = e;
-            moved = fabsf(e.X.z - z0) * band.weight(z0);
+        float moved = 0.f;
+        [[maybe_unused]] float3 at{0.f, 0.f, 0.f};  // BIN: where the entry of slot i is now
+        if (i < n) {
+            if (d_X1) {
+                const Pt X0 = d_X0[i];
+                const Pt X1 = X0 + ya::minus_fix(d_dX[i], fix) * dt;
+                d_X1[i] = X1;
+                moved = fabsf(X1.z - X0.z) * band.weight(X0.z);
+            }
+            if (d_sorted) {
+                ya::Entry<Pt> e = d_sorted[i];
+                Pt dX = d_dX_sorted[i];
+                if constexpr (S == ya::Fix_src::totals)
+                    if (e.id >= n_active) dX = d_dX[e.id];
+                const float z0 = e.X.z;
+                e.X = e.X + ya::minus_fix(dX, fix) * dt;
+                (d_sorted_out ? d_sorted_out : d_sorted)[i] = e;
+                moved = fabsf(e.X.z - z0) * band.weight(z0);
+                if constexpr (BIN) at = float3{e.X.x, e.X.y, e.X.z};
+            }
+            if (d_zero) d_zero[i] = ya::zero<Pt>();
         }
-        if (d_zero) d_zero[i] = ya::zero<Pt>();
+        if constexpr (S == ya::Fix_src::totals)
+            if (pred_partial) ya::block_max_to(moved, pred_partial);
+        if constexpr (BIN) ya::bin_entry(bin, i < n, i, at.x, at.y, at.z);  // (every lane: shuffles, a ballot)
     }
-    if constexpr (S == ya::Fix_src::totals)
-        if (pred_partial) ya::block_max_to(moved, pred_partial);
 }
 
 // The corrector X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v (solvers.cuh:127-144): fix is the first stage's
@@ -2148,23 +2162,33 @@ __global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step(const int n, const
 // at d_slot2[s], where the second build put the cell (near s: cells move little).  Same operands and statements
 // as heun_step (ya::heun_update).  Leaves {X, id} and {old_v, 0} in slot s of d_out / d_out_v, from which the
 // next step's first build starts, and -- the call's last step: d_X, d_old_v given -- the id-ordered arrays.
-template<typename Pt>
+// BIN: the lane also bins the entry it leaves in slot s for that next build (ya::bin_entry, as euler_step's);
+// whole wavefronts reach the binning, so no lane leaves early.  TILES: as euler_step's.
+template<typename Pt, bool BIN = false, int TILES = 1>
 __global__ __launch_bounds__(ya::UPDATE_BLOCK) void heun_step_sorted(const int n, const float dt,
     const float* __restrict__ d_fix, const ya::Fix_args fix1_args, const ya::Entry<Pt>* __restrict__ d_sorted,
     const Pt* __restrict__ d_dX_sorted, const int* __restrict__ d_slot2, const Pt* __restrict__ d_dX1_sorted,
-    ya::Entry<Pt>* __restrict__ d_out, float4* __restrict__ d_out_v, Pt* __restrict__ d_X, float3* __restrict__ d_old_v)
+    ya::Entry<Pt>* __restrict__ d_out, float4* __restrict__ d_out_v, Pt* __restrict__ d_X, float3* __restrict__ d_old_v,
+    const ya::Grid_bin bin = {})
 {
     const float3 fix1 = ya::resolve_fix<ya::Fix_src::partials, Pt>(fix1_args, n);
-    const int s = blockIdx.x * ya::UPDATE_BLOCK + threadIdx.x;
-    if (s >= n) return;
-    ya::Entry<Pt> e = d_sorted[s];
-    const float3 v = ya::heun_update(e.X, d_dX_sorted[s], d_dX1_sorted[d_slot2[s]],
-        float3{d_fix[0], d_fix[1], d_fix[2]}, fix1, dt);
-    d_out[s] = e;
-    d_out_v[s] = make_float4(v.x, v.y, v.z, 0.f);
-    if (d_X) {
-        d_X[e.id] = e.X;
-        d_old_v[e.id] = v;
+    const float3 fix{d_fix[0], d_fix[1], d_fix[2]};
+#pragma unroll
+    for (int tile = 0; tile < TILES; tile++) {
+        const int s = (blockIdx.x * TILES + tile) * ya::UPDATE_BLOCK + threadIdx.x;
+        [[maybe_unused]] float3 at{0.f, 0.f, 0.f};  // BIN: where the entry of slot s is now
+        if (s < n) {
+            ya::Entry<Pt> e = d_sorted[s];
+            const float3 v = ya::heun_update(e.X, d_dX_sorted[s], d_dX1_sorted[d_slot2[s]], fix, fix1, dt);
+            d_out[s] = e;
+            d_out_v[s] = make_float4(v.x, v.y, v.z, 0.f);
+            if (d_X) {
+                d_X[e.id] = e.X;
+                d_old_v[e.id] = v;
+            }
+            if constexpr (BIN) at = float3{e.X.x, e.X.y, e.X.z};
+        }
+        if constexpr (BIN) ya::bin_entry(bin, s < n, s, at.x, at.y, at.z);
     }
 }
 
@@ -2462,6 +2486,16 @@ public:
     // take_steps: false = always the loop of take_step (A/B, tests; same results)
     bool carry_sorted = true;
     long carried_steps = 0;  // read-only: steps whose first build started from the step before's cube-sorted cells
+    // carried steps: the update kernels bin the entries they store (euler_step / heun_step_sorted<BIN>), and the
+    // rebuild behind them runs without k_bin; false = k_bin as before (A/B, tests; same results)
+    bool bin_in_update = true;
+    // ... and those rebuilds whose public point ids nobody can read skip storing them (YA_REBUILD_PRIVATE);
+    // false = every rebuild stores them (A/B; same results).  Only with bin_in_update.
+    bool trim_carried_stores = true;
+    // ... and their workgroups take four tiles of UPDATE_BLOCK slots each (euler_step / heun_step_sorted<TILES>);
+    // false = one (A/B; same results).  Only with bin_in_update.
+    bool four_tile_updates = true;
+    long fused_bin_rebuilds = 0;  // read-only: rebuilds that ran without k_bin, 2 k - 1 per carried call of k steps
 
 protected:
 #ifndef YA_GRAPH_MAX_CELLS
@@ -2824,24 +2858,70 @@ protected:
             return true;
         }
         const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
+        // bin_in_update: every rebuild of the call (stage 2, and stage 1 of steps 2 .. k) bins the entries that
+        // the update kernel in front of it has just stored, so that kernel bins them itself and the rebuild runs
+        // without k_bin.  INVARIANT: the grid's count[] is zero between builds only because a scan follows every
+        // binning (k_scan zeroes it in passing).  The predictor's binning is scanned by stage 2's rebuild, a
+        // corrector's by the next step's stage 1 -- so the call's LAST corrector, behind which this call queues
+        // no rebuild, must not bin.  The public point ids and the next build's visit order are read after the
+        // call only: every rebuild but the last step's stage 2 leaves them unwritten (YA_REBUILD_PRIVATE).
+        const bool fuse = bin_in_update;
+        const ya::Grid_bin bin = fuse ? Computer<Pt>::bin_target() : ya::Grid_bin{};
+        const unsigned quiet = fuse && trim_carried_stores ? YA_REBUILD_PRIVATE : 0u;
+        // four_tile_updates (with bin_in_update): a workgroup of the update kernels takes four tiles of slots, so
+        // the fold of the partial sums that each of them repeats runs in a quarter as many
+        const auto launch = [&](auto tiles, auto kernel_of, auto... args) {
+            constexpr int T = decltype(tiles)::value;
+            const int wgs = (n + T * ya::UPDATE_BLOCK - 1) / (T * ya::UPDATE_BLOCK);
+            kernel_of(tiles)<<<wgs, ya::UPDATE_BLOCK, 0, this->stream>>>(args...);
+        };
+        const auto tiled = [&](auto kernel_of, auto... args) {
+            if (four_tile_updates)
+                launch(std::integral_constant<int, 4>{}, kernel_of, args...);
+            else
+                launch(std::integral_constant<int, 1>{}, kernel_of, args...);
+        };
+        const auto predict = [&](const int n, const float dt, const ya::Fix_args fix, const ya::Grid_bin bin) {
+            tiled([](auto t) { return euler_step<Pt, Fix::partials, true, decltype(t)::value>; }, n, dt, fix,
+                (const Pt*)d_dX, (const Pt*)d_X, (Pt*)nullptr, Computer<Pt>::sorted_rhs(), Computer<Pt>::sorted_cells(),
+                n, (Pt*)nullptr, (float*)nullptr, ya::Guard_band{}, Computer<Pt>::carried_cells(), bin);
+        };
+        const auto correct = [&](auto binning, const int n, const float dt, const ya::Fix_args fix1, Pt* X_by_id,
+                                 float3* v_by_id, const ya::Grid_bin bin) {
+            tiled([](auto t) { return heun_step_sorted<Pt, decltype(binning)::value, decltype(t)::value>; }, n, dt,
+                (const float*)d_mean_first, fix1, (const ya::Entry<Pt>*)Computer<Pt>::sorted_cells(),
+                Computer<Pt>::sorted_rhs(), Computer<Pt>::carried_slots(), Computer<Pt>::carried_rhs(),
+                Computer<Pt>::carried_cells(), Computer<Pt>::carried_v(), X_by_id, v_by_id, bin);
+        };
         for (int s = 0; s < k; s++) {
+            const bool last = s == k - 1;
             int n_partials = 0;
             if (s == 0)
                 Computer<Pt>::template pwints<pw_int, pw_friction>(n, d_X, d_old_v, d_dX, false, n, true);
             else
-                Computer<Pt>::template pwints_carried<pw_int, pw_friction>(1, n, d_dX);
+                Computer<Pt>::template pwints_carried<pw_int, pw_friction>(1, n, d_dX, fuse, quiet);
             YA_CHECK(ya_reduce_partials(d_dX, n_floats, n, d_workspace, &n_partials, this->stream));
-            euler_step<Pt, Fix::partials><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt,
-                ya::Fix_args{d_workspace, n_partials, d_mean_first}, d_dX, d_X, nullptr, Computer<Pt>::sorted_rhs(),
-                Computer<Pt>::sorted_cells(), n, nullptr, nullptr, ya::Guard_band{}, Computer<Pt>::carried_cells());
-            Computer<Pt>::template pwints_carried<pw_int, pw_friction>(2, n, d_dX1);
+            const ya::Fix_args fix{d_workspace, n_partials, d_mean_first};
+            if (fuse)
+                predict(n, dt, fix, bin);
+            else
+                euler_step<Pt, Fix::partials><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, fix, d_dX, d_X,
+                    nullptr, Computer<Pt>::sorted_rhs(), Computer<Pt>::sorted_cells(), n, nullptr, nullptr,
+                    ya::Guard_band{}, Computer<Pt>::carried_cells());
+            Computer<Pt>::template pwints_carried<pw_int, pw_friction>(2, n, d_dX1, fuse, last ? 0u : quiet);
             YA_CHECK(ya_reduce_partials(d_dX1, n_floats, n, d_workspace, &n_partials, this->stream));
-            const bool last = s == k - 1;
-            heun_step_sorted<Pt><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, d_mean_first,
-                ya::Fix_args{d_workspace, n_partials}, Computer<Pt>::sorted_cells(), Computer<Pt>::sorted_rhs(),
-                Computer<Pt>::carried_slots(), Computer<Pt>::carried_rhs(), Computer<Pt>::carried_cells(),
-                Computer<Pt>::carried_v(), last ? d_X : nullptr, last ? d_old_v : nullptr);
+            const ya::Fix_args fix1{d_workspace, n_partials};
+            if (fuse && !last)  // (the invariant above)
+                correct(std::true_type{}, n, dt, fix1, nullptr, nullptr, bin);
+            else if (fuse)
+                correct(std::false_type{}, n, dt, fix1, d_X, d_old_v, ya::Grid_bin{});
+            else
+                heun_step_sorted<Pt><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, d_mean_first, fix1,
+                    Computer<Pt>::sorted_cells(), Computer<Pt>::sorted_rhs(), Computer<Pt>::carried_slots(),
+                    Computer<Pt>::carried_rhs(), Computer<Pt>::carried_cells(), Computer<Pt>::carried_v(),
+                    last ? d_X : nullptr, last ? d_old_v : nullptr);
         }
+        if (fuse) fused_bin_rebuilds += 2 * k - 1;
         stage1_fix = d_mean_first;
         sorted_stage_cells = -1;
         rhs_zeroed[0] = rhs_zeroed[1] = 0;
@@ -2888,7 +2968,8 @@ protected:
     // no cube order to carry from step to step (Heun_solver::take_steps)
     bool carry_ready(int) { return false; }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void pwints_carried(int, int, Pt*) {}
+    void pwints_carried(int, int, Pt*, bool, unsigned) {}
+    ya::Grid_bin bin_target() { return {}; }
     ya::Entry<Pt>* carried_cells() { return nullptr; }
     float4* carried_v() { return nullptr; }
     const Pt* carried_rhs() const { return nullptr; }
@@ -2985,6 +3066,23 @@ public:
     {
         YA_CHECK(ya_grid_rebuild_sorted_map(handle, d_prev, sizeof(ya::Entry<Pt>), sizeof(Pt),
             d_prev_v, n, cube_size, d_sorted, d_sorted_v, d_slot_of_prev, stream));
+    }
+    // rebuild_sorted without its binning launch, for entries that the caller's own kernels have binned
+    // (ya::bin_entry into bin_target()) since this grid's last build: exactly these n, each once, in storage order,
+    // with this cube size (ya_grid_rebuild_sorted_binned's precondition).  flags: YA_REBUILD_*.
+    template<typename Pt>
+    void rebuild_sorted_binned(const int n, const ya::Entry<Pt>* d_prev, const float4* d_prev_v,
+        const float cube_size, ya::Entry<Pt>* d_sorted, float4* d_sorted_v, hipStream_t stream, int* d_slot_of_prev,
+        const unsigned flags)
+    {
+        YA_CHECK(ya_grid_rebuild_sorted_binned(handle, d_prev, sizeof(ya::Entry<Pt>), sizeof(Pt), d_prev_v, n,
+            cube_size, d_sorted, d_sorted_v, d_slot_of_prev, flags, stream));
+    }
+    ya_grid_bin_target bin_target()
+    {
+        ya_grid_bin_target t{};
+        YA_CHECK(ya_grid_bin_target_get(handle, &t));
+        return t;
     }
     const int* offsets() const { return d_offs; }
     // The ids the last build saw mean other cells now (Solution::renumber): the next build visits
@@ -3463,17 +3561,23 @@ protected:
     bool carry_refused = false;
     // stage 1 of a carried step after the call's first: from the corrector's output, as stage 2 starts from
     // the predictor's; stage 2: from the predicted entries, with the slot map and the sorted right-hand sides
+    // binned: the update kernel in front has binned d_carried's entries into bin_target() with this cube size
+    // (Grid::rebuild_sorted_binned's precondition); flags: YA_REBUILD_*
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void pwints_carried(const int stage, const int n, Pt* d_dX)
+    void pwints_carried(const int stage, const int n, Pt* d_dX, const bool binned, const unsigned flags)
     {
-        if (stage == 1) {
-            grid.rebuild_sorted(n, d_carried, d_resorted_v, cube_size, d_sorted, d_sorted_v, stream);
-            forces<pw_int, pw_friction>(n, d_sorted, d_sorted_v, d_dX, false, n, d_dX_sorted);
-        } else {
-            grid.rebuild_sorted(n, d_carried, d_sorted_v, cube_size, d_resorted, d_resorted_v, stream, d_carried_slots);
-            forces<pw_int, pw_friction>(n, d_resorted, d_resorted_v, d_dX, false, n, d_carried_rhs);
-        }
+        const float4* prev_v = stage == 1 ? d_resorted_v : d_sorted_v;
+        ya::Entry<Pt>* out = stage == 1 ? d_sorted : d_resorted;
+        float4* out_v = stage == 1 ? d_sorted_v : d_resorted_v;
+        int* slots = stage == 1 ? nullptr : d_carried_slots;
+        if (binned)
+            grid.rebuild_sorted_binned(n, d_carried, prev_v, cube_size, out, out_v, stream, slots, flags);
+        else
+            grid.rebuild_sorted(n, d_carried, prev_v, cube_size, out, out_v, stream, slots);
+        forces<pw_int, pw_friction>(n, out, out_v, d_dX, false, n, stage == 1 ? d_dX_sorted : d_carried_rhs);
     }
+    // where the update kernels of a carried step bin (the cube size is the one the rebuilds are given)
+    ya::Grid_bin bin_target() { return ya::Grid_bin{grid.bin_target(), cube_size}; }
     ya::Entry<Pt>* carried_cells() { return d_carried; }
     float4* carried_v() { return d_resorted_v; }
     const Pt* carried_rhs() const { return d_carried_rhs; }

@@ -29,7 +29,7 @@ extern "C" {
 /* The libraries are built with -fvisibility=hidden; only this C ABI is exported. */
 #pragma GCC visibility push(default)
 
-#define YA_ABI_VERSION 10  /* 10: + ya_grid_build_sorted_begin_publish; 9: + ya_comm_info, ya_reduce_partials; 8: + ya_grid_set_cube_range, YA_STATUS_OUT_OF_RANGE, the slab guard / fixed point / payload entries, ya_async_read_* */
+#define YA_ABI_VERSION 10  /* 10: + ya_grid_build_sorted_begin_publish (and, added under 10 since: ya_grid_rebuild_sorted_map, ya_grid_bin_target_get, ya_grid_rebuild_sorted_binned); 9: + ya_comm_info, ya_reduce_partials; 8: + ya_grid_set_cube_range, YA_STATUS_OUT_OF_RANGE, the slab guard / fixed point / payload entries, ya_async_read_* */
 
 /* Status bits reported by ya_grid_status(). */
 #define YA_STATUS_OUT_OF_GRID 1 /* a cell's cube id fell outside [0, n_cubes):
@@ -159,6 +159,35 @@ int ya_grid_rebuild_sorted(ya_grid* g, const void* d_prev_sorted, size_t entry_b
 int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
     size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
     void* d_sorted_v_out, int* d_slot_of_prev, void* stream);
+
+/* Binning done by the caller's own kernels (added under ABI version 10, as ya_grid_rebuild_sorted_map was).
+ * A kernel that has a cell's new position in a register can bin it there and then -- ya::bin_entry,
+ * include/grid_bin.cuh, the device text k_bin itself runs -- instead of leaving that to a k_bin launch that
+ * reads the position back.  ya_grid_bin_target_get hands out what such a lane needs of the opaque grid; the
+ * pointers are stable for the grid's life, the cube range is the one set at the time of the call. */
+typedef struct ya_grid_bin_target {
+    int* d_cube_of; /* [n_max] cube id of the entry in storage slot s */
+    int* d_rank;    /* [n_max] its arrival rank in that cube's counter */
+    int* d_count;   /* one counter per cube; zero between builds (every scan leaves it so) */
+    int* d_status;  /* YA_STATUS_* bits */
+    int grid_size, n_cubes, range_lo, range_hi;
+} ya_grid_bin_target;
+int ya_grid_bin_target_get(ya_grid* g, ya_grid_bin_target* out);
+/* ya_grid_rebuild_sorted_map without its binning launch.  PRECONDITION: since the grid's last scan (the last
+ * build or rebuild of any kind) exactly these n entries of d_prev_sorted have been binned through
+ * ya_grid_bin_target, each once, entry s into d_cube_of[s] / d_rank[s], in storage order and with this
+ * cube_size, by work queued earlier in `stream` -- and nothing else has.  A cell binned twice or a binning
+ * that no scan follows leaves count[] wrong for every later build of this grid.  Same outputs as
+ * ya_grid_rebuild_sorted_map, except under
+ *   YA_REBUILD_PRIVATE  d_point_id and the visit order of the next build by id are NOT written (8 bytes per
+ *                       cell): for a rebuild whose public arrays nobody reads before a later rebuild WITHOUT
+ *                       the flag of the same n cells writes them again; d_cube_id, d_cube_start, d_cube_end
+ *                       and the outputs are written as ever.
+ * Other flag bits are refused. */
+#define YA_REBUILD_PRIVATE 1u
+int ya_grid_rebuild_sorted_binned(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
+    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
+    void* d_sorted_v_out, int* d_slot_of_prev, unsigned flags, void* stream);
 
 /* A build visits the cells in the previous build's sorted order (they move little between builds:
  * neighbouring lanes then bin into neighbouring counters).  After the caller has given the cells

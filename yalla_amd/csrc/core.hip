@@ -39,6 +39,7 @@
 
 #include "cube_id.cuh"
 #include "fold256.cuh"
+#include "grid_bin.cuh"
 #include "yalla_hip.h"
 
 namespace {
@@ -97,35 +98,13 @@ __global__ __launch_bounds__(BLOCK) void k_bin(const float* __restrict__ X,
             for (int k = 3; k < stash_f; k++) out[k] = p[k];
         }
         id = cube_id_of(x, y, z, cs, gs);
-        if (id < 0 || id >= n_cubes) {
-            atomicOr(status, YA_STATUS_OUT_OF_GRID);
-            id = id < 0 ? 0 : n_cubes - 1;
-        }
-        // ya_grid_set_cube_range: the caller promised cube ids in [range_lo, range_hi) and the
-        // prefix sum only covers those; a cell outside is reported and kept inside (memory-safe)
-        if (id < range_lo || id >= range_hi) {
-            atomicOr(status, YA_STATUS_OUT_OF_RANGE);
-            id = id < range_lo ? range_lo : range_hi - 1;
-        }
     }
-    // Wave-aggregated counting: in visit order equal cube ids sit in adjacent
-    // lanes, so each run of equal ids issues ONE atomic (by its first lane, for
-    // the run length) instead of one per lane on the same counter.  Any
-    // arrival order inside a cube is fine: k_order restores ascending ids.
-    const int lane = threadIdx.x & 63;
-    const int id_before = __shfl_up(id, 1, 64);
-    const bool head = lane == 0 || id != id_before;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = heads & (~0ULL >> (63 - lane));          // heads in lanes <= lane
-    const unsigned long long after = lane == 63 ? 0ULL : heads & (~0ULL << (lane + 1));
-    const int head_lane = 63 - __builtin_clzll(upto);
-    const int run_end = after ? __builtin_ctzll(after) : 64;
-    int base = 0;
-    if (head && id >= 0) base = atomicAdd(&count[id], run_end - lane);
-    base = __shfl(base, head_lane, 64);
+    // the clamps, the status bits and the wave-aggregated count: ya::bin_lane (include/grid_bin.cuh), which
+    // every lane calls
+    const int arrival = ya::bin_lane(i, id, n_cubes, range_lo, range_hi, count, status);
     if (s < n_visit) {
         cube_of[s] = id;  // -1: nothing to visit at this position
-        rank[s] = base + (lane - head_lane);
+        rank[s] = arrival;
     }
 }
 
@@ -335,8 +314,12 @@ __global__ __launch_bounds__(BLOCK) void k_order_from(const int* __restrict__ ar
     int smaller = 0;
     for (int t = a; t < b; t++) smaller += arrival_pid[t] < p;
     const int dst = a + smaller;
-    point_id[dst] = p;
-    next_prev_pid[dst] = p;
+    // (point_id == NULL, YA_REBUILD_PRIVATE: a rebuild inside a call whose public arrays and visit order nobody
+    // reads before a later rebuild of the same call writes them)
+    if (point_id) {
+        point_id[dst] = p;
+        next_prev_pid[dst] = p;
+    }
     unsigned w[EW];
 #pragma unroll
     for (int k = 0; k < EW; k++) w[k] = mine[k];
@@ -1191,9 +1174,11 @@ int ya_grid_rebuild_sorted(ya_grid* g, const void* d_prev_sorted, size_t entry_b
         d_sorted_out, d_sorted_v_out, nullptr, stream);
 }
 
-int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
-    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
-    void* d_sorted_v_out, int* d_slot_of_prev, void* stream)
+// binned: the caller's kernels have binned these n entries since the last scan (ya_grid_rebuild_sorted_binned),
+// so no k_bin; flags: YA_REBUILD_*
+static int rebuild_from(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes, size_t point_bytes,
+    const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out, void* d_sorted_v_out,
+    int* d_slot_of_prev, bool binned, unsigned flags, void* stream)
 {
     if (!g || n < 0 || n > g->n_max || point_bytes < 12 || entry_bytes < point_bytes + 4 ||
         entry_bytes % 4 || point_bytes % 4 || !d_prev_sorted || !d_prev_sorted_v || !d_sorted_out ||
@@ -1203,13 +1188,16 @@ int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t ent
     const int entry_f = (int)(entry_bytes / 4);
     const int nb = ceil_div(n, BLOCK);
     // cells are read in the order they are stored: visit = identity (n_prev = 0)
-    if (n > 0)
+    if (n > 0 && !binned)
         k_bin<<<nb, BLOCK, 0, st>>>((const float*)d_prev_sorted, entry_f, n, cube_size, g->grid_size,
             g->n_cubes, g->d_prev_pid, 0, g->d_cube_of, g->d_rank, g->d_count, g->d_status,
             nullptr, 0, nullptr, g->range_lo, g->range_hi);
     launch_scan(g, n, nullptr, st);
     if (n > 0) {
         const int id_word = (int)(point_bytes / 4);
+        const bool is_private = (flags & YA_REBUILD_PRIVATE) != 0;
+        int* const point_id = is_private ? nullptr : g->d_point_id;
+        int* const next_prev_pid = is_private ? nullptr : g->d_prev_pid;
         k_scatter<<<nb, BLOCK, 0, st>>>(g->d_cube_of, g->d_rank, g->d_offs, n, g->d_prev_pid, 0,
             g->d_arrival, g->d_cube_id, g->d_arrival_src, (const unsigned*)d_prev_sorted, entry_f,
             id_word, nullptr);
@@ -1217,7 +1205,7 @@ int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t ent
     case EW:                                                                                 \
         k_order_from<EW><<<nb, BLOCK, 0, st>>>(g->d_arrival, g->d_arrival_src, g->d_cube_id, \
             g->d_offs, n, (const unsigned*)d_prev_sorted, (const float4*)d_prev_sorted_v,    \
-            g->d_point_id, g->d_prev_pid, (unsigned*)d_sorted_out, (float4*)d_sorted_v_out,  \
+            point_id, next_prev_pid, (unsigned*)d_sorted_out, (float4*)d_sorted_v_out,       \
             d_slot_of_prev);                                                                 \
         break;
         switch (entry_f) {
@@ -1245,6 +1233,37 @@ int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t ent
     }
     g->n_prev = n;
     return (int)hipGetLastError();
+}
+
+int ya_grid_rebuild_sorted_map(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
+    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
+    void* d_sorted_v_out, int* d_slot_of_prev, void* stream)
+{
+    return rebuild_from(g, d_prev_sorted, entry_bytes, point_bytes, d_prev_sorted_v, n, cube_size, d_sorted_out,
+        d_sorted_v_out, d_slot_of_prev, false, 0, stream);
+}
+
+int ya_grid_rebuild_sorted_binned(ya_grid* g, const void* d_prev_sorted, size_t entry_bytes,
+    size_t point_bytes, const void* d_prev_sorted_v, int n, float cube_size, void* d_sorted_out,
+    void* d_sorted_v_out, int* d_slot_of_prev, unsigned flags, void* stream)
+{
+    if (flags & ~(unsigned)YA_REBUILD_PRIVATE) return (int)hipErrorInvalidValue;
+    return rebuild_from(g, d_prev_sorted, entry_bytes, point_bytes, d_prev_sorted_v, n, cube_size, d_sorted_out,
+        d_sorted_v_out, d_slot_of_prev, true, flags, stream);
+}
+
+int ya_grid_bin_target_get(ya_grid* g, ya_grid_bin_target* out)
+{
+    if (!g || !out) return (int)hipErrorInvalidValue;
+    out->d_cube_of = g->d_cube_of;
+    out->d_rank = g->d_rank;
+    out->d_count = g->d_count;
+    out->d_status = g->d_status;
+    out->grid_size = g->grid_size;
+    out->n_cubes = g->n_cubes;
+    out->range_lo = g->range_lo;
+    out->range_hi = g->range_hi;
+    return 0;
 }
 
 int ya_grid_build(ya_grid* g, const void* d_X, size_t stride_bytes, int n, float cube_size,

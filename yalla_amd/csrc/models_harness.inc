@@ -53,6 +53,7 @@ struct Sim_base {
     virtual long graph_launches() { return -1; }
 #if YA_IS_DEVICE
     virtual long carried_steps() = 0;
+    virtual long fused_bin_rebuilds() = 0;
 #endif
     // z-slab decomposition (Grid_solver models only)
     virtual int slab_init(float, float, float, const int*) { return -2; }
@@ -716,6 +717,18 @@ struct Sim : public Sim_base {
             cells.carry_sorted = v != 0;
             return 0;
         }
+        if (std::string(name) == "bin_in_update") {  // Heun_solver::bin_in_update (A/B, tests; same results)
+            cells.bin_in_update = v != 0;
+            return 0;
+        }
+        if (std::string(name) == "four_tile_updates") {  // Heun_solver::four_tile_updates (A/B; same results)
+            cells.four_tile_updates = v != 0;
+            return 0;
+        }
+        if (std::string(name) == "trim_carried_stores") {  // Heun_solver::trim_carried_stores (A/B; same results)
+            cells.trim_carried_stores = v != 0;
+            return 0;
+        }
 #endif
 #ifndef YA_ORACLE
         if (std::string(name) == "links_segmented_min") {  // ya::links_segmented_min(), process-wide
@@ -771,6 +784,7 @@ struct Sim : public Sim_base {
     }
 #if YA_IS_DEVICE
     long carried_steps() override { return cells.carried_steps; }
+    long fused_bin_rebuilds() override { return cells.fused_bin_rebuilds; }
 #endif
 #ifdef YA_ORACLE
     int set_reduce_order(int order) override
@@ -1038,6 +1052,10 @@ long ya_sim_graph_launches(ya_sim* s) { return s->p->graph_launches(); }
 // first grid build started from the step before's cube-sorted cells (Heun_solver::carried_steps): k - 1 per
 // qualifying ya_sim_take_steps call of k steps, 0 for everything that ran as the loop of take_step.
 __attribute__((visibility("default"))) long ya_sim_carried_steps(ya_sim* s) { return s->p->carried_steps(); }
+// The same kind of hook: the grid rebuilds of this system so far that ran without a k_bin launch because the update
+// kernel in front of them had binned their entries (Heun_solver::fused_bin_rebuilds): 2 k - 1 per carried call of
+// k steps while bin_in_update is on, 0 otherwise.
+__attribute__((visibility("default"))) long ya_sim_fused_bin_rebuilds(ya_sim* s) { return s->p->fused_bin_rebuilds(); }
 #endif
 
 }  // extern "C"

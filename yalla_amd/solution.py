@@ -181,6 +181,16 @@ class Solution:
         fn.restype, fn.argtypes = C.c_long, [C.c_void_p]
         return fn(self._h)
 
+    def fused_bin_rebuilds(self):
+        """Grid rebuilds so far that ran without a binning launch, their entries binned by the update kernel in
+        front of them (2 k - 1 per carried `take_step(dt, k)` while the parameter `bin_in_update` is on; -1 where
+        the library has no such counter, as the oracle)."""
+        fn = getattr(self.lib, "ya_sim_fused_bin_rebuilds", None)
+        if fn is None:
+            return -1
+        fn.restype, fn.argtypes = C.c_long, [C.c_void_p]
+        return fn(self._h)
+
     def profile(self, enable, every=1):
         """Time every `every`-th launch of the force kernel with HIP events."""
         return self.lib.ya_sim_profile(self._h, int(every) if enable else 0)
