@@ -27,8 +27,9 @@ exist, a sum_order flip 0 -> 1 between the first and the second step, a cell cou
 and comes back while the graph captured for it is alive.
 
 Models: every model of the harness whose functors use + - * / sqrt fma only and whose sums have a fixed order.
-Left out: springs_links_grid (link forces accumulate with atomics on the device, in no fixed order: tolerance
-only, tests/test_parity_gpu.py::test_links_parity), models with libm functors (sorting, branching, passive
+Left out: springs_links_grid (at its default threshold the link forces accumulate with atomics on the device, in no
+fixed order; tests/native/test_links_sums.cu and tests/test_links_order_gpu.py hold both link paths, bit for bit
+wherever the order is fixed or does not matter, and a model added to MODELS would change every drawn session), models with libm functors (sorting, branching, passive
 growth: lock-step 1e-5 tests cover them), slab sessions (tests/fuzz_slab.py).
 
 A session in which the ORACLE goes non-finite or (grid, Gabriel) comes within two cubes of the grid's edge is no

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ensemble_support import DT, bits, largest_slots, links_lds_bytes, seeded_rows  # noqa: E402
 from ensemble_support import LINKED_MODELS as MODELS  # noqa: E402
 from ensemble_support import LINKED_N_FLOATS as N_FLOATS  # noqa: E402
-from test_reference_statement_numpy import f32, fma32  # noqa: E402
+from links_support import reference_linked_steps  # noqa: E402
 
 from yalla_amd.ensemble import LinkedEnsemble, YallaError  # noqa: E402
 from yalla_amd.solution import Solution  # noqa: E402
@@ -246,53 +246,6 @@ def test_hubs_against_the_cpu_restatement(oracle):
 
 
 # ---- the numpy statement -------------------------------------------------------------------------------------------
-def reference_linked_steps(X, links, strength, steps, dt, p):
-    """tests/test_reference_statement_numpy.reference_tile_steps with the link terms added before the pairwise sum:
-    per stage L = 0; for every link in slot order (a == b skipped) r = Y[a] - Y[b], dist = sqrtf(fmaf(z, z, fmaf(y,
-    y, x x))), f = strength r / dist, L[a] += -f, L[b] += f (links.cuh linear_force); the right-hand side is
-    L + F (store_rhs on what the generic forces left), then the friction term."""
-    n = len(X)
-    X = X.copy()
-    old_v = np.zeros((n, 3), f32)
-    dt, strength = f32(dt), f32(strength)
-
-    def rhs(Y):
-        L = np.zeros((n, 3), f32)
-        for a, b in links:
-            if a == b:
-                continue
-            r = Y[a] - Y[b]
-            dist = np.sqrt(fma32(r[2], r[2], fma32(r[1], r[1], f32(r[0] * r[0]))))
-            f = (strength * r) / dist
-            L[a] = L[a] + (-f)
-            L[b] = L[b] + f
-        dX = np.zeros((n, 3), f32)
-        for i in range(n):
-            F, sv, sf = np.zeros(3, f32), np.zeros(3, f32), f32(0)
-            for k in range(n):
-                r = Y[i] - Y[k]
-                dist = np.sqrt(fma32(r[2], r[2], fma32(r[1], r[1], f32(r[0] * r[0]))))
-                if k != i:
-                    F = F + (r * (f32(0.5) - dist)) * f32(np.float64(1.0) / np.float64(dist))
-                    if dist < f32(1.0):
-                        sf = sf + f32(1)
-                        sv = sv + old_v[k]
-            dX[i] = L[i] + F
-            if sf > 0:
-                dX[i] = dX[i] + sv / sf
-        return dX
-
-    for _ in range(steps):
-        dX = rhs(X)
-        dX = dX - dX[p]
-        X1 = X + dX * dt
-        dX1 = rhs(X1)
-        dX1 = dX1 - dX1[p]
-        X = X + ((dX + dX1) * f32(0.5)) * dt
-        old_v = (dX + dX1) * f32(0.5)
-    return X, old_v
-
-
 @pytest.mark.parametrize("whole", [1, -1])
 def test_against_a_numpy_statement_of_the_step(whole):
     """springs_links, 40 cells, 60 slots: random links with a hub, a doubled link and a self-link, 3 steps of dt 0.05

@@ -66,6 +66,17 @@ def test_link_forces_with_cell_ids_beyond_2_to_24():
 
 
 @pytest.mark.gpu
+def test_link_forces_sums_slot_order_and_segment_cuts():
+    """Links::link_forces at force level, the atomics kernel and the segmented sum: lattice inputs whose sums are
+    exact in any order against integer arithmetic with memcmp (n_max around the block edge, hub segments of 255 ..
+    513 entries on, before and behind the cut every 256 entries, inert links, *d_n set from the host and lowered by a
+    kernel right before the call, float4 and Po_cell, the scratch buffers from call to call, a custom Link_force),
+    and random inputs against a host binary32 statement of the sorted, cut sum bit for bit where the order is fixed,
+    against binary64 within a derived bound where it is not."""
+    run("test_links_sums", "ALL LINK SUM TESTS PASSED")
+
+
+@pytest.mark.gpu
 def test_one_line_declares_a_functor_stateless():
     """YA_STATELESS(Pt, functor) next to a model's functor: Grid_solver at 10 000 cells and
     Tile_solver at 800 pick the several-lanes-per-cell kernels by themselves -- bit-identical

@@ -327,6 +327,29 @@ def test_links_segmented_sum_matches_atomics_and_oracle(oracle, device):
             s.set_param("links_segmented_min", 1000000)
     assert_close_positions(res["oracle"], res["atomics"])
     assert_close_positions(res["oracle"], res["segmented"])
+    # The hub case run to run: a cell in at most two pieces gets the same bits every time (one plain store, or two
+    # atomics on the zeroed right-hand side, which commute); only the hub's three and more pieces may land in another
+    # order.  Read where nothing of the hub has spread yet: a step of dt = 0 leaves the first stage's right-hand side in
+    # old_v, the fixed cell one of those in one piece.
+    from links_support import pieces_per_cell
+    pieces = pieces_per_cell(pairs, n)
+    assert pieces[17] >= 3 and (pieces >= 3).sum() == 1 and (pieces == 2).sum() >= 5
+    fixed = int(np.flatnonzero(pieces == 1)[0])
+    rhs = []
+    try:
+        for _ in range(2):
+            with Solution("springs_links_grid", n, 50, 1.0, lib=device) as s:
+                s.set_param("links_segmented_min", 1)
+                s.random_sphere(0.5, 42)
+                s.set_links(pairs, 0.2)
+                s.set_fixed(fixed)
+                s.take_step(0.0, 1)
+                rhs.append(s.old_v()[:n])
+    finally:
+        with Solution("springs_links_grid", 8, 50, 1.0, lib=device) as s:
+            s.set_param("links_segmented_min", 1000000)
+    assert np.abs(rhs[0]).max() > 0.1
+    assert np.array_equal(rhs[0][pieces <= 2].view(np.uint32), rhs[1][pieces <= 2].view(np.uint32))
     # without a hub every cell's sum has a fixed order: the run repeats bit for bit
     # (the atomics' order, and so their rounding, need not)
     plain = rng.integers(0, n, size=(5000, 2))
