@@ -14,6 +14,8 @@ NATIVE = os.path.join(ROOT, "tests", "native_ensemble")
 DT = 0.05
 # the all-pairs models whose steps can run whole (no generic forces); `push` must fall back
 WHOLE = ["springs", "clipped", "fading", "relu", "relu_po", "oscillator"]
+# the rows of user-written frictions in the three unlinked harnesses' tables (tests/test_friction_functors_gpu.py steps them)
+FRICTION_MODELS = ["friction_ids", "friction_ids_plain", "friction_field"]
 LINKED_MODELS = ["links", "links4", "springs_links", "relu_links", "relu_po_links"]
 LINKED_N_FLOATS = {"links": 3, "links4": 4, "springs_links": 3, "relu_links": 3, "relu_po_links": 5}
 

@@ -93,12 +93,20 @@ def wall_relu_force(Xi, r, dist, i, j):                          # examples/grow
     return np.where(keep[..., None], out, f32(0)).astype(f32)
 
 
-def friction_w_neighbour(dist, i, j):                            # solvers.cuh:26-33
+def friction_w_neighbour(dist, i, j, Xi=None, r=None):           # solvers.cuh:26-33
     return np.where((i != j) & (dist < f32(1)), f32(1), f32(0)).astype(f32)
 
 
-def friction_on_background(dist, i, j):
+def friction_on_background(dist, i, j, Xi=None, r=None):
     return np.zeros(dist.shape, f32)
+
+
+def _user_friction(name):
+    """A user-written friction of tests/friction_statement.py (Xi and r with every field of the point)."""
+    def pw_friction(dist, i, j, Xi, r):
+        import friction_statement
+        return friction_statement.FRICTIONS[name](Xi, r, dist, i, j)
+    return pw_friction
 
 
 # relu_plain_gabriel: the same functor, not declared stateless on the device (another kernel body, the same
@@ -109,8 +117,13 @@ MODELS = {"relu_gabriel": (relu_force, friction_w_neighbour),
           "relu_po_gabriel": (relu_force, friction_w_neighbour),
           "relu_cell_gabriel": (relu_force, friction_w_neighbour),
           "clipped_gabriel": (clipped_spring, friction_w_neighbour),
-          "wall_gabriel": (wall_relu_force, friction_on_background)}
-WIDTH = {"relu_po_gabriel": 5, "relu_cell_gabriel": 7}
+          "wall_gabriel": (wall_relu_force, friction_on_background),
+          # user-written frictions (yalla_amd/csrc/model_functors.h), declared and not: the same numbers
+          "friction_graded_gabriel": (relu_force, _user_friction("graded")),
+          "friction_ids_gabriel": (relu_force, _user_friction("ids")),
+          "friction_ids_plain_gabriel": (relu_force, _user_friction("ids")),
+          "friction_field_gabriel": (relu_force, _user_friction("field"))}
+WIDTH = {"relu_po_gabriel": 5, "relu_cell_gabriel": 7, "friction_field_gabriel": 5}
 
 _memo = {}
 
@@ -182,6 +195,7 @@ def _rhs(X, gs, coefficient, model, old_v, gen):
     n = len(X)
     width = X.shape[1]
     assert width == WIDTH.get(model, 3)
+    rows = np.ascontiguousarray(X, f32)                           # (every field: what a friction may read)
     X = np.ascontiguousarray(X[:, :3], f32)
     if gen is not None:
         assert width == 3
@@ -197,7 +211,7 @@ def _rhs(X, gs, coefficient, model, old_v, gen):
         dm = np.where(on, dist[:, m], f32(1))
         r = (X - X[jj]).astype(f32)
         F = np.where(on[:, None], F + pw_int(X, r, dm, i, j), F)
-        fr = pw_friction(dm, i, j)
+        fr = pw_friction(dm, i, j, rows, (rows - rows[jj]).astype(f32))
         sf = np.where(on, sf + fr, sf)
         if old_v is not None:
             sv = np.where(on[:, None], sv + fr[:, None] * old_v[jj], sv)

@@ -4,7 +4,7 @@ import ctypes
 import os
 
 import pytest
-from ensemble_support import ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported
+from ensemble_support import FRICTION_MODELS, ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported
 
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble.so")
 
@@ -23,7 +23,7 @@ def test_only_the_ensemble_c_abi_is_exported():
 def test_the_model_table():
     from yalla_amd import ensemble
     names = ensemble.models()
-    assert names == ["springs", "clipped", "fading", "relu", "relu_po", "oscillator", "push"]
+    assert names == ["springs", "clipped", "fading", "relu", "relu_po", "oscillator", "push"] + FRICTION_MODELS
     check_models_name_bounds(ensemble._ffi.ensemble_lib().ya_ens_models_name, len(names))
 
 

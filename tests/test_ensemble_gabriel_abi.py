@@ -4,7 +4,7 @@ import ctypes
 import os
 
 import pytest
-from ensemble_support import (ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported,
+from ensemble_support import (FRICTION_MODELS, ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported,
                               declared_functions)
 
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble_gabriel.so")
@@ -34,7 +34,7 @@ def test_the_model_table():
     from yalla_amd import GabrielEnsemble, GridEnsemble, ensemble
     assert issubclass(GabrielEnsemble, GridEnsemble)   # grid(r), status(r) and the cube_size setter come with it
     names = ensemble.gabriel_models()
-    assert names == MODELS
+    assert names == MODELS + FRICTION_MODELS
     check_models_name_bounds(ensemble._ffi.gabriel_ensemble_lib().ya_gabens_models_name, len(names))
 
 

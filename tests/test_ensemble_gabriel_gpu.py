@@ -88,8 +88,9 @@ class GabrielLockstep(Lockstep):
 
 def test_the_models_are_those_of_the_gabriel_harness():
     from yalla_amd import models as single_models
-    assert gabriel_models() == MODELS
-    assert all(m + "_gabriel" in single_models() for m in MODELS if m != "clipped_push")
+    from ensemble_support import FRICTION_MODELS
+    assert gabriel_models() == MODELS + FRICTION_MODELS
+    assert all(m + "_gabriel" in single_models() for m in MODELS + FRICTION_MODELS if m != "clipped_push")
 
 
 def test_the_mixed_input_is_what_it_says():

@@ -29,8 +29,9 @@ def counts_for(m):
 
 def test_the_models_are_those_of_the_tile_harness():
     from yalla_amd import models as tile_models
-    assert models() == MODELS
-    assert all(m + "_tile" in tile_models() for m in MODELS)
+    from ensemble_support import FRICTION_MODELS
+    assert models() == MODELS + FRICTION_MODELS
+    assert all(m + "_tile" in tile_models() for m in MODELS + FRICTION_MODELS)
 
 
 @pytest.mark.parametrize("m", [1, 3, 64, 257])

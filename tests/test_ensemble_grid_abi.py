@@ -4,7 +4,7 @@ import ctypes
 import os
 
 import pytest
-from ensemble_support import ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported
+from ensemble_support import FRICTION_MODELS, ROOT, check_abi, check_models_name_bounds, check_only_the_c_abi_is_exported
 
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble_grid.so")
 MODELS = ["springs", "clipped", "fading", "relu", "relu_po", "relu_cell", "push", "clipped_push"]
@@ -25,7 +25,7 @@ def test_only_the_grid_ensemble_c_abi_is_exported():
 def test_the_model_table():
     from yalla_amd import GridEnsemble, ensemble  # noqa: F401  (the package exports the class)
     names = ensemble.grid_models()
-    assert names == MODELS
+    assert names == MODELS + FRICTION_MODELS
     check_models_name_bounds(ensemble._ffi.grid_ensemble_lib().ya_gens_models_name, len(names))
 
 

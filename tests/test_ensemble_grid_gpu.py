@@ -65,8 +65,9 @@ def against_singles(model, counts, n_max, grid_size, dt, steps, seed=0, rows=Non
 
 def test_the_models_are_those_of_the_grid_harness():
     from yalla_amd import models as single_models
-    assert grid_models() == MODELS
-    assert all(m + "_grid" in single_models() for m in MODELS)
+    from ensemble_support import FRICTION_MODELS
+    assert grid_models() == MODELS + FRICTION_MODELS
+    assert all(m + "_grid" in single_models() for m in MODELS + FRICTION_MODELS)
 
 
 @pytest.mark.parametrize("m", [1, 3, 33])

@@ -70,6 +70,11 @@ static const Model<Base* (*)(int, int)> model_table[] = {
     YA_ENSEMBLE_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
     YA_ENSEMBLE_MODEL("oscillator", float4, oscillator_by_local_id, friction_w_neighbour<float4>, Oscillator_ids),
     YA_ENSEMBLE_MODEL("push", float3, models::no_pw_int<float3>, friction_w_neighbour<float3>, Push_gen<float3>),
+    // user-written frictions (model_functors.h; tests/test_friction_functors_gpu.py): ids through local ids
+    // (ensemble_harness.h), declared and `_plain`, and field on the wide point
+    YA_ENSEMBLE_MODEL("friction_ids", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction>, ens_harness::Local_friction_ids),
+    YA_ENSEMBLE_MODEL("friction_ids_plain", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction_plain>, ens_harness::Local_friction_ids),
+    YA_ENSEMBLE_MODEL("friction_field", Po_cell, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 

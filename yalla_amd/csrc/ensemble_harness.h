@@ -39,6 +39,26 @@ struct Push_gen {
     static void before_steps(int) {}
 };
 
+// A friction that reads its ids' VALUES (models::ids_friction), for an ensemble: the functors of an ensemble get
+// global ids (r * n_max + local), so the ensemble's model hands the friction the local ones (as ensemble.hip's
+// oscillator_by_local_id does for a force): the same statements, hence the bits of the lone model in every replica.
+// n_max travels in a device variable of the library, set when it changes.
+__device__ int friction_rows_per_replica = 1;
+template<Pairwise_friction<float3> friction>
+__device__ inline float friction_by_local_id(float3 Xi, float3 r, float dist, int i, int j)
+{
+    return friction(Xi, r, dist, i % friction_rows_per_replica, j % friction_rows_per_replica);
+}
+struct Local_friction_ids : public No_gen<float3> {
+    static void before_steps(int n_max)
+    {
+        static int rows_set = 1;
+        if (rows_set == n_max) return;
+        YA_CHECK((int)hipMemcpyToSymbol(HIP_SYMBOL(friction_rows_per_replica), &n_max, sizeof(int)));
+        rows_set = n_max;
+    }
+};
+
 // THE INTERFACES.  What every form exposes to its C functions, and what the two all-pairs and the two grid forms
 // add.  A grid form's take_steps and a form's own setters are declared by the interface each .hip derives from one
 // of these.
@@ -293,3 +313,6 @@ inline int get_grid(Grid_replicas& s, int r, int* cube_id, int* point_id, int* c
 }
 
 }  // namespace ens_harness
+
+// (the wrapper of the declared name is declared as that name is; the `_plain` twin's is not)
+YA_STATELESS_FRICTION(float3, ens_harness::friction_by_local_id<models::ids_friction>)

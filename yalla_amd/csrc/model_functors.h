@@ -113,6 +113,59 @@ __device__ inline float3 fading_spring(float3 Xi, float3 r, float dist, int i, i
     return dF;
 }
 
+// --- friction functors of the tests (NOT reference models; tests/test_friction_functors.py and its GPU twin).  The
+// two default frictions return 0 or 1 and look at i and j through `i == j` only; these do neither.  Each body is
+// written once and has two names: the first is listed under YA_STATELESS_FRICTION at the end of this file, the
+// `_plain` one is NOT, on purpose (as relu_force / relu_plain): beside relu_force the friction's declaration alone
+// decides between the several-lane and the one-lane kernel bodies, and both must give the same bits.  No libm call,
+// no binary64 constant; the coefficients keep sum_friction exact, or its smallest positive value away from 0.
+// graded: fractional and distance-dependent, continuous at the cut-off, a self term (sum_friction >= 0.25).
+template<typename Pt>
+__device__ inline float graded_friction_body(Pt Xi, Pt r, float dist, int i, int j)
+{
+    if (i == j) return 0.25f;
+    return dist < 1.f ? 1.f - dist : 0.f;
+}
+// ids: asymmetric in i and j, changed by any id offset that is no multiple of 8, signed eighths from -0.25 to 0.625
+// (sums are exact; they may be negative, or zero from non-zero terms), the self term included.
+__device__ inline float ids_friction_body(float3 Xi, float3 r, float dist, int i, int j)
+{
+    if (!(dist < 1.f)) return 0.f;
+    return 0.125f * float(((5 * i + 2 * j) & 7) - 2);
+}
+// field: reads a non-position field of r and one of Xi.
+__device__ inline float field_friction_body(Po_cell Xi, Po_cell r, float dist, int i, int j)
+{
+    if (i == j || !(dist < 1.f)) return 0.f;
+    return 0.25f + 0.5f * fminf(1.f, fabsf(r.theta)) + 0.25f * fminf(1.f, fabsf(Xi.phi));
+}
+template<typename Pt>
+__device__ inline float graded_friction(Pt Xi, Pt r, float dist, int i, int j)
+{
+    return graded_friction_body(Xi, r, dist, i, j);
+}
+template<typename Pt>
+__device__ inline float graded_friction_plain(Pt Xi, Pt r, float dist, int i, int j)
+{
+    return graded_friction_body(Xi, r, dist, i, j);
+}
+__device__ inline float ids_friction(float3 Xi, float3 r, float dist, int i, int j)
+{
+    return ids_friction_body(Xi, r, dist, i, j);
+}
+__device__ inline float ids_friction_plain(float3 Xi, float3 r, float dist, int i, int j)
+{
+    return ids_friction_body(Xi, r, dist, i, j);
+}
+__device__ inline float field_friction(Po_cell Xi, Po_cell r, float dist, int i, int j)
+{
+    return field_friction_body(Xi, r, dist, i, j);
+}
+__device__ inline float field_friction_plain(Po_cell Xi, Po_cell r, float dist, int i, int j)
+{
+    return field_friction_body(Xi, r, dist, i, j);
+}
+
 // --- sorting: examples/sorting.cu:9-28 (differential adhesion between two cell
 // types; the first half of the ids is the strongly adhering type).  n_cells is
 // a compile-time constant in the example and a model parameter here. -----------
@@ -487,4 +540,18 @@ YA_STATELESS(float3, relu_force<float3>)
 YA_STATELESS(Po_cell, relu_force<Po_cell>)
 YA_STATELESS(Cell, relu_force<Cell>)
 YA_STATELESS(Cell, models::epi_turing_mes_noturing)
+// (the `_plain` twins of these three are not listed: see there)
+YA_STATELESS_FRICTION(float3, models::graded_friction<float3>)
+YA_STATELESS_FRICTION(float3, models::ids_friction)
+YA_STATELESS_FRICTION(Po_cell, models::field_friction)
+// what picks the kernels (ya::stateless_pair), held at compile time: the declared names count, their twins do not
+static_assert(ya::stateless_pair<float3, relu_force<float3>, models::graded_friction<float3>>() &&
+                  !ya::stateless_pair<float3, relu_force<float3>, models::graded_friction_plain<float3>>(),
+    "graded_friction is declared stateless, graded_friction_plain is not");
+static_assert(ya::stateless_pair<float3, relu_force<float3>, models::ids_friction>() &&
+                  !ya::stateless_pair<float3, relu_force<float3>, models::ids_friction_plain>(),
+    "ids_friction is declared stateless, ids_friction_plain is not");
+static_assert(ya::stateless_pair<Po_cell, relu_force<Po_cell>, models::field_friction>() &&
+                  !ya::stateless_pair<Po_cell, relu_force<Po_cell>, models::field_friction_plain>(),
+    "field_friction is declared stateless, field_friction_plain is not");
 #endif

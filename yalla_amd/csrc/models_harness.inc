@@ -882,6 +882,23 @@ static const Model model_table[] = {
     YA_MODEL("count_gabriel", float3, GABRIEL, models::count_neighbours, friction_w_neighbour<float3>, Count_gen),
     YA_MODEL("relu_po_gabriel", Po_cell, GABRIEL, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
     YA_MODEL("relu_cell_gabriel", Cell, GABRIEL, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
+    // user-written frictions (model_functors.h: graded, ids, field) beside the declared relu_force, so that the
+    // friction's YA_STATELESS_FRICTION line alone decides the kernel body: the declared name gets the several-lane
+    // bodies, its `_plain` twin the one-lane ones (tests/test_friction_functors*.py).  The fewest rows that reach
+    // every body; graded sits beside fading_spring, whose force does not jump at the cut-off (the fast tier's row).
+    YA_MODEL("friction_graded_tile", float3, false, relu_force<float3>, models::graded_friction<float3>, No_gen<float3>),
+    YA_MODEL("friction_ids_tile", float3, false, relu_force<float3>, models::ids_friction, No_gen<float3>),
+    YA_MODEL("friction_ids_plain_tile", float3, false, relu_force<float3>, models::ids_friction_plain, No_gen<float3>),
+    YA_MODEL("friction_field_tile", Po_cell, false, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
+    YA_MODEL("friction_field_plain_tile", Po_cell, false, relu_force<Po_cell>, models::field_friction_plain, No_gen<Po_cell>),
+    YA_MODEL("friction_graded_fading_grid", float3, true, models::fading_spring, models::graded_friction<float3>, No_gen<float3>),
+    YA_MODEL("friction_ids_grid", float3, true, relu_force<float3>, models::ids_friction, No_gen<float3>),
+    YA_MODEL("friction_ids_plain_grid", float3, true, relu_force<float3>, models::ids_friction_plain, No_gen<float3>),
+    YA_MODEL("friction_field_grid", Po_cell, true, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
+    YA_MODEL("friction_graded_gabriel", float3, GABRIEL, relu_force<float3>, models::graded_friction<float3>, No_gen<float3>),
+    YA_MODEL("friction_ids_gabriel", float3, GABRIEL, relu_force<float3>, models::ids_friction, No_gen<float3>),
+    YA_MODEL("friction_ids_plain_gabriel", float3, GABRIEL, relu_force<float3>, models::ids_friction_plain, No_gen<float3>),
+    YA_MODEL("friction_field_gabriel", Po_cell, GABRIEL, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
     YA_MODEL_EXTRA
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
