@@ -176,7 +176,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     const int blocks_per_replica, const int* __restrict__ d_n, const Entry<Pt>* __restrict__ sorted_all,
     const float4* __restrict__ sorted_v_all, const int* __restrict__ cube_id_all, const int* __restrict__ offs_all,
     const int gs, const int n_cubes, const float cut2, Pt* __restrict__ d_dX_all, const bool has_gen,
-    const bool by_plane)
+    const bool by_plane, const int pass_facts)
 {
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     // (tiles in storage order: which workgroup serves which tile changes no result)
     grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, false, OFF32>(n, w.block, (int)base, -1, 0, sorted_all + base,
         sorted_v_all + base, cube_id_all + base, offs_all + (size_t)w.replica * (n_cubes + 1), gs, n_cubes, cut2,
-        d_dX_all + base, has_gen, n, nullptr, nullptr, nullptr, nullptr, by_plane);
+        d_dX_all + base, has_gen, n, nullptr, nullptr, nullptr, nullptr, by_plane, pass_facts);
 }
 
 // ya::grid_force_coop for every replica at once: a 256-thread workgroup owns 256 / LANES sorted slots of ONE
@@ -575,6 +575,7 @@ public:
     // the one-lane kernel keeps old_v in LDS too while the launch's n_replicas * n_max cells are at most this many
     // (Grid_computer::stage_v_max: is the launch big enough to hide the L2's latency?)
     int stage_v_max = 130000;
+    int pass_facts = 1;  // the one-lane kernel: as Grid_computer::pass_facts
 
     // take_steps as launches that step from LDS (ya::ens::grid_lds_steps: one workgroup per replica): -1 = never,
     // 1 = whenever the call is eligible, 0 (default) = the engine's choice, eligible and
@@ -663,7 +664,8 @@ protected:
     }
 #define YA_ENS_BITS_LAUNCH(stage_v_, off32_)                                                                    \
     ya::ens::grid_force_bits_batched<Pt, pw_int, pw_friction, stage_v_, off32_><<<this->grid_of(blocks), ya::bits::BLOCK>>>( \
-        n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane)
+        n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane, \
+        ya::bits::launch_facts(pass_facts, cut2))
         if (lanes == 16) {
             YA_ENS_COOP_LAUNCH(16)
         } else if (lanes == 8) {

@@ -832,19 +832,52 @@ __host__ __device__ constexpr bool offsets_fit_32_bits(const long long n)
     return n >= 0 && 16ll * n < (1ll << 32);
 }
 
+// What a pass may know about its hits before it pops the first one (Grid_computer::pass_facts).  A pass that knows
+// drains its stream through a phase 2 compiled under that knowledge; what the pass computes does not change.
+//   DISTINCT  no hit is the lane's own cell (i != j).  A cell is its own candidate in one stencil row of its own plane:
+//             ids are unique per slot, so the fact holds iff no active lane's own slot lies in one of the pass'
+//             three candidate ranges -- which the caller tests on the ranges themselves, wave-uniformly, not on the
+//             plane number (in a grid of one cube an axis the rows of the planes below and above are the cell's own
+//             cube too).  spring's `i == j ? 0 : dF` and friction_w_neighbour's `i != j` then fold away.
+//   NEAR      every hit has dist < 1.  A hit is a candidate with d2 < cut2, dist2_to (phase 1) and the statements
+//             in front of dist3 (phase 2) are the same subtractions, product and two fmaf, and exact_sqrt is sqrtf
+//             for every bit pattern: where cut2 <= cutoff_squared(1) -- the smallest binary32 whose root reaches 1
+//             -- sqrtf(d2) < 1.  Decided once per launch on the host (launch_facts).
+// Under both, friction_w_neighbour's coefficient is the constant 1: sum_friction += 1 and three plain adds
+// (fmaf(1, v, s) and s + v round alike; a non-finite old_v poisons the sum either way).
+// The fast tier keeps the generic body alone: NEAR is not true there (its bare v_sqrt_f32, <= 1 ulp, can return 1 just
+// below the cut-off), and DISTINCT alone measured 2 us per step SLOWER than the generic body alone at 10^6 cells
+// (DESIGN.md section 6, round 10).
+#ifdef YA_ARITH_FAST
+constexpr bool FACT_BODIES = false;
+#else
+constexpr bool FACT_BODIES = true;
+#endif
+constexpr int FACT_DISTINCT = 1, FACT_NEAR = 2;
+// The facts a launch with cut-off cut2 may use.  `setting` is Grid_computer::pass_facts: 0 none (generic bodies only),
+// 1 (default) both, 2 / 3 DISTINCT / NEAR alone (A/B).  Any setting gives the same bits.
+inline int launch_facts(const int setting, const float cut2)
+{
+    if (!FACT_BODIES) return 0;
+    int facts = setting == 0 ? 0 : (setting == 2 ? FACT_DISTINCT : (setting == 3 ? FACT_NEAR : FACT_DISTINCT | FACT_NEAR));
+    if (!(cut2 <= cutoff_squared(1.0f))) facts &= ~FACT_NEAR;
+    return facts;
+}
+
+// Phase 1 of a pass leaves the bit stream in LDS and these in registers: bits emitted, where segments 1 and 2 begin
+// in the stream, and per segment LDS index - bit position.
+struct Scan {
+    int p, p1, p2, d0, d1, d2;
+};
+
 // One pass: up to three candidate segments [b_r, e_r) of the staged cells (LDS indices;
 // empty if b_r >= e_r), at most PASS_BITS bits after padding each to a multiple of four.
 // shift_r turns an LDS index of segment r into a slot of the sorted arrays.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
-    bool OFF32>
-__device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const float4* __restrict__ sh_v,
-    Lds_word* const words,
-    const int b0, const int e0, const int b1, const int e1, const int b2, const int e2,
-    const int shift0, const int shift1, const int shift2, const float4* __restrict__ sorted_v,
-    const Pt& Xi, const int i, const float cut2, Pt& F, float3& sum_v, float& sum_friction,
-    const int* __restrict__ global_id, const int id_base = 0)
+// scan() is phase 1, drain() phase 2 (DISTINCT, NEAR: above), pass() one after the other.
+template<typename Pt>
+__device__ __forceinline__ Scan scan(const Entry<Pt>* __restrict__ sh_e, Lds_word* const words,
+    const int b0, const int e0, const int b1, const int e1, const int b2, const int e2, const Pt& Xi, const float cut2)
 {
-    constexpr int POPS = Pops<Pt>::value;
     // ---- phase 1 ----
     unsigned m = 0;
     int p = 0;  // bits emitted
@@ -882,7 +915,19 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
 #undef YA_BITS_SEGMENT
 #undef YA_BITS_GROUP
     if (p & 31) *mp = m << (32 - (p & 31));  // left-align the last, partial word
+    return {p, p1, p2, d0, d1, d2_};
+}
 
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
+    bool OFF32, bool DISTINCT, bool NEAR>
+__device__ __forceinline__ void drain(const Entry<Pt>* __restrict__ sh_e, const float4* __restrict__ sh_v,
+    Lds_word* const words, const Scan& sc, const int shift0, const int shift1, const int shift2,
+    const float4* __restrict__ sorted_v, const Pt& Xi, const int i, Pt& F, float3& sum_v, float& sum_friction,
+    const int* __restrict__ global_id, const int id_base)
+{
+    static_assert(!(DISTINCT && GLOBAL_IDS), "a slab's launches keep the generic body");
+    constexpr int POPS = Pops<Pt>::value;
+    const int p = sc.p, p1 = sc.p1, p2 = sc.p2, d0 = sc.d0, d1 = sc.d1, d2_ = sc.d2;
     // ---- phase 2 ----
     // A hit at bit position q of segment r is staged cell q + d_r, sorted slot q + d_r + shift_r.  The three
     // per-lane BYTE offsets of either are formed once per pass; a hit then costs two compares, the selects and
@@ -921,6 +966,9 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
         Pt r = Xi - other_.X;                                                          \
         float dist = dist3(r.x, r.y, r.z);                                             \
         const int j = (GLOBAL_IDS ? global_id[other_.id] : other_.id) + id_base;       \
+        /* what the pass knows, said on this side of the functors (as YA_CALL_INLINED is) */ \
+        if constexpr (DISTINCT) __builtin_assume(i != j);                              \
+        if constexpr (NEAR) __builtin_assume(dist < 1.f);                              \
         YA_CALL_INLINED F += pw_int(Xi, r, dist, i, j);                                \
         pair_friction<Pt, pw_friction>(Xi, r, dist, i, j, v_, sum_v, sum_friction);    \
     }
@@ -956,6 +1004,20 @@ __device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const f
 #undef YA_BITS_LOAD
 #undef YA_BITS_PAIR
 }
+
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V, bool GLOBAL_IDS,
+    bool OFF32, bool DISTINCT = false, bool NEAR = false>
+__device__ __forceinline__ void pass(const Entry<Pt>* __restrict__ sh_e, const float4* __restrict__ sh_v,
+    Lds_word* const words,
+    const int b0, const int e0, const int b1, const int e1, const int b2, const int e2,
+    const int shift0, const int shift1, const int shift2, const float4* __restrict__ sorted_v,
+    const Pt& Xi, const int i, const float cut2, Pt& F, float3& sum_v, float& sum_friction,
+    const int* __restrict__ global_id, const int id_base = 0)
+{
+    const Scan sc = scan<Pt>(sh_e, words, b0, e0, b1, e1, b2, e2, Xi, cut2);
+    drain<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32, DISTINCT, NEAR>(sh_e, sh_v, words, sc, shift0, shift1,
+        shift2, sorted_v, Xi, i, F, sum_v, sum_friction, global_id, id_base);
+}
 }  // namespace bits
 
 // GLOBAL_IDS (z-slab decomposition): functors get global_id[local index]; a template parameter
@@ -966,7 +1028,7 @@ __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile
     const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
     const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
     Pt* d_dX, const bool has_gen, const int n_active, Pt* d_dX_sorted,
-    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane);
+    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane, const int facts = 0);
 
 // OFF32: old_v gathered through 32-bit byte offsets (bits::offsets_fit_32_bits(n); bits::pass)
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool STAGE_V = false,
@@ -978,7 +1040,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     const int n_active, Pt* __restrict__ d_dX_sorted, const int* __restrict__ global_id, const int n_tiles,
     const int tail, float* tail_exchange, int* tail_tickets, const bool by_plane,
     const int part = 0, const int part_cube_lo = 0, const int part_cube_hi = 0, const int own_cube_lo = 0,
-    const int own_cube_hi = 0x7fffffff)
+    const int own_cube_hi = 0x7fffffff, const int pass_facts = 0)
 {
     constexpr int FB = bits::BLOCK;
 
@@ -1050,7 +1112,7 @@ __global__ __launch_bounds__(bits::BLOCK, bits::Min_waves<Pt>::value) void grid_
     // which tile is mine ends here; the tile itself is the body an ensemble's kernel shares (include/ensemble_grid.cuh)
     grid_force_bits_tile<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32>(n, tile, 0, half, compact - whole, sorted,
         sorted_v, cube_id, offs, gs, n_cubes, cut2, d_dX, has_gen, n_active, d_dX_sorted, global_id, tail_exchange,
-        tail_tickets, by_plane);
+        tail_tickets, by_plane, pass_facts);
 }
 
 // One tile of grid_force_bits -- 64 consecutive sorted slots of ONE system's arrays -- as the workgroup that was
@@ -1064,7 +1126,7 @@ __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile
     const int slot, const Entry<Pt>* sorted, const float4* sorted_v,
     const int* cube_id, const int* offs, const int gs, const int n_cubes, const float cut2,
     Pt* d_dX, const bool has_gen, const int n_active, Pt* d_dX_sorted,
-    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane)
+    const int* global_id, float* tail_exchange, int* tail_tickets, const bool by_plane, const int facts)
 {
     constexpr int FB = bits::BLOCK;
     constexpr int CAP = bits::Stage<Pt>::value;
@@ -1162,9 +1224,34 @@ __device__ __forceinline__ void grid_force_bits_tile(const int n, const int tile
             const int bits_needed = (max(se[0] - sb[0], 0) + 3 & ~3) + (max(se[1] - sb[1], 0) + 3 & ~3) +
                                     (max(se[2] - sb[2], 0) + 3 & ~3);
             if (!__any(bits_needed > bits::PASS_BITS)) {
-                bits::pass<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32>(sh_e, sh_v, words, sb[0], se[0], sb[1], se[1], sb[2],
-                    se[2], shift[0], shift[1], shift[2], sorted_v, Xi, gi, cut2, F, sum_v, sum_friction,
-                    global_id, id_base);
+                const bits::Scan sc = bits::scan<Pt>(sh_e, words, sb[0], se[0], sb[1], se[1], sb[2], se[2], Xi, cut2);
+                // phase 2 under what this pass knows about its hits (bits::FACT_DISTINCT, FACT_NEAR): the own slot is
+                // looked for in the pass' candidate ranges themselves, never inferred from the plane
+#define YA_BITS_DRAIN(distinct_, near_)                                                        \
+    bits::drain<Pt, pw_int, pw_friction, STAGE_V, GLOBAL_IDS, OFF32, distinct_, near_>(sh_e, sh_v, words, sc, shift[0], \
+        shift[1], shift[2], sorted_v, Xi, gi, F, sum_v, sum_friction, global_id, id_base)
+                constexpr bool GENERIC_ONLY = GLOBAL_IDS || !bits::FACT_BODIES;  // slabs; the fast tier
+                bool distinct = false;
+                if constexpr (!GENERIC_ONLY) {
+                    bool own_among = false;
+#pragma unroll
+                    for (int r = 0; r < 3; r++) own_among |= (s - shift[r] >= sb[r]) & (s - shift[r] < se[r]);
+                    distinct = (facts & bits::FACT_DISTINCT) && !__any(own_among);
+                }
+                const bool near = facts & bits::FACT_NEAR;
+                if constexpr (GENERIC_ONLY) {
+                    YA_BITS_DRAIN(false, false);
+                } else if (distinct) {
+                    if (near)
+                        YA_BITS_DRAIN(true, true);
+                    else
+                        YA_BITS_DRAIN(true, false);
+                } else if (near) {
+                    YA_BITS_DRAIN(false, true);
+                } else {
+                    YA_BITS_DRAIN(false, false);
+                }
+#undef YA_BITS_DRAIN
             } else {
                 // dense rows: one pass per stretch of PASS_BITS candidates, rows in order
 #pragma unroll 1
@@ -3153,6 +3240,10 @@ public:
     // grid_force_bits gathers old_v through 32-bit byte offsets while 16 n fits them (ya::bits::offsets_fit_32_bits)
     // and builds 64-bit addresses beyond: 0 = by n, 64 = the 64-bit form at any size (A/B, tests; same results)
     int gather_offset_bits = 0;
+    // grid_force_bits: what a pass may know about its hits before phase 2 (ya::bits::launch_facts): 1 (default) = no
+    // self pair where the pass' rows cannot hold the lane's own slot, and dist < 1 for every hit while cube_size <= 1
+    // (exact tier); 0 = the generic bodies only; 2 / 3 = the first / the second fact alone (A/B).  Same results.
+    int pass_facts = 1;
     bool gathers_by_32_bit_offsets(const int n) const
     {
         return gather_offset_bits != 64 && ya::bits::offsets_fit_32_bits(n);
@@ -3241,19 +3332,21 @@ protected:
     // kernel, a launch size or a kernel argument belongs here too.
     struct Step_variant {
         int force_variant = -1, sum_order = 0, coop_lanes = 0, stage_v_max = 0, tail_tiles = 0, gather_offset_bits = 0;
+        int pass_facts = 1;
         int tail_areas = 0;  // allocations of tail exchange areas so far: a graph made before one holds freed pointers
         const int* global_id = nullptr;
         bool operator==(const Step_variant& o) const
         {
             return force_variant == o.force_variant && sum_order == o.sum_order && coop_lanes == o.coop_lanes &&
                    stage_v_max == o.stage_v_max && tail_tiles == o.tail_tiles &&
-                   gather_offset_bits == o.gather_offset_bits && tail_areas == o.tail_areas && global_id == o.global_id;
+                   gather_offset_bits == o.gather_offset_bits && pass_facts == o.pass_facts &&
+                   tail_areas == o.tail_areas && global_id == o.global_id;
         }
     };
     Step_variant step_variant() const
     {
-        return {force_variant, (int)sum_order, coop_lanes, stage_v_max, force_tail_tiles, gather_offset_bits, tail_areas,
-            d_global_id};
+        return {force_variant, (int)sum_order, coop_lanes, stage_v_max, force_tail_tiles, gather_offset_bits, pass_facts,
+            tail_areas, d_global_id};
     }
     int tail_areas = 0;
     Grid grid;
@@ -3374,7 +3467,7 @@ protected:
         d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes, cut2, d_dX,  \
         has_gen, n_active, d_dX_in_cell_order, (const int*)d_global_id, tiles, tail,           \
         d_tail_exchange[part], d_tail_tickets[part], by_plane, part, force_part_cube_lo,                 \
-        force_part_cube_hi, force_own_cube_lo, force_own_cube_hi)
+        force_part_cube_hi, force_own_cube_lo, force_own_cube_hi, ya::bits::launch_facts(pass_facts, cut2))
             const int tiles = (n + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
             // Half tiles (grid_force_bits, "the tail"; > 0: the last so many tiles of the launch, < 0: all).
             // With R one-wavefront workgroups resident at once (5120 for springs): launches of up to R / 2 tiles

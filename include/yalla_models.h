@@ -89,7 +89,8 @@ int ya_sim_build_grid(ya_sim* sim, int grid_size, float cube_size, int* cube_id,
  * result: "force_variant", "coop_lanes", "stage_v_max", "tail_tiles" (grid_force_bits: -1 the engine's choice,
  * 0 whole tiles only, k the last k tiles of a launch as half tiles, the launch's tile count or more: all),
  * "gather_offset_bits" (grid_force_bits: 0 = old_v through 32-bit byte offsets while 16 n fits them, 64 = 64-bit
- * addresses at any size), "sorted_pipeline", "graph", "tile_lanes", "carry_sorted" (device build only). */
+ * addresses at any size), "pass_facts" (grid_force_bits: 1 = phase 2 compiled under what a pass knows about its
+ * hits -- no self pair, dist < 1 -- where the pass can prove it, 0 = the generic bodies only), "sorted_pipeline", "graph", "tile_lanes", "carry_sorted" (device build only). */
 int ya_sim_set_param(ya_sim* sim, const char* name, double value);
 /* Integer per-cell properties of a model ("type", "mes_nbs", "epi_nbs"). */
 int ya_sim_set_prop(ya_sim* sim, const char* name, const int* values, int n);

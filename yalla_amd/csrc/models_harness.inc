@@ -99,6 +99,7 @@ struct Cells<Pt, TILE> : public Solution<Pt, Tile_solver> {
     int set_coop_lanes(int) { return -2; }
     int set_stage_v_max(int) { return -2; }
     int set_gather_offset_bits(int) { return -2; }
+    int set_pass_facts(int) { return -2; }
     int set_tail_tiles(int) { return -2; }
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
@@ -169,6 +170,18 @@ struct Cells<Pt, GRID> : public Solution<Pt, Harness_slab_solver> {
 #else
         if (v != 0 && v != 64) return -1;
         this->gather_offset_bits = v;
+        return 0;
+#endif
+    }
+    // grid_force_bits: what a pass may know about its hits (Grid_computer::pass_facts: 1 default, 0 generic bodies
+    // only, 2 / 3 one fact alone)
+    int set_pass_facts(int v)
+    {
+#ifdef YA_ORACLE
+        return -2;
+#else
+        if (v < 0 || v > 3) return -1;
+        this->pass_facts = v;
         return 0;
 #endif
     }
@@ -270,6 +283,7 @@ struct Cells<Pt, GABRIEL> : public Solution<Pt, Gabriel_solver> {
     int set_coop_lanes(int) { return -2; }
     int set_stage_v_max(int) { return -2; }
     int set_gather_offset_bits(int) { return -2; }
+    int set_pass_facts(int) { return -2; }
     int set_tail_tiles(int) { return -2; }
     int set_sum_order(int) { return -2; }
     int set_sorted_pipeline(int) { return -2; }
@@ -700,6 +714,7 @@ struct Sim : public Sim_base {
         if (std::string(name) == "stage_v_max") return cells.set_stage_v_max((int)v);
         if (std::string(name) == "tail_tiles") return cells.set_tail_tiles((int)v);
         if (std::string(name) == "gather_offset_bits") return cells.set_gather_offset_bits((int)v);
+        if (std::string(name) == "pass_facts") return cells.set_pass_facts((int)v);
         if (std::string(name) == "sum_order") return cells.set_sum_order((int)v);
         if (std::string(name) == "sorted_pipeline") return cells.set_sorted_pipeline((int)v);
         if (std::string(name) == "graph") return cells.set_graph((int)v);
