@@ -646,43 +646,27 @@ protected:
         const int* d_n = this->d_n;
         this->build(d_in);
         const int grid_size = this->grid_size, n_cubes = this->n_cubes;
-        const int *d_cube_id = this->d_cube_id, *d_offs = this->d_offs;
-        const ya::Entry<Pt>* d_sorted = this->d_sorted;
-        const float4* d_sorted_v = this->d_sorted_v;
-
         const float cut2 = ya::cutoff_squared(this->cube_size);
         const bool by_plane = sum_order == YA_SUM_BY_PLANE;
         int lanes = lanes_per_cell;
         if (lanes == 0)
             lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::grid_lanes_for(n_replicas, n_max) : 1;
-#define YA_ENS_COOP_LAUNCH(lanes_)                                                                              \
-    {                                                                                                           \
-        const int blocks = (n_max + ya::coop::BLOCK / lanes_ - 1) / (ya::coop::BLOCK / lanes_);                 \
-        ya::ens::grid_force_coop_batched<Pt, pw_int, pw_friction, lanes_><<<this->grid_of(blocks), ya::coop::BLOCK>>>( \
-            n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen,  \
-            by_plane);                                                                                          \
-    }
-#define YA_ENS_BITS_LAUNCH(stage_v_, off32_)                                                                    \
-    ya::ens::grid_force_bits_batched<Pt, pw_int, pw_friction, stage_v_, off32_><<<this->grid_of(blocks), ya::bits::BLOCK>>>( \
-        n_max, blocks, d_n, d_sorted, d_sorted_v, d_cube_id, d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane, \
-        ya::bits::launch_facts(pass_facts, cut2))
-        if (lanes == 16) {
-            YA_ENS_COOP_LAUNCH(16)
-        } else if (lanes == 8) {
-            YA_ENS_COOP_LAUNCH(8)
-        } else if (lanes == 4) {
-            YA_ENS_COOP_LAUNCH(4)
-        } else {
-            const int blocks = (n_max + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
-            if (this->rows() <= (size_t)stage_v_max) {
-                YA_ENS_BITS_LAUNCH(true, true);
-            } else if (ya::bits::offsets_fit_32_bits(n_max)) {
-                YA_ENS_BITS_LAUNCH(false, true);
-            } else {
-                YA_ENS_BITS_LAUNCH(false, false);
-            }
-        }
-#undef YA_ENS_BITS_LAUNCH
-#undef YA_ENS_COOP_LAUNCH
+        const bool coop = ya::coop::with_lanes(lanes, [&](auto per_cell) {
+            constexpr int CELLS = ya::coop::BLOCK / decltype(per_cell)::value;
+            const int blocks = (n_max + CELLS - 1) / CELLS;
+            ya::launch(ya::ens::grid_force_coop_batched<Pt, pw_int, pw_friction, decltype(per_cell)::value>,
+                this->grid_of(blocks), ya::coop::BLOCK, nullptr, nullptr, nullptr, n_max, blocks, d_n, this->d_sorted,
+                this->d_sorted_v, this->d_cube_id, this->d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane);
+        });
+        if (coop) return;
+        const int blocks = (n_max + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
+        ya::bits::with_gather(this->rows() <= (size_t)stage_v_max, ya::bits::offsets_fit_32_bits(n_max),
+            [&](auto stage_v, auto off32) {
+                ya::launch(ya::ens::grid_force_bits_batched<Pt, pw_int, pw_friction, decltype(stage_v)::value,
+                               decltype(off32)::value>,
+                    this->grid_of(blocks), ya::bits::BLOCK, nullptr, nullptr, nullptr, n_max, blocks, d_n, this->d_sorted,
+                    this->d_sorted_v, this->d_cube_id, this->d_offs, grid_size, n_cubes, cut2, d_rhs, has_gen, by_plane,
+                    ya::bits::launch_facts(pass_facts, cut2));
+            });
     }
 };

@@ -51,6 +51,7 @@
 
 #include <functional>
 #include <mutex>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -2102,6 +2103,17 @@ struct Fix_args {
     int arg = 0;
     float* out = nullptr;  // predictor, may be NULL: its thread 0 leaves the velocity here for the corrector
 };
+// What the update kernels read and write of a computer that keeps the cells cube-sorted (Computer::carries; all null
+// for one that does not).  The last four exist once Grid_computer::carry_ready has said so.
+template<typename Pt>
+struct Sorted_buffers {
+    Entry<Pt>* cells = nullptr;          // the cube-sorted copy stage 1 kept (stage_update moves it)
+    const Pt* rhs = nullptr;             // ... and its right-hand side in that order
+    Entry<Pt>* carried = nullptr;        // a carried step: the predictor's output, then the corrector's
+    float4* carried_v = nullptr;         // the corrector's {old_v, 0}
+    const Pt* carried_rhs = nullptr;     // stage 2's right-hand sides in stage 2's sorted order
+    const int* carried_slots = nullptr;  // stage-1 slot -> stage-2 slot
+};
 // Every thread of the workgroup calls it, before any early return: the partials fold has barriers.
 template<Fix_src S, typename Pt>
 __device__ __forceinline__ float3 resolve_fix(const Fix_args& f, const int n)
@@ -2519,20 +2531,21 @@ public:
     {
         const int n = get_d_n();
         if (n <= 0) return;
-        const int* order = Computer<Pt>::cube_order(n, d_X);  // order[s] = the id of the cell in slot s
-        if (!order) return;
-        permute_array(order, n, d_X);
-        permute_array(order, n, d_old_v);
-        int* new_id = nullptr;
-        const int unused[] = {0, (renumber_one(order, n, arrays, new_id), 0)...};
-        (void)unused;
-        if (new_id) ya_free(new_id);
-        rhs_zeroed[0] = rhs_zeroed[1] = 0;  // (nothing here writes d_dX / d_dX1; no promise is carried over a renumbering)
-        Computer<Pt>::ids_changed();
-        // a graph captured NOW would bake the forgotten visit order (n_prev = 0) into its first build:
-        // capture again one step later, when the grid remembers an order again
-        drop_graph();
-        last_key = Step_key{};
+        if constexpr (has_grid) {
+            const int* order = Computer<Pt>::cube_order(n, d_X);  // order[s] = the id of the cell in slot s
+            permute_array(order, n, d_X);
+            permute_array(order, n, d_old_v);
+            int* new_id = nullptr;
+            const int unused[] = {0, (renumber_one(order, n, arrays, new_id), 0)...};
+            (void)unused;
+            if (new_id) ya_free(new_id);
+            rhs_zeroed[0] = rhs_zeroed[1] = 0;  // (nothing here writes d_dX / d_dX1; no promise is carried over a renumbering)
+            Computer<Pt>::ids_changed();
+            // a graph captured NOW would bake the forgotten visit order (n_prev = 0) into its first build:
+            // capture again one step later, when the grid remembers an order again
+            drop_graph();
+            last_key = Step_key{};
+        }
     }
 
     // ... or ONE line after the model has made its arrays, instead of a call in its loop (round 5):
@@ -2595,11 +2608,8 @@ protected:
         typename Computer<Pt>::Step_variant variant{};
         int fix_mode = 0, fix_point = 0;
         bool fold = true;
-        bool operator==(const Step_key& o) const
-        {
-            return functors == o.functors && n == o.n && dt == o.dt && cube_size == o.cube_size &&
-                   variant == o.variant && fix_mode == o.fix_mode && fix_point == o.fix_point && fold == o.fold;
-        }
+        auto tied() const { return std::tie(functors, n, dt, cube_size, variant, fix_mode, fix_point, fold); }
+        bool operator==(const Step_key& o) const { return tied() == o.tied(); }
     };
     Step_key graph_key, last_key;
     hipGraphExec_t graph_exec = nullptr;
@@ -2638,7 +2648,18 @@ protected:
         assert(n <= n_max);
         return n;
     }
-    void check_status() { Computer<Pt>::check_status(); }
+    void check_status() { if constexpr (has_grid) Computer<Pt>::check_status(); }
+    // A computer's traits.  has_grid: the code for a grid (renumbering, the status, the cube-sorted copy of the cells
+    // kept between stages and steps, captured steps) is compiled for such computers only, so Tile_computer declares
+    // none of the members it calls.  carries: whether a computer with a grid keeps that copy at all (Gabriel's: no).
+    static constexpr bool has_grid = Computer<Pt>::has_grid;
+    bool sorted_pipeline_on() const
+    {
+        if constexpr (has_grid) return Computer<Pt>::carries && Computer<Pt>::use_sorted_pipeline();
+        return false;
+    }
+    // set_fixed() (the default) with fold_in_update: the update kernel folds the mean from the reduction's partial sums
+    bool update_folds_mean() const { return fix_com and !fix_com_z and fold_in_update; }
     // renumber(): array[s] = array[order[s]] for s < n, through a scratch buffer that is kept
     void* renumber_scratch = nullptr;
     size_t renumber_scratch_bytes = 0;
@@ -2710,14 +2731,15 @@ protected:
             gen_forces(n, d_in, d_rhs);
         }
         rhs_zeroed[stage - 1] = 0;  // the force kernel writes it next
-        if (stage == 2 && sorted_stage_cells == n) {
-            // the second stage starts from the sorted copy stage_update(1) moved, mirrored cells included (the
-            // generic forces above were given d_X1, as the reference does)
-            sorted_stage_cells = -1;
-            Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(n, d_dX1, n_active, has_gen);
-            return;
-        }
-        const bool keep_sorted = stage == 1 && Computer<Pt>::use_sorted_pipeline();
+        if constexpr (has_grid)
+            if (stage == 2 && sorted_stage_cells == n) {
+                // the second stage starts from the sorted copy stage_update(1) moved, mirrored cells included (the
+                // generic forces above were given d_X1, as the reference does)
+                sorted_stage_cells = -1;
+                Computer<Pt>::template pwints_from_sorted<pw_int, pw_friction>(n, d_dX1, n_active, has_gen);
+                return;
+            }
+        const bool keep_sorted = stage == 1 && sorted_pipeline_on();
         Computer<Pt>::template pwints<pw_int, pw_friction>(n, d_in, d_old_v, d_rhs, has_gen, n_active, keep_sorted);
         sorted_stage_cells = keep_sorted ? n : -1;
     }
@@ -2755,10 +2777,11 @@ protected:
             const bool in_sorted = sorted_stage_cells == n;
             fix.out = S == Fix::memory ? nullptr : d_mean_first;
             stage1_fix = S == Fix::memory ? fix.src : d_mean_first;
+            ya::Sorted_buffers<Pt> sorted;  // (all null without a grid)
+            if constexpr (has_grid) sorted = Computer<Pt>::sorted_buffers();
             euler_step<Pt, S><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, fix, d_dX, d_X,
-                has_gen || !in_sorted ? d_X1 : nullptr, Computer<Pt>::sorted_rhs(),
-                in_sorted ? Computer<Pt>::sorted_cells() : nullptr, n_active, has_gen ? d_dX1 : nullptr,
-                slab_out.pred_partial, slab_out.band);
+                has_gen || !in_sorted ? d_X1 : nullptr, sorted.rhs, in_sorted ? sorted.cells : nullptr, n_active,
+                has_gen ? d_dX1 : nullptr, slab_out.pred_partial, slab_out.band);
             rhs_zeroed[1] = has_gen ? n : 0;
         } else {
             heun_step<Pt, S><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, stage1_fix, fix, d_dX, d_dX1, d_X,
@@ -2795,9 +2818,8 @@ protected:
         for (int stage = 1; stage <= 2; stage++) {
             stage_rhs<pw_int, pw_friction>(stage, n, n, gen_forces);
             Pt* d_rhs = stage == 1 ? d_dX : d_dX1;
-            if (fix_com and !fix_com_z and fold_in_update) {
-                // set_fixed() (the default): the mean, folded by the update kernel from the reduction's partial
-                // sums (ya::fixed_velocity_from_partials: a launch fewer per stage, the same bits)
+            if (update_folds_mean()) {
+                // (ya::fixed_velocity_from_partials: a launch fewer per stage, the same bits)
                 int n_partials = 0;
                 YA_CHECK(ya_reduce_partials(d_rhs, n_floats, n, d_workspace, &n_partials, this->stream));
                 stage_update<Fix::partials>(stage, n, dt, {d_workspace, n_partials}, has_gen, n);
@@ -2813,16 +2835,77 @@ protected:
     Step_key key_of(const int n, const float dt)
     {
         static const char functors_tag = 0;  // one per <pw_int, pw_friction>
-        Step_key k;
-        k.functors = &functors_tag;
-        k.n = n;
-        k.dt = dt;
-        k.cube_size = Computer<Pt>::step_cube_size();
-        k.variant = Computer<Pt>::step_variant();
+        Step_key k{&functors_tag, n, dt};
+        if constexpr (has_grid) {
+            k.cube_size = this->cube_size;
+            k.variant = Computer<Pt>::step_variant();
+        }
         k.fix_mode = (fix_com ? 1 : 0) | (fix_com_z ? 2 : 0);
         k.fix_point = fix_point;
         k.fold = fold_in_update;
         return k;
+    }
+    // The number of cells of the step that begins; <= 0: there is none (a build begun is cancelled).
+    // build_ahead: the reference reads n first (solvers.cuh:229) and so must we, model kernels change it between
+    // steps; but the round trip is hidden behind the binning kernels of the first grid build, which read the count
+    // on the device.  (Round 5: with generic forces too.  They need n on the host -- gen_forces(n, d_X, d_dX) --
+    // but the first build reads d_X only and the generic forces write d_dX only, so the build's first three kernels
+    // may run before them: the device works while the count travels, instead of standing idle between two steps.
+    // Round 6: the count travels in the first binning kernel itself, ya_grid_build_sorted_begin_publish, not in a
+    // 4-byte copy queued ahead of it: one 4 us kernel fewer in the stream per step.)
+    int read_n(const bool build_ahead)
+    {
+        if constexpr (has_grid) {
+            int n = build_ahead ? 0 : get_d_n();
+            if (build_ahead) {
+                Computer<Pt>::begin_build(d_X, d_n, n_max, n_reader);
+                YA_CHECK(ya_n_read_end(n_reader, &n));
+                assert(n <= n_max);
+            }
+            if (n <= 0) Computer<Pt>::cancel_build();
+            return n;
+        }
+        return get_d_n();
+    }
+    // The step of n cells as one hipGraphLaunch, a replay or a capture and its first launch; false = nothing was done
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    bool graph_step(const int n, const float dt, Generic_forces<Pt>& gen_forces)
+    {
+        const Step_key key = key_of<pw_int, pw_friction>(n, dt);
+        // Replay only what the step before was too (key == last_key: every plain step leaves its key
+        // there).  The graph also bakes in what the grid remembered when it was captured -- the visit
+        // order of a build of these n cells (n_prev, d_prev_pid) -- and that holds only straight after
+        // such a step: a graph whose key comes back after other steps (n down and up again) waits one
+        // plain step.
+        if (graph_exec && key == graph_key && key == last_key) {
+            YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
+            graph_launches++;
+            return true;
+        }
+        // NOTHING between hipStreamBeginCapture and hipStreamEndCapture may synchronise, allocate, free or
+        // use the null stream (ya_device_synchronize, ya_malloc / ya_free, hipMemcpy, a memset or launch
+        // without this->stream): the runtime fails such a call and YA_CHECK ends the process.  The step
+        // before ran the same launches plainly, so everything lazily sized exists (the grid's stash, the
+        // tail exchange area); a computer that would still have to allocate says so (ready_to_capture)
+        // and the step stays a plain one.  The same step as last time is captured (thread-local mode: other
+        // host threads of the model, e.g. one writing output, may keep using HIP).
+        if (!(key == last_key && (graph_steps > 0 || n < YA_GRAPH_MAX_CELLS) &&
+                Computer<Pt>::template ready_to_capture<pw_int, pw_friction>(n)))
+            return false;
+        drop_graph();
+        if (!capture_stream) YA_CHECK((int)hipStreamCreateWithFlags(&capture_stream, hipStreamNonBlocking));
+        YA_CHECK((int)hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal));
+        this->stream = capture_stream;
+        heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
+        this->stream = nullptr;
+        hipGraph_t graph = nullptr;
+        YA_CHECK((int)hipStreamEndCapture(capture_stream, &graph));
+        YA_CHECK((int)hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
+        YA_CHECK((int)hipGraphDestroy(graph));
+        graph_key = key;
+        YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
+        graph_launches++;
+        return true;
     }
 
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
@@ -2832,78 +2915,16 @@ protected:
             keep_order();
             keep_order_wait = keep_order_every - 1;
         }
-        const bool sorted_path =
-            Computer<Pt>::use_sorted_pipeline() && ya::is_no_gen_forces<Pt>(gen_forces);
-        int n;
-        if (sorted_path && graph_steps != 0 && last_key.n > 0 && !Computer<Pt>::profiler.active() &&
-            (graph_steps > 0 || last_key.n < YA_GRAPH_MAX_CELLS)) {
-            // Small system: read n first (solvers.cuh:229), then replay / capture / launch.
-            n = get_d_n();
-            if (n <= 0) return;
-            const Step_key key = key_of<pw_int, pw_friction>(n, dt);
-            // Replay only what the step before was too (key == last_key: every plain step leaves its key
-            // there).  The graph also bakes in what the grid remembered when it was captured -- the visit
-            // order of a build of these n cells (n_prev, d_prev_pid) -- and that holds only straight after
-            // such a step: a graph whose key comes back after other steps (n down and up again) waits one
-            // plain step.
-            if (graph_exec && key == graph_key && key == last_key) {
-                YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
-                graph_launches++;
-                return;
-            }
-            // NOTHING between hipStreamBeginCapture and hipStreamEndCapture may synchronise, allocate, free or
-            // use the null stream (ya_device_synchronize, ya_malloc / ya_free, hipMemcpy, a memset or launch
-            // without this->stream): the runtime fails such a call and YA_CHECK ends the process.  The step
-            // before ran the same launches plainly, so everything lazily sized exists (the grid's stash, the
-            // tail exchange area); a computer that would still have to allocate says so (ready_to_capture)
-            // and the step stays a plain one.
-            if (key == last_key && (graph_steps > 0 || n < YA_GRAPH_MAX_CELLS) &&
-                Computer<Pt>::template ready_to_capture<pw_int, pw_friction>(n)) {
-                // the same step as last time: capture it (thread-local mode: other host
-                // threads of the model, e.g. one writing output, may keep using HIP)
-                drop_graph();
-                if (!capture_stream)
-                    YA_CHECK((int)hipStreamCreateWithFlags(&capture_stream, hipStreamNonBlocking));
-                YA_CHECK((int)hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal));
-                this->stream = capture_stream;
-                heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
-                this->stream = nullptr;
-                hipGraph_t graph = nullptr;
-                YA_CHECK((int)hipStreamEndCapture(capture_stream, &graph));
-                YA_CHECK((int)hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
-                YA_CHECK((int)hipGraphDestroy(graph));
-                graph_key = key;
-                YA_CHECK((int)hipGraphLaunch(graph_exec, nullptr));
-                graph_launches++;
-                return;
-            }
-            heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
-            last_key = key_of<pw_int, pw_friction>(n, dt);  // (after the launches: they may have allocated)
-            return;
-        }
-        if (Computer<Pt>::use_sorted_pipeline()) {
-            // The reference reads n first (solvers.cuh:229) and so must we, model kernels
-            // change it between steps; but the round trip is hidden behind the binning
-            // kernels of the first grid build, which read the count on the device.
-            // (Round 5: with generic forces too.  They need n on the host -- gen_forces(n, d_X, d_dX) -- but
-            // the first build reads d_X only and the generic forces write d_dX only, so the build's first
-            // three kernels may run before them: the device works while the count travels, instead of
-            // standing idle between two steps.)
-            // (Round 6: the count travels in the first binning kernel itself, ya_grid_build_sorted_begin_publish,
-            // not in a 4-byte copy queued ahead of it: one 4 us kernel fewer in the stream per step.)
-            Computer<Pt>::begin_build(d_X, d_n, n_max, n_reader);
-            YA_CHECK(ya_n_read_end(n_reader, &n));
-            assert(n <= n_max);
-        } else {
-            n = get_d_n();
-        }
-        if (n <= 0) {
-            Computer<Pt>::cancel_build();
-            return;
-        }
-
+        const bool sorted_path = sorted_pipeline_on() && ya::is_no_gen_forces<Pt>(gen_forces);
+        // a small system whose steps may run as a graph reads n first, then replays / captures / launches
+        const bool graph = sorted_path && graph_steps != 0 && last_key.n > 0 && !Computer<Pt>::profiler.active() &&
+                           (graph_steps > 0 || last_key.n < YA_GRAPH_MAX_CELLS);
+        const int n = read_n(!graph && sorted_pipeline_on());
+        if (n <= 0) return;
+        if constexpr (has_grid)
+            if (graph && graph_step<pw_int, pw_friction>(n, dt, gen_forces)) return;
         heun_stages<pw_int, pw_friction>(n, dt, gen_forces);
-        last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};  // (after the launches, as above)
+        last_key = sorted_path ? key_of<pw_int, pw_friction>(n, dt) : Step_key{};  // (after the launches: they may have allocated)
     }
 
     // k steps in one call, bit for bit what k calls of take_step leave in d_X, d_old_v, d_n, d_dX, d_dX1 and
@@ -2925,26 +2946,50 @@ protected:
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(const float dt, const int k, Generic_forces<Pt> gen_forces)
     {
-        if (take_steps_carried<pw_int, pw_friction>(dt, k, gen_forces)) return;
+        if constexpr (has_grid)
+            if (take_steps_carried<pw_int, pw_friction>(dt, k, gen_forces)) return;
         for (int s = 0; s < k; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
+    }
+    // The update kernels of a carried call, one launch each.  Bin: the kernel bins the entries it stores (bin_in_update);
+    // Tiles (four_tile_updates, with bin_in_update): its workgroups take so many tiles of UPDATE_BLOCK slots each, so
+    // that the fold of the partial sums that each of them repeats runs in a quarter as many.
+    template<typename F>
+    void with_update_shape(F&& f) const
+    {
+        if (!bin_in_update) return f(std::false_type{}, std::integral_constant<int, 1>{});
+        if (four_tile_updates) return f(std::true_type{}, std::integral_constant<int, 4>{});
+        f(std::true_type{}, std::integral_constant<int, 1>{});
+    }
+    template<typename Bin, typename Tiles>
+    void predict(Bin, Tiles, const int n, const float dt, const ya::Fix_args fix, const ya::Sorted_buffers<Pt>& at,
+        const ya::Grid_bin bin)
+    {
+        constexpr int TILES = Tiles::value;
+        const int wgs = (n + TILES * ya::UPDATE_BLOCK - 1) / (TILES * ya::UPDATE_BLOCK);
+        euler_step<Pt, Fix::partials, Bin::value, TILES><<<wgs, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, fix, d_dX, d_X,
+            nullptr, at.rhs, at.cells, n, nullptr, nullptr, ya::Guard_band{}, at.carried, bin);
+    }
+    template<typename Bin, typename Tiles>
+    void correct(Bin, Tiles, const int n, const float dt, const ya::Fix_args fix1, const ya::Sorted_buffers<Pt>& at,
+        Pt* X_by_id, float3* v_by_id, const ya::Grid_bin bin)
+    {
+        constexpr int TILES = Tiles::value;
+        const int wgs = (n + TILES * ya::UPDATE_BLOCK - 1) / (TILES * ya::UPDATE_BLOCK);
+        heun_step_sorted<Pt, Bin::value, TILES><<<wgs, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, d_mean_first, fix1, at.cells,
+            at.rhs, at.carried_slots, at.carried_rhs, at.carried, at.carried_v, X_by_id, v_by_id, bin);
     }
     // false: does not qualify, nothing was done
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     bool take_steps_carried(const float dt, const int k, Generic_forces<Pt>& gen_forces)
     {
-        if (!carry_sorted || k < 2 || graph_steps != 0 || keep_order) return false;
-        if (!(fix_com and !fix_com_z and fold_in_update) || !ya::is_no_gen_forces<Pt>(gen_forces)) return false;
+        if (!Computer<Pt>::carries || !carry_sorted || k < 2 || graph_steps != 0 || keep_order) return false;
+        if (!update_folds_mean() || !ya::is_no_gen_forces<Pt>(gen_forces)) return false;
         if (!Computer<Pt>::carry_ready(n_max)) return false;  // (may allocate: before anything is queued)
-        int n;
-        Computer<Pt>::begin_build(d_X, d_n, n_max, n_reader);
-        YA_CHECK(ya_n_read_end(n_reader, &n));
-        assert(n <= n_max);
+        const int n = read_n(true);
         if (n <= 0) {  // nothing is carried, nothing is stale: the rest of the loop as it is
-            Computer<Pt>::cancel_build();
             for (int s = 1; s < k; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
             return true;
         }
-        const int blocks = (n + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
         // bin_in_update: every rebuild of the call (stage 2, and stage 1 of steps 2 .. k) bins the entries that
         // the update kernel in front of it has just stored, so that kernel bins them itself and the rebuild runs
         // without k_bin.  INVARIANT: the grid's count[] is zero between builds only because a scan follows every
@@ -2955,31 +3000,7 @@ protected:
         const bool fuse = bin_in_update;
         const ya::Grid_bin bin = fuse ? Computer<Pt>::bin_target() : ya::Grid_bin{};
         const unsigned quiet = fuse && trim_carried_stores ? YA_REBUILD_PRIVATE : 0u;
-        // four_tile_updates (with bin_in_update): a workgroup of the update kernels takes four tiles of slots, so
-        // the fold of the partial sums that each of them repeats runs in a quarter as many
-        const auto launch = [&](auto tiles, auto kernel_of, auto... args) {
-            constexpr int T = decltype(tiles)::value;
-            const int wgs = (n + T * ya::UPDATE_BLOCK - 1) / (T * ya::UPDATE_BLOCK);
-            kernel_of(tiles)<<<wgs, ya::UPDATE_BLOCK, 0, this->stream>>>(args...);
-        };
-        const auto tiled = [&](auto kernel_of, auto... args) {
-            if (four_tile_updates)
-                launch(std::integral_constant<int, 4>{}, kernel_of, args...);
-            else
-                launch(std::integral_constant<int, 1>{}, kernel_of, args...);
-        };
-        const auto predict = [&](const int n, const float dt, const ya::Fix_args fix, const ya::Grid_bin bin) {
-            tiled([](auto t) { return euler_step<Pt, Fix::partials, true, decltype(t)::value>; }, n, dt, fix,
-                (const Pt*)d_dX, (const Pt*)d_X, (Pt*)nullptr, Computer<Pt>::sorted_rhs(), Computer<Pt>::sorted_cells(),
-                n, (Pt*)nullptr, (float*)nullptr, ya::Guard_band{}, Computer<Pt>::carried_cells(), bin);
-        };
-        const auto correct = [&](auto binning, const int n, const float dt, const ya::Fix_args fix1, Pt* X_by_id,
-                                 float3* v_by_id, const ya::Grid_bin bin) {
-            tiled([](auto t) { return heun_step_sorted<Pt, decltype(binning)::value, decltype(t)::value>; }, n, dt,
-                (const float*)d_mean_first, fix1, (const ya::Entry<Pt>*)Computer<Pt>::sorted_cells(),
-                Computer<Pt>::sorted_rhs(), Computer<Pt>::carried_slots(), Computer<Pt>::carried_rhs(),
-                Computer<Pt>::carried_cells(), Computer<Pt>::carried_v(), X_by_id, v_by_id, bin);
-        };
+        const ya::Sorted_buffers<Pt> at = Computer<Pt>::sorted_buffers();
         for (int s = 0; s < k; s++) {
             const bool last = s == k - 1;
             int n_partials = 0;
@@ -2989,24 +3010,16 @@ protected:
                 Computer<Pt>::template pwints_carried<pw_int, pw_friction>(1, n, d_dX, fuse, quiet);
             YA_CHECK(ya_reduce_partials(d_dX, n_floats, n, d_workspace, &n_partials, this->stream));
             const ya::Fix_args fix{d_workspace, n_partials, d_mean_first};
-            if (fuse)
-                predict(n, dt, fix, bin);
-            else
-                euler_step<Pt, Fix::partials><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, fix, d_dX, d_X,
-                    nullptr, Computer<Pt>::sorted_rhs(), Computer<Pt>::sorted_cells(), n, nullptr, nullptr,
-                    ya::Guard_band{}, Computer<Pt>::carried_cells());
+            with_update_shape([&](auto binning, auto tiles) { predict(binning, tiles, n, dt, fix, at, bin); });
             Computer<Pt>::template pwints_carried<pw_int, pw_friction>(2, n, d_dX1, fuse, last ? 0u : quiet);
             YA_CHECK(ya_reduce_partials(d_dX1, n_floats, n, d_workspace, &n_partials, this->stream));
             const ya::Fix_args fix1{d_workspace, n_partials};
-            if (fuse && !last)  // (the invariant above)
-                correct(std::true_type{}, n, dt, fix1, nullptr, nullptr, bin);
-            else if (fuse)
-                correct(std::false_type{}, n, dt, fix1, d_X, d_old_v, ya::Grid_bin{});
-            else
-                heun_step_sorted<Pt><<<blocks, ya::UPDATE_BLOCK, 0, this->stream>>>(n, dt, d_mean_first, fix1,
-                    Computer<Pt>::sorted_cells(), Computer<Pt>::sorted_rhs(), Computer<Pt>::carried_slots(),
-                    Computer<Pt>::carried_rhs(), Computer<Pt>::carried_cells(), Computer<Pt>::carried_v(),
-                    last ? d_X : nullptr, last ? d_old_v : nullptr);
+            with_update_shape([&](auto binning, auto tiles) {
+                if (last)  // (the invariant above)
+                    correct(std::false_type{}, tiles, n, dt, fix1, at, d_X, d_old_v, ya::Grid_bin{});
+                else
+                    correct(binning, tiles, n, dt, fix1, at, nullptr, nullptr, bin);
+            });
         }
         if (fuse) fused_bin_rebuilds += 2 * k - 1;
         stage1_fix = d_mean_first;
@@ -3028,7 +3041,7 @@ class Tile_computer {
 public:
     Tile_computer(int n_max) {}
     ya::Profiler profiler;
-    bool use_sorted_pipeline() const { return false; }
+    static constexpr bool has_grid = false, carries = false;  // (what Heun_solver may ask of a computer)
     // 0 (default) = one thread owns a cell for the whole stage, as in the reference, unless the
     // functors are declared stateless (YA_STATELESS): then 64 lanes per cell up to 4096 cells and
     // 16 above; 1 = always one thread per cell; 16 or 64 = ya::tile_force_coop with that many
@@ -3038,29 +3051,7 @@ public:
 
 protected:
     hipStream_t stream = nullptr;  // every launch of a step goes here (null = the default stream)
-    float step_cube_size() const { return 0; }
     using Step_variant = int;  // (no captured step: Heun_solver::Step_key)
-    Step_variant step_variant() const { return 0; }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    bool ready_to_capture(int) const { return false; }
-    void check_status() {}
-    void begin_build(const Pt*, const int*, int, ya_n_reader*) {}
-    void cancel_build() {}
-    const int* cube_order(int, const Pt*) { return nullptr; }  // no grid: renumber() is a no-op
-    void ids_changed() {}
-    const Pt* sorted_rhs() const { return nullptr; }
-    ya::Entry<Pt>* sorted_cells() { return nullptr; }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void pwints_from_sorted(int, Pt*, int, bool) {}
-    // no cube order to carry from step to step (Heun_solver::take_steps)
-    bool carry_ready(int) { return false; }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void pwints_carried(int, int, Pt*, bool, unsigned) {}
-    ya::Grid_bin bin_target() { return {}; }
-    ya::Entry<Pt>* carried_cells() { return nullptr; }
-    float4* carried_v() { return nullptr; }
-    const Pt* carried_rhs() const { return nullptr; }
-    const int* carried_slots() const { return nullptr; }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints(const int n, const Pt* __restrict__ d_X, const float3* __restrict__ d_old_v,
         Pt* d_dX, const bool has_gen, const int n_active, const bool keep_sorted)
@@ -3214,6 +3205,81 @@ __constant__ int d_nhood[27];  // stencil offsets for model kernels (solvers.cuh
 
 enum Ya_sum_order { YA_SUM_REFERENCE = 0, YA_SUM_BY_PLANE = 1 };  // Grid_computer::sum_order
 
+namespace ya {
+// One launch of a force kernel.  A timed launch (start given) carries its events in the dispatch itself
+// (ya::Profiler); an untimed one is a plain launch, which is also what a stream capture records.
+template<typename... Params, typename... Args>
+void launch(void (*kernel)(Params...), const dim3 grid, const dim3 block, hipStream_t stream, hipEvent_t start,
+    hipEvent_t stop, Args... args)
+{
+    if (start)
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, start, stop, 0, static_cast<Params>(args)...);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<Params>(args)...);
+}
+// The runtime-to-template choices of the grid force launches, each written once: f is a generic lambda that is handed
+// the choice as std::integral_constant values.  Exactly these combinations are built, no others.
+namespace coop {
+template<typename F>
+bool with_lanes(const int lanes, F&& f)  // false: not a grid_force_coop launch
+{
+    if (lanes == 16) return f(std::integral_constant<int, 16>{}), true;
+    if (lanes == 8) return f(std::integral_constant<int, 8>{}), true;
+    if (lanes == 4) return f(std::integral_constant<int, 4>{}), true;
+    return false;
+}
+}  // namespace coop
+namespace bits {
+// (STAGE_V, OFF32): old_v from LDS, where every offset fits 32 bits; else from global memory through 32-bit byte
+// offsets while 16 n fits them, through 64-bit addresses beyond
+template<typename F>
+void with_gather(const bool stage_v, const bool off32, F&& f)
+{
+    if (stage_v) return f(std::true_type{}, std::true_type{});
+    if (off32) return f(std::false_type{}, std::true_type{});
+    f(std::false_type{}, std::false_type{});
+}
+// The shape of one grid_force_bits launch of n cells, pure arithmetic: Grid_computer::forces launches by it, and
+// Grid_computer::ready_to_capture asks the same function.
+// HALF TILES ("the tail"; tail > 0: the last so many tiles of the launch, < 0: all, 0: none).  With R = `resident`
+// one-wavefront workgroups on the chip at once (5120 for springs): launches of up to R / 2 tiles are made of halves
+// altogether; up to R tiles, as many tiles are split as fill the chip in its one round (R - tiles); beyond, the launch
+// ends with 768 tiles as halves (measured at 2 * 10^5 ... 10^7 cells, profiles/r05_tail_ab.txt).  A slab stage's two
+// launches (part 1 / 2) run side by side: all halves only if both fit at once; the kernel leaves a list of < 4 tails'
+// tiles whole.  Two wavefronts then call the functor for the same cell i at once: only for functors declared stateless
+// (YA_STATELESS; relu_w_epithelium's `d_mes_nbs[i] += 1` would lose counts), and only summing by plane.
+struct Plan_settings {
+    bool by_plane, stateless;                         // Grid_computer::sum_order, ya::stateless_pair
+    int tail_tiles, stage_v_max, gather_offset_bits;  // Grid_computer::force_tail_tiles, ...
+    bool tail_by_residency() const { return by_plane && stateless && tail_tiles < 0; }  // else `resident` is not read
+};
+struct Plan {
+    int tiles, tail, room, blocks;  // room: exchange slots the tail needs; blocks: workgroups launched
+    bool stage_v, off32;
+    bool fits(const int tail_room) const { return room <= tail_room; }  // no exchange area has to be allocated
+};
+inline Plan plan(const int n, const int part, const int resident, const Plan_settings& s)
+{
+    Plan p{};
+    p.tiles = (n + BLOCK - 1) / BLOCK;
+    if (!s.by_plane || !s.stateless)
+        p.tail = 0;
+    else if (s.tail_tiles >= 0)
+        p.tail = s.tail_tiles >= p.tiles ? -1 : s.tail_tiles;
+    else if (2 * p.tiles <= resident)
+        p.tail = -1;
+    else
+        p.tail = part == 0 && p.tiles <= resident ? resident - p.tiles : 768;
+    p.room = p.tail < 0 ? p.tiles : p.tail;
+    p.blocks = p.tail < 0 ? 16 * ((p.tiles + 7) / 8) : p.tiles + (p.tail > 0 ? std::min(p.tail, p.tiles) + 24 : 0);
+    // (old_v in LDS costs a launch of halves the residency it lives on: 13 KB per workgroup are 12 per CU)
+    p.stage_v = n <= s.stage_v_max && p.tail >= 0;
+    p.off32 = s.gather_offset_bits != 64 && offsets_fit_32_bits(n);
+    return p;
+}
+}  // namespace bits
+}  // namespace ya
+
 template<typename Pt>
 class Grid_computer {
 public:
@@ -3244,10 +3310,8 @@ public:
     // self pair where the pass' rows cannot hold the lane's own slot, and dist < 1 for every hit while cube_size <= 1
     // (exact tier); 0 = the generic bodies only; 2 / 3 = the first / the second fact alone (A/B).  Same results.
     int pass_facts = 1;
-    bool gathers_by_32_bit_offsets(const int n) const
-    {
-        return gather_offset_bits != 64 && ya::bits::offsets_fit_32_bits(n);
-    }
+    // (Heun_solver's traits; use_sorted_pipeline() and carry_ready() say when the cells are kept cube-sorted)
+    static constexpr bool has_grid = true, carries = true;
     Grid_computer(int n_max, int grid_size = 50, float cube_size = 1)
         : cube_size{cube_size}, grid{n_max, grid_size}
     {
@@ -3326,7 +3390,6 @@ public:
 
 protected:
     hipStream_t stream = nullptr;  // every launch of a step goes here (null = the default stream)
-    float step_cube_size() const { return cube_size; }
     // Everything of this class that a captured step bakes into its launches (Heun_solver::Step_key compares it
     // at every step: the members are public and assigned directly).  A member added to forces() that picks a
     // kernel, a launch size or a kernel argument belongs here too.
@@ -3335,13 +3398,12 @@ protected:
         int pass_facts = 1;
         int tail_areas = 0;  // allocations of tail exchange areas so far: a graph made before one holds freed pointers
         const int* global_id = nullptr;
-        bool operator==(const Step_variant& o) const
+        auto tied() const
         {
-            return force_variant == o.force_variant && sum_order == o.sum_order && coop_lanes == o.coop_lanes &&
-                   stage_v_max == o.stage_v_max && tail_tiles == o.tail_tiles &&
-                   gather_offset_bits == o.gather_offset_bits && pass_facts == o.pass_facts &&
-                   tail_areas == o.tail_areas && global_id == o.global_id;
+            return std::tie(force_variant, sum_order, coop_lanes, stage_v_max, tail_tiles, gather_offset_bits, pass_facts,
+                tail_areas, global_id);
         }
+        bool operator==(const Step_variant& o) const { return tied() == o.tied(); }
     };
     Step_variant step_variant() const
     {
@@ -3396,35 +3458,65 @@ protected:
     void forces(const int n, const ya::Entry<Pt>* d_cells, const float4* d_cells_v, Pt* d_dX,
         const bool has_gen, const int n_active, Pt* d_dX_in_cell_order)
     {
-        const int blocks = (n + ya::FORCE_BLOCK - 1) / ya::FORCE_BLOCK;
         hipEvent_t start, stop;
         profiler.next(&start, &stop);
         const float cut2 = ya::cutoff_squared(cube_size);
         const bool by_plane = sum_order == YA_SUM_BY_PLANE;
-        // a timed launch carries its events in the dispatch itself (ya::Profiler); an untimed
-        // one is a plain launch, which is also what a stream capture records
-#define YA_FORCE_LAUNCH(kernel_, grid_, block_, ...)                                          \
-    if (start)                                                                                \
-        hipExtLaunchKernelGGL((kernel_), dim3(grid_), dim3(block_), 0, stream, start, stop, 0, \
-            __VA_ARGS__);                                                                     \
-    else                                                                                      \
-        hipLaunchKernelGGL((kernel_), dim3(grid_), dim3(block_), 0, stream, __VA_ARGS__)
         // the kernel this launch goes to: an explicit choice, or by what the model said about its functors
         const Kernel_choice choice = kernel_choice<pw_int, pw_friction>(n);
-        const int force_variant = choice.variant, lanes = choice.lanes;
-        if (force_variant < 0 || force_variant > 3) {
-            fprintf(stderr, "yalla-hip: Grid_computer::force_variant %d is not a kernel (-1, 0, 1, 2, 3)\n", force_variant);
+        if (choice.variant < 0 || choice.variant > 3) {
+            fprintf(stderr, "yalla-hip: Grid_computer::force_variant %d is not a kernel (-1, 0, 1, 2, 3)\n", choice.variant);
             abort();
         }
-        // two launches per stage (force_part) are what grid_force_bits offers; the other kernels
-        // compute every tile in the first call
-        const bool bits_kernel = choice.bits_kernel();
-        int part = 0;
-        hipStream_t stream = this->stream;
+        const int part = slab_part({n, n_active, d_cells, d_cells_v, d_dX, d_dX_in_cell_order, has_gen, choice.bits_kernel()});
+        hipStream_t stream = part == 2 ? interior_stream : this->stream;
+        const bool coop = ya::coop::with_lanes(choice.lanes, [&](auto lanes) {
+            constexpr int CELLS = ya::coop::BLOCK / decltype(lanes)::value;
+            ya::launch(ya::grid_force_coop<Pt, pw_int, pw_friction, decltype(lanes)::value>, (n + CELLS - 1) / CELLS,
+                ya::coop::BLOCK, stream, start, stop, n, d_cells, d_cells_v, grid.d_cube_id, grid.offsets(),
+                grid.grid_size, grid.n_cubes, cut2, d_dX, has_gen, n_active, d_dX_in_cell_order, d_global_id, by_plane);
+        });
+        if (coop) return;
+        if (choice.variant >= 2) {
+            const ya::bits::Plan plan = bits_plan<pw_int, pw_friction>(n, part);
+            ensure_tail_room<pw_int, pw_friction>(part, plan.room);
+            const auto launch_bits = [&](auto global_ids) {
+                ya::bits::with_gather(plan.stage_v, plan.off32, [&](auto stage_v, auto off32) {
+                    ya::launch(ya::grid_force_bits<Pt, pw_int, pw_friction, decltype(stage_v)::value,
+                                   decltype(global_ids)::value, decltype(off32)::value>,
+                        plan.blocks, ya::bits::BLOCK, stream, start, stop, n, d_cells, d_cells_v, grid.d_cube_id,
+                        grid.offsets(), grid.grid_size, grid.n_cubes, cut2, d_dX, has_gen, n_active, d_dX_in_cell_order,
+                        d_global_id, plan.tiles, plan.tail, d_tail_exchange[part], d_tail_tickets[part], by_plane, part,
+                        force_part_cube_lo, force_part_cube_hi, force_own_cube_lo, force_own_cube_hi,
+                        ya::bits::launch_facts(pass_facts, cut2));
+                });
+            };
+            return d_global_id ? launch_bits(std::true_type{}) : launch_bits(std::false_type{});
+        }
+#ifdef YA_EXPERIMENTAL_FORCE_VARIANTS
+        const int blocks = (n + ya::FORCE_BLOCK - 1) / ya::FORCE_BLOCK;
+        if (choice.variant == 0)
+            ya::launch(ya::grid_force_direct<Pt, pw_int, pw_friction>, blocks, ya::FORCE_BLOCK, stream, start, stop, n,
+                d_cells, d_cells_v, grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes, cube_size, d_dX,
+                has_gen, n_active, d_global_id, by_plane);
+        else
+            ya::launch(ya::grid_force<Pt, pw_int, pw_friction>, blocks, ya::FORCE_BLOCK, stream, start, stop, n, d_cells,
+                d_cells_v, grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes, cut2, d_dX, has_gen, n_active,
+                d_dX_in_cell_order, d_global_id, by_plane);
+#else
+        fprintf(stderr, "yalla-hip: Grid_computer::force_variant %d is an A/B baseline kept in "
+                        "tools/ab/force_variants.cuh: compile with -DYA_EXPERIMENTAL_FORCE_VARIANTS -Itools/ab\n", choice.variant);
+        abort();
+#endif
+    }
+    // A z-slab's stage as two launches (force_part; what grid_force_bits offers -- the other kernels compute every tile
+    // in the first call): which part the launch of `call` is -- 0 the whole stage, 1 the tiles next to the slab's faces,
+    // 2 the rest -- with what orders part 2, on its own stream, behind the grid build and not behind part 1.
+    int slab_part(const Forces_call& call)
+    {
         if (force_part == 1) {
-            boundary_call = Forces_call{n, n_active, d_cells, d_cells_v, d_dX, d_dX_in_cell_order, has_gen, bits_kernel};
-            if (bits_kernel) {
-                part = 1;
+            boundary_call = call;
+            if (call.split) {
                 if (!interior_stream) {
                     // YA_INTERIOR_LOW_PRIORITY=1: the boundary launch, whose rows the neighbours
                     // wait for, gets the chip first.  Measured in the one-GPU rehearsal (10 M cells,
@@ -3443,113 +3535,47 @@ protected:
                 }
                 // the interior launch needs the grid, not the boundary launch
                 YA_CHECK((int)hipEventRecord(grid_built, stream));
+                return 1;
             }
         } else if (force_part == 2) {
-            part = 2;
-            stream = interior_stream;
             YA_CHECK((int)hipStreamWaitEvent(interior_stream, grid_built, 0));
+            return 2;
         }
-#define YA_COOP_LAUNCH(lanes_)                                                                 \
-    YA_FORCE_LAUNCH((ya::grid_force_coop<Pt, pw_int, pw_friction, lanes_>),                    \
-        (n + ya::coop::BLOCK / lanes_ - 1) / (ya::coop::BLOCK / lanes_), ya::coop::BLOCK, n,   \
-        d_cells, d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size,        \
-        grid.n_cubes, cut2, d_dX, has_gen, n_active, d_dX_in_cell_order, (const int*)d_global_id, by_plane)
-        if (lanes == 16) {
-            YA_COOP_LAUNCH(16);
-        } else if (lanes == 8) {
-            YA_COOP_LAUNCH(8);
-        } else if (lanes == 4) {
-            YA_COOP_LAUNCH(4);
-        } else if (force_variant == 2 || force_variant == 3) {
-#define YA_BITS_LAUNCH(stage_v_, gids_, off32_)                                                \
-    YA_FORCE_LAUNCH((ya::grid_force_bits<Pt, pw_int, pw_friction, stage_v_, gids_, off32_>),   \
-        tail < 0 ? 16 * ((tiles + 7) / 8) : tiles + (tail > 0 ? std::min(tail, tiles) + 24 : 0), ya::bits::BLOCK, n, d_cells, \
-        d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes, cut2, d_dX,  \
-        has_gen, n_active, d_dX_in_cell_order, (const int*)d_global_id, tiles, tail,           \
-        d_tail_exchange[part], d_tail_tickets[part], by_plane, part, force_part_cube_lo,                 \
-        force_part_cube_hi, force_own_cube_lo, force_own_cube_hi, ya::bits::launch_facts(pass_facts, cut2))
-            const int tiles = (n + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
-            // Half tiles (grid_force_bits, "the tail"; > 0: the last so many tiles of the launch, < 0: all).
-            // With R one-wavefront workgroups resident at once (5120 for springs): launches of up to R / 2 tiles
-            // are made of halves altogether; up to R tiles, as many tiles are split as fill the chip in its one
-            // round (R - tiles); beyond, the launch ends with 768 tiles as halves (measured at 2 * 10^5 ...
-            // 10^7 cells, profiles/r05_tail_ab.txt).  Two wavefronts then call the functor for the same cell i
-            // at once: only for functors declared stateless (YA_STATELESS; relu_w_epithelium's
-            // `d_mes_nbs[i] += 1` would lose counts).
-            const int tail = tail_of<pw_int, pw_friction>(tiles, part);
-            const int room = tail < 0 ? tiles : tail;
-            if (room > 0 && (!d_tail_exchange[part] || tail_room[part] < room)) {
-                // (a solver's launches are stream-ordered except parts 1 and 2 of a slab stage, which have
-                // exchange areas of their own)
-                constexpr int NC = ya::N_floats<Pt>::value + 4;
-                // Never inside a stream capture: Heun_solver::take_step captures a step only after the same step
-                // ran plainly (which came through here) and after ready_to_capture() said nothing is missing.
-                // Should a new path get here all the same, say what happened instead of a bare HIP error code.
-                hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-                if (this->stream) YA_CHECK((int)hipStreamIsCapturing(this->stream, &capturing));
-                if (capturing != hipStreamCaptureStatusNone) {
-                    fprintf(stderr, "yalla-hip: grid_force_bits' tail exchange area would have to be allocated inside a "
-                                    "stream capture (Grid_computer::ready_to_capture missed a case)\n");
-                    abort();
-                }
-                YA_CHECK(ya_device_synchronize());
-                if (d_tail_exchange[part]) ya_free(d_tail_exchange[part]), ya_free(d_tail_tickets[part]);
-                // once per solver, not once per size: a system that grows (proliferation) asks for a tile more
-                // every few steps while its launches are made of halves, which they are up to `resident` tiles
-                const int most = std::min((grid.n_max + ya::bits::BLOCK - 1) / ya::bits::BLOCK,
-                    std::max(resident_workgroups<ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>>(), 768));
-                const size_t slots = (size_t)std::max(room, most) + 8;
-                YA_CHECK(ya_malloc((void**)&d_tail_exchange[part], slots * 2 * NC * ya::bits::BLOCK * sizeof(float)));
-                YA_CHECK(ya_malloc((void**)&d_tail_tickets[part], slots * sizeof(int)));
-                YA_CHECK(ya_memset_async(d_tail_tickets[part], 0, slots * sizeof(int), nullptr));
-                YA_CHECK(ya_device_synchronize());
-                tail_room[part] = (int)slots - 8;
-                tail_areas++;  // (graphs captured so far hold the freed areas' addresses: Step_variant)
-            }
-            // (old_v in LDS costs a launch of halves the residency it lives on: 13 KB per workgroup are 12 per CU)
-            const bool stage_v = n <= stage_v_max && tail >= 0;
-            // (old_v from global memory: through 32-bit byte offsets while 16 n fits them; staged old_v is
-            // addressed in LDS, where every offset does)
-            const bool off32 = gathers_by_32_bit_offsets(n);
-            if (d_global_id) {
-                if (stage_v) {
-                    YA_BITS_LAUNCH(true, true, true);
-                } else if (off32) {
-                    YA_BITS_LAUNCH(false, true, true);
-                } else {
-                    YA_BITS_LAUNCH(false, true, false);
-                }
-            } else if (stage_v) {
-                YA_BITS_LAUNCH(true, false, true);
-            } else if (off32) {
-                YA_BITS_LAUNCH(false, false, true);
-            } else {
-                YA_BITS_LAUNCH(false, false, false);
-            }
-#undef YA_BITS_LAUNCH
-        }
-#ifdef YA_EXPERIMENTAL_FORCE_VARIANTS
-        else if (force_variant == 0) {
-            YA_FORCE_LAUNCH((ya::grid_force_direct<Pt, pw_int, pw_friction>), blocks, ya::FORCE_BLOCK, n,
-                d_cells, d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size,
-                grid.n_cubes, cube_size, d_dX, has_gen, n_active, (const int*)d_global_id, by_plane);
-        } else {
-            YA_FORCE_LAUNCH((ya::grid_force<Pt, pw_int, pw_friction>), blocks, ya::FORCE_BLOCK, n, d_cells,
-                d_cells_v, (const int*)grid.d_cube_id, grid.offsets(), grid.grid_size, grid.n_cubes,
-                cut2, d_dX, has_gen, n_active, d_dX_in_cell_order, (const int*)d_global_id, by_plane);
-        }
-#else
-        else {
-            fprintf(stderr, "yalla-hip: Grid_computer::force_variant %d is an A/B baseline kept in "
-                            "tools/ab/force_variants.cuh: compile with -DYA_EXPERIMENTAL_FORCE_VARIANTS -Itools/ab\n", force_variant);
+        return 0;
+    }
+    // Room for `room` half tiles' sums in part's exchange area (a solver's launches are stream-ordered except parts 1
+    // and 2 of a slab stage, which have exchange areas of their own).
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void ensure_tail_room(const int part, const int room)
+    {
+        if (room <= tail_room[part]) return;
+        constexpr int NC = ya::N_floats<Pt>::value + 4;
+        // Never inside a stream capture: Heun_solver::take_step captures a step only after the same step
+        // ran plainly (which came through here) and after ready_to_capture() said nothing is missing.
+        // Should a new path get here all the same, say what happened instead of a bare HIP error code.
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (this->stream) YA_CHECK((int)hipStreamIsCapturing(this->stream, &capturing));
+        if (capturing != hipStreamCaptureStatusNone) {
+            fprintf(stderr, "yalla-hip: grid_force_bits' tail exchange area would have to be allocated inside a "
+                            "stream capture (Grid_computer::ready_to_capture missed a case)\n");
             abort();
         }
-#endif
-#undef YA_COOP_LAUNCH
-#undef YA_FORCE_LAUNCH
+        YA_CHECK(ya_device_synchronize());
+        if (d_tail_exchange[part]) ya_free(d_tail_exchange[part]), ya_free(d_tail_tickets[part]);
+        // once per solver, not once per size: a system that grows (proliferation) asks for a tile more
+        // every few steps while its launches are made of halves, which they are up to `resident` tiles
+        const int most = std::min((grid.n_max + ya::bits::BLOCK - 1) / ya::bits::BLOCK,
+            std::max(resident_workgroups<ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>>(), 768));
+        const size_t slots = (size_t)std::max(room, most) + 8;
+        YA_CHECK(ya_malloc((void**)&d_tail_exchange[part], slots * 2 * NC * ya::bits::BLOCK * sizeof(float)));
+        YA_CHECK(ya_malloc((void**)&d_tail_tickets[part], slots * sizeof(int)));
+        YA_CHECK(ya_memset_async(d_tail_tickets[part], 0, slots * sizeof(int), nullptr));
+        YA_CHECK(ya_device_synchronize());
+        tail_room[part] = (int)slots - 8;
+        tail_areas++;  // (graphs captured so far hold the freed areas' addresses: Step_variant)
     }
-    // The kernel a launch of n cells goes to (forces(), and ready_to_capture() which must agree with it): an
-    // explicit choice, or by what the model said about its functors; lanes per cell (1: not grid_force_coop)
+    // The kernel a launch of n cells goes to (forces() and ready_to_capture()): an explicit choice, or by what the
+    // model said about its functors; lanes per cell (1: not grid_force_coop)
     struct Kernel_choice {
         int variant, lanes;
         bool bits_kernel() const { return lanes == 1 && variant >= 2; }  // grid_force_bits: tails, two launches per stage
@@ -3562,27 +3588,21 @@ protected:
             variant == 3 ? (coop_lanes ? coop_lanes : ya::coop::lanes_for(n, sum_order == YA_SUM_BY_PLANE)) : 1;
         return {variant, lanes};
     }
-    // grid_force_bits' tail for a launch of `tiles` tiles: > 0 the last so many as half tiles, < 0 all, 0 none
+    // ya::bits::plan of this computer's settings; the occupancy is asked for only where the plan reads it
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    int tail_of(const int tiles, const int part)
+    ya::bits::Plan bits_plan(const int n, const int part) const
     {
-        if (sum_order != YA_SUM_BY_PLANE || !ya::stateless_pair<Pt, pw_int, pw_friction>()) return 0;
-        if (force_tail_tiles >= 0) return force_tail_tiles >= tiles ? -1 : force_tail_tiles;
-        const int resident = resident_workgroups<ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>>();
-        if (part != 0)  // a slab stage's two launches, side by side: all halves only if both fit at once;
-            return 2 * tiles <= resident ? -1 : 768;  // the kernel leaves a list of < 4 tails' tiles whole
-        return 2 * tiles <= resident ? -1 : (tiles <= resident ? resident - tiles : 768);
+        const ya::bits::Plan_settings s{sum_order == YA_SUM_BY_PLANE, ya::stateless_pair<Pt, pw_int, pw_friction>(),
+            force_tail_tiles, stage_v_max, gather_offset_bits};
+        constexpr auto kernel = ya::grid_force_bits<Pt, pw_int, pw_friction, false, false>;
+        return ya::bits::plan(n, part, s.tail_by_residency() ? resident_workgroups<kernel>() : 0, s);
     }
     // Heun_solver::take_step before it captures a step of n cells: would forces() have to allocate?  (The captured
     // step is an undivided one: part 0.)
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    bool ready_to_capture(const int n)
+    bool ready_to_capture(const int n) const
     {
-        if (!kernel_choice<pw_int, pw_friction>(n).bits_kernel()) return true;
-        const int tiles = (n + ya::bits::BLOCK - 1) / ya::bits::BLOCK;
-        const int tail = tail_of<pw_int, pw_friction>(tiles, 0);
-        const int room = tail < 0 ? tiles : tail;
-        return room <= 0 || (d_tail_exchange[0] && tail_room[0] >= room);
+        return !kernel_choice<pw_int, pw_friction>(n).bits_kernel() || bits_plan<pw_int, pw_friction>(n, 0).fits(tail_room[0]);
     }
     // Heun_solver::renumber: the cells' ids in (cube, id) order = the point ids of a fresh build
     const int* cube_order(const int n, const Pt* d_X)
@@ -3613,9 +3633,11 @@ protected:
         forces<pw_int, pw_friction>(n, d_sorted, d_sorted_v, d_dX, has_gen, n_active,
             keep_sorted ? d_dX_sorted : nullptr);
     }
-    // the cube-sorted copy stage 1 kept and its right-hand side in sorted order (Heun_solver::stage_update moves it)
-    const Pt* sorted_rhs() const { return d_dX_sorted; }
-    ya::Entry<Pt>* sorted_cells() { return d_sorted; }
+    // (the corrector's {old_v, 0} go to d_resorted_v, dead after stage 2's force launch)
+    ya::Sorted_buffers<Pt> sorted_buffers()
+    {
+        return {d_sorted, d_dX_sorted, d_carried, d_resorted_v, d_carried_rhs, d_carried_slots};
+    }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void pwints_from_sorted(const int n, Pt* d_dX, const int n_active, const bool has_gen)
     {
@@ -3627,7 +3649,6 @@ protected:
     //   d_carried        entries: the predictor's output, then -- dead once stage 2 is built -- the corrector's
     //   d_carried_rhs    stage 2's right-hand sides in stage 2's sorted order
     //   d_carried_slots  stage-1 slot -> stage-2 slot
-    // (the corrector's {old_v, 0} go to d_resorted_v, dead after stage 2's force launch)
     ya::Entry<Pt>* d_carried = nullptr;
     Pt* d_carried_rhs = nullptr;
     int* d_carried_slots = nullptr;
@@ -3671,10 +3692,6 @@ protected:
     }
     // where the update kernels of a carried step bin (the cube size is the one the rebuilds are given)
     ya::Grid_bin bin_target() { return ya::Grid_bin{grid.bin_target(), cube_size}; }
-    ya::Entry<Pt>* carried_cells() { return d_carried; }
-    float4* carried_v() { return d_resorted_v; }
-    const Pt* carried_rhs() const { return d_carried_rhs; }
-    const int* carried_slots() const { return d_carried_slots; }
 };
 
 template<typename Pt>
@@ -3702,8 +3719,7 @@ public:
         if (d_workspace) ya_free(d_workspace);
     }
     Gabriel_computer(const Gabriel_computer&) = delete;
-    bool use_sorted_pipeline() const { return false; }
-    bool carry_ready(int) { return false; }  // (d_X pipeline only: Heun_solver::take_steps is the loop)
+    static constexpr bool carries = false;  // (d_X pipeline only: Heun_solver::take_steps is the loop)
 
 protected:
     int* d_dense = nullptr;  // [0] cells left to gabriel_force_dense, [1] their largest count, then the cells
