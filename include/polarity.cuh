@@ -37,10 +37,20 @@ __device__ __host__ float3 pol_to_float3(Pt p)
 }
 
 // Direction of r as a polarity (polarity.cuh:24-40).
+//
+// The quotient is clamped to [-1, 1] before acosf.  With a correctly rounded dist the clamp is the identity:
+// dist >= |r.z| (sqrt(RN(z^2)) rounds to |z| and the square root is monotone), so the exact tier, the oracle and
+// every golden keep their bits.  Under YA_ARITH_FAST dist is the bare v_sqrt_f32 (<= 1 ulp), which on an MI355X
+// returns one ulp BELOW |z| for 2 % of all binary32 z on the polar axis (2 053 716 of the 100 663 296 in
+// [2^-6, 2^6); 360 408 with x = 2^-13 z beside it; tests/native/test_polarity_pairs.cu counts them): the quotient
+// then exceeds 1, acosf returns NaN and the NaN enters dF.theta / dF.phi of both cells.  Written with comparisons,
+// not fminf / fmaxf, so that a NaN quotient (r = 0, dist = 0) stays the NaN it was.
 template<typename Pt>
 __device__ __host__ Polarity pt_to_pol(Pt r, float dist)
 {
-    Polarity pol{acosf(r.z / dist), atan2f(r.y, r.x)};
+    float quotient = r.z / dist;
+    quotient = quotient > 1.f ? 1.f : (quotient < -1.f ? -1.f : quotient);
+    Polarity pol{acosf(quotient), atan2f(r.y, r.x)};
     return pol;
 }
 

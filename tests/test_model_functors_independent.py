@@ -8,36 +8,11 @@ Also the neighbour counters the functor keeps per cell (exact integers)."""
 import numpy as np
 import pytest
 
+from polarity_statement import bending_force  # (with pol_to_vec and unidirectional_polarization_force: tests/polarity_statement.py)
 from yalla_amd.solution import Solution
 
 MESENCHYME, EPITHELIUM = 0, 1
 R_MAX = 1.0  # passive_growth.cu:14
-
-
-def pol_to_vec(theta, phi):  # polarity.cuh:13-21
-    return np.array([np.sin(theta) * np.cos(phi), np.sin(theta) * np.sin(phi), np.cos(theta)])
-
-
-def unidirectional_polarization_force(theta_i, phi_i, p_theta, p_phi):  # polarity.cuh:50-60
-    d_theta = np.cos(theta_i) * np.sin(p_theta) * np.cos(phi_i - p_phi) - np.sin(theta_i) * np.cos(p_theta)
-    d_phi = 0.0
-    if abs(np.sin(theta_i)) > 1e-10:
-        d_phi = -np.sin(p_theta) * np.sin(phi_i - p_phi) / np.sin(theta_i)
-    return d_theta, d_phi
-
-
-def bending_force(Xi, r, dist):  # polarity.cuh:72-94, Xi and r = (x, y, z, theta, phi)
-    pi = pol_to_vec(Xi[3], Xi[4])
-    prodi = pi.dot(r[:3]) / dist
-    r_hat = (np.arccos(r[2] / dist), np.arctan2(r[1], r[0]))  # pt_to_pol, :23-28
-    u_theta, u_phi = unidirectional_polarization_force(Xi[3], Xi[4], *r_hat)
-    dF = np.zeros(5)
-    dF[3], dF[4] = -prodi * u_theta, -prodi * u_phi
-    dF[:3] = -prodi / dist * pi + prodi ** 2 / dist ** 2 * r[:3]
-    pj = pol_to_vec(Xi[3] - r[3], Xi[4] - r[4])  # the neighbour's polarity
-    prodj = pj.dot(r[:3]) / dist
-    dF[:3] += -prodj / dist * pj + prodj ** 2 / dist ** 2 * r[:3]
-    return dF
 
 
 def relu_w_epithelium(Xi, r, dist, i, j, types, mes_nbs, epi_nbs):  # passive_growth.cu:29-57
