@@ -27,7 +27,18 @@
 // lds_steps_max steps: a workgroup per replica sorts the replica's (cube, id) keys in LDS, finds the stencil rows by
 // searching that order and steps from LDS (ya::ens::grid_lds_steps) -- no counters, nothing of size grid_size^3 touched
 // in between.  The step itself is ya::ens::whole_steps_in_lds (ensemble.cuh), which the all-pairs whole steps call too.
-// Not built for these launches: several lanes per cell, Replica_links, the Gabriel form, the fast tier, graph capture.
+// Not built for these launches: several lanes per cell, the Gabriel form, the fast tier, graph capture.
+//
+// LINKS  cells.take_steps<my_force>(dt, K, ya::ens::Replica_links{links, S}) steps with the ORDERED link forces of a
+// Links object over the flat id space (ensemble_links.cuh: slot s belongs to replica s / S, a == b is inert, slots
+// from *links.d_n on are unused, a slot with an end outside its own replica's rows is skipped, a cell's terms are
+// added in ascending slot order from +0, the right-hand side is "zero, links, force kernel").  The result is DEFINED
+// as K calls of take_step(dt, gen) with gen calling ya::ens::link_forces_ordered<Pt>; where the replica and its
+// incidence list fit one workgroup's LDS (ya::ens::grid_lds_links_bytes<Pt>(n_max, S) != 0) and `lds_steps` allows
+// it, the call runs as launches that step from LDS (ya::ens::grid_lds_steps_linked), bit for bit alike, the public
+// grid arrays and d_status included.  Out of scope for these linked launches: the Gabriel form, several lanes per
+// cell in LDS-step launches, the fast tier, graph capture, links that change inside a launch (a launch reads the
+// links and their count at its start).
 //
 // COST  Every stage scans n_replicas * grid_size^3 counters (one workgroup per replica walks its cubes) whatever
 // the replicas hold: a sweep picks grid_size to fit its replicas, not the single system's default of 50.
@@ -255,6 +266,24 @@ constexpr int grid_lds_capacity()
     return rows;
 }
 
+// With ordered links (grid_lds_steps_linked) the replica's incidence list (ensemble_links.cuh: n_max + 1 offsets and
+// at most 2 S entries of 4 bytes, whole_step_links_list_bytes) lies behind the keys, whose end is 8-byte aligned (the
+// list needs 4): the step's arrays, then the keys, then the list.  The answer is the launch's dynamic LDS; 0 = no room
+// within the workgroup's LDS beside the fold's static scratch (an 8-float point's 1024 rows leave 896 bytes: no
+// list of 1025 offsets, whatever S is).  The rule may fill the LDS to the byte: grid_lds_steps_linked's static LDS is
+// WHOLE_STEP_STATIC_LDS and no more (grid_lds_steps' __syncthreads_or takes 256 bytes on top, which its launches spare).
+template<typename Pt>
+constexpr size_t grid_lds_links_base(const int n_max)  // where the list starts
+{
+    return grid_lds_bytes<Pt>(n_max);
+}
+template<typename Pt>
+constexpr size_t grid_lds_links_bytes(const int n_max, const int slots)
+{
+    const size_t bytes = grid_lds_links_base<Pt>(n_max) + whole_step_links_list_bytes(n_max, slots);
+    return bytes + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP ? 0 : bytes;
+}
+
 // The replica's cube ids (ya::cube_id_of, clamped as grid_count_batched clamps it) and THE ORDER: sh_key[0 .. n)
 // ascending in (cube, id), by a bitonic sort of P = the power of two from n up keys (the padding sorts last).  Every
 // thread calls it; its barriers are log2(P) (log2(P) + 1) / 2 + 1, a function of n.  Returns whether one of THIS
@@ -321,7 +350,9 @@ __device__ __forceinline__ int grid_lds_lower_bound(const unsigned long long* sh
 // different shapes there and here, so the statements are written again rather than shared), the neighbour's old_v
 // from sh_v, ids ensemble-global.  by_plane: rows 0 - 2 and rows 3 - 8 each summed from +0, then added
 // (grid_force_bits_tile's whole-tile arithmetic).  No barrier in here.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+// HAS_GEN: the right-hand sides hold a start the forces are added to (the ordered link forces, ensemble_links.cuh),
+// written by the thread that owns the ROW, not the slot: the caller's barrier lies in between (grid_lds_order's).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool HAS_GEN = false>
 __device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
     Pt* sh_rhs, const unsigned long long* sh_key, const int gs, const int n_cubes, const float cut2, const bool by_plane)
 {
@@ -369,7 +400,7 @@ __device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, co
             sum_v.x = own[NF] + sum_v.x, sum_v.y = own[NF + 1] + sum_v.y, sum_v.z = own[NF + 2] + sum_v.z;
             sum_friction = own[NF + 3] + sum_friction;
         }
-        store_rhs(sh_rhs, local, false, F, sum_v, sum_friction);
+        store_rhs(sh_rhs, local, HAS_GEN, F, sum_v, sum_friction);
     }
 }
 
@@ -382,15 +413,19 @@ __device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, co
 // YA_STATUS_OUT_OF_GRID in d_status[r] if a cell of any stage lay outside the grid (one atomic).  A replica with
 // n_r <= 0 gets the empty grid (offs all 0) and nothing else.  Nothing else is written: not the unused rows, not
 // d_n, not the right-hand-side arrays, not the build's private arrays (d_count stays zeroed for the next take_step).
-// Every barrier is reached by all 256 threads; the trip counts around them depend on n_r and n_steps only.
-// Not here: several lanes per cell (lanes_per_cell plays no part), Replica_links, the Gabriel form, the fast tier,
-// graph capture.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,
+// Every barrier is reached by all 256 threads; the trip counts around them depend on n_r and n_steps only (LINKED:
+// and on the replica's slots in use, which every thread reads alike).
+// LINKED (grid_lds_steps_linked below): once per launch the workgroup builds the replica's incidence list behind the
+// keys (whole_links_build, its scan scratch the fold's, as in whole_steps_of_a_replica); every stage starts with the
+// ordered link forces of its positions as the right-hand sides (whole_stage_links), the order's barriers follow, and
+// the walk adds the stage's forces to them.  Links do not change during a launch.
+// Not here: several lanes per cell (lanes_per_cell plays no part), the Gabriel form, the fast tier, graph capture.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
+__device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
-    int* __restrict__ d_status)
+    int* __restrict__ d_status, const Links_view links = Links_view{})
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char grid_step_lds[];
     const int replica = blockIdx.x;
@@ -401,12 +436,23 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, 
         return;
     }
     unsigned long long* sh_key = reinterpret_cast<unsigned long long*>(grid_step_lds + grid_lds_keys_base<Pt>(n_max));
+    int* sh_off = nullptr;       // the incidence list: n_max + 1 offsets,
+    unsigned* sh_ent = nullptr;  // at most 2 slots_per_replica entries
+    if constexpr (LINKED) {
+        sh_off = reinterpret_cast<int*>(grid_step_lds + grid_lds_links_base<Pt>(n_max));
+        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
+        // (its scratch is the fold's, behind the step's arrays)
+        whole_links_build(links, replica, n, n_max, sh_off, sh_ent,
+            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max));
+    }
     const int id_base = replica * n_max;
     bool outside = false;
     whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
         [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
+            if constexpr (LINKED) whole_stage_links<Pt>(n, sh_in, sh_rhs, sh_off, sh_ent, links.strength);
             outside |= grid_lds_order<Pt>(n, sh_in, cs, gs, n_cubes, sh_key);
-            grid_lds_walk<Pt, pw_int, pw_friction>(n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane);
+            grid_lds_walk<Pt, pw_int, pw_friction, LINKED>(
+                n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane);
         });
     // (the keys are the last stage's: its walk was followed by barriers, and nothing has written them since)
     const size_t base = (size_t)replica * n_max;
@@ -416,7 +462,45 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, 
         d_point_id_all[base + s] = (int)(unsigned)key;
     }
     for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = grid_lds_lower_bound(sh_key, n, c);
-    if (__syncthreads_or(outside) && threadIdx.x == 0) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
+    if constexpr (LINKED) {
+        // The threads' flags meet in the fold's scratch, which nothing uses after the last step: __syncthreads_or costs
+        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list that grid_lds_links_bytes admits may leave none.
+        int* sh_flag =
+            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max);
+        if (threadIdx.x == 0) *sh_flag = 0;
+        __syncthreads();
+        if (outside) *sh_flag = 1;  // (every writer writes the same value)
+        __syncthreads();
+        if (threadIdx.x == 0 && *sh_flag) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
+    } else {
+        if (__syncthreads_or(outside) && threadIdx.x == 0) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
+    }
+}
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,
+    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
+    const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
+    int* __restrict__ d_status)
+{
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, false>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+        d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status);
+}
+// The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage: bit for
+// bit n_steps of the 14-launch take_step with ya::ens::link_forces_ordered as its generic force.  Dynamic LDS of
+// grid_lds_links_bytes<Pt>(n_max, links.slots_per_replica) > 0.  Besides what grid_lds_steps reads, the replica's
+// slots of links.d_link and *links.d_n are read, at the start of the launch; what it writes is what grid_lds_steps
+// writes.  No atomics but the status bit, no scratch, no cooperative launch.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked(const int n_max, const int* __restrict__ d_n,
+    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
+    const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
+    int* __restrict__ d_status, const Links_view links)
+{
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, true>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+        d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status,
+        links);
 }
 
 // Whether these launches beat the 14-launch step when the model leaves the choice to the engine
@@ -579,8 +663,9 @@ public:
 
     // take_steps as launches that step from LDS (ya::ens::grid_lds_steps: one workgroup per replica): -1 = never,
     // 1 = whenever the call is eligible, 0 (default) = the engine's choice, eligible and
-    // ya::ens::lds_steps_pay(n_replicas, n_max, n_cubes).  Eligible: no generic forces and
-    // n_max <= ya::ens::grid_lds_capacity<Pt>().  Any choice gives the same bits.
+    // ya::ens::lds_steps_pay(n_replicas, n_max, n_cubes).  Eligible: n_max <= ya::ens::grid_lds_capacity<Pt>() and
+    // either no generic forces, or ya::ens::Replica_links whose incidence list fits
+    // (ya::ens::grid_lds_links_bytes<Pt>(n_max, slots_per_replica) != 0).  Any choice gives the same bits.
     int lds_steps = 0;
     // Such a launch runs at most this many steps (no single kernel runs unboundedly long); take_steps splits longer
     // requests.
@@ -607,15 +692,62 @@ public:
     {
         const int n_max = this->n_max;
         const bool eligible = ya::is_no_gen_forces<Pt>(gen_forces) && n_max <= ya::ens::grid_lds_capacity<Pt>();
-        const bool from_lds = eligible && (lds_steps > 0 || (lds_steps == 0 && ya::ens::lds_steps_pay(
-                                                                                  this->n_replicas, n_max, this->n_cubes)));
-        if (!from_lds) {
+        if (!from_lds(eligible)) {
             for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
             return;
         }
+        launch_lds_steps<pw_int, pw_friction>(ya::ens::grid_lds_bytes<Pt>(n_max), dt, n_steps);
+    }
+
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, links);
+    }
+    // n_steps Heun steps of every replica with the ORDERED link forces of `links` as the generic force
+    // (ensemble_links.cuh's contract; this file's header).  Bit for bit n_steps calls of take_step(dt, gen) where gen
+    // calls ya::ens::link_forces_ordered, and that loop unless the call steps from LDS: as launches of
+    // ya::ens::grid_lds_steps_linked where lds_steps allows it, n_max <= ya::ens::grid_lds_capacity<Pt>() and the
+    // incidence list fits the workgroup's LDS beside the keys (ya::ens::grid_lds_links_bytes<Pt>(n_max,
+    // slots_per_replica) != 0).  A launch reads the links and their count at its start: what a model's kernel left
+    // there before the call is what the call sees.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
+    {
+        const int n_max = this->n_max, slots = links.slots_per_replica;
+        assert(slots >= 0 && (size_t)this->n_replicas * (size_t)slots <= (size_t)links.links.n_max);
+        const size_t lds = ya::ens::grid_lds_links_bytes<Pt>(n_max, slots);
+        if (!from_lds(n_max <= ya::ens::grid_lds_capacity<Pt>() && lds != 0)) {
+            const int* d_n = this->d_n;
+            Links* l = &links.links;
+            Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
+                ya::ens::link_forces_ordered<Pt>(ya::ens::Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
+            };
+            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
+            return;
+        }
+        launch_lds_steps<pw_int, pw_friction>(lds, dt, n_steps, ya::ens::view_of(links));
+    }
+
+protected:
+    // whether an eligible take_steps call steps from LDS (lds_steps)
+    bool from_lds(const bool eligible) const
+    {
+        return eligible && (lds_steps > 0 || (lds_steps == 0 && ya::ens::lds_steps_pay(
+                                                                    this->n_replicas, this->n_max, this->n_cubes)));
+    }
+    // n_steps steps as launches of at most lds_steps_max steps each with `lds` bytes of dynamic LDS: of grid_lds_steps,
+    // or of grid_lds_steps_linked with its Links_view as `more`.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename... More>
+    void launch_lds_steps(const size_t lds, const float dt, const int n_steps, const More... more)
+    {
         assert(lds_steps_max >= 1);
-        const auto kernel = &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction>;
-        const size_t lds = ya::ens::grid_lds_bytes<Pt>(n_max);
+        const auto kernel = [] {
+            if constexpr (sizeof...(More) == 0)
+                return &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction>;
+            else
+                return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction>;
+        }();
         // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
         static size_t lds_allowed = 64 * 1024;
         if (lds > lds_allowed) {
@@ -626,10 +758,10 @@ public:
         const float cut2 = ya::cutoff_squared(this->cube_size);
         for (int done = 0; done < n_steps;) {
             const int k = n_steps - done < lds_steps_max ? n_steps - done : lds_steps_max;
-            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(n_max, this->d_n, dt, k,
+            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k,
                 this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v, this->cube_size,
                 this->grid_size, this->n_cubes, cut2, sum_order == YA_SUM_BY_PLANE, this->d_cube_id, this->d_point_id,
-                this->d_offs, this->d_status);
+                this->d_offs, this->d_status, more...);
             lds_step_launches++;
             done += k;
         }
@@ -637,7 +769,6 @@ public:
         this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
     }
 
-protected:
     // Five launches: the grid of every replica from d_in, then the forces.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void forces(const Pt* d_in, Pt* d_rhs, const bool has_gen)

@@ -1,4 +1,5 @@
-// Ordered link forces for Ensemble<Pt, Tile_solver> (and, as a generic force, for the grid and Gabriel forms).
+// Ordered link forces for Ensemble<Pt, Tile_solver> and Ensemble<Pt, Grid_solver> (ensemble_grid.cuh: inside its
+// launches that step from LDS too) and, as a generic force, for the Gabriel form.
 // Part of ensemble.cuh, which includes it between the whole-step pieces it builds on and the whole-step kernels
 // that use it; a model includes ensemble.cuh.
 //

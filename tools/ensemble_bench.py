@@ -10,6 +10,7 @@
     python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
     python tools/ensemble_bench.py --solver grid --lds-steps [--out profiles/ensemble_grid_lds_steps_bench.json]
     python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
+    python tools/ensemble_bench.py --solver grid --links [--out profiles/ensemble_grid_links_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -51,6 +52,13 @@ ordered forces, the baseline), the ordered forces on the six-launch step (link_f
 forces inside whole-step launches of one step each (a model that renews its links every step) and of up to 256 steps
 each.  M in {1, 16, 64, 256, 1024, 4096} x n in {32, 100, 256, 1024} with M * n^2 <= 2^28.  ratio_* = the setting's
 rate over the baseline's.
+
+--solver grid --links: ONE LinkedGridEnsemble("relu_links", M, n, S = 2 n, grid_size fitted to the ball) per shape
+(every cell holds two links to random other cells of its replica), under the protocol of --lds-steps, three settings
+alternating: the ordered forces on the 14-launch step (lds_steps -1: link_forces_ordered and a memset per stage, the
+baseline) and inside launches that step from LDS of one step each (lds_steps 1, lds_steps_max 1: a model that renews
+its links every step) and of up to 256 steps each.  M in {16, 256, 1024, 4096} x n in {100, 256, 512, 1024}.
+ratio_* = the setting's rate over the baseline's.  A record, not a gate.
 """
 import argparse
 import json
@@ -63,7 +71,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from yalla_amd.ensemble import Ensemble, GabrielEnsemble, GridEnsemble, LinkedEnsemble  # noqa: E402
+from yalla_amd.ensemble import (Ensemble, GabrielEnsemble, GridEnsemble, LinkedEnsemble,  # noqa: E402
+                                LinkedGridEnsemble)
 from yalla_amd.solution import Solution  # noqa: E402
 
 SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
@@ -81,6 +90,10 @@ LINKS_SHAPES = [(m, n) for n in (32, 100, 256, 1024) for m in (1, 16, 64, 256, 1
 # (links_path, whole_steps, steps_per_launch)
 LINKS_SETTINGS = {"atomics_six_launches": (1, -1, 256), "ordered_six_launches": (0, -1, 256),
                   "ordered_whole_1_step_per_launch": (0, 1, 1), "ordered_whole_256_steps_per_launch": (0, 1, 256)}
+# --solver grid --links: one LinkedGridEnsemble("relu_links", M, n, 2 n), (lds_steps, lds_steps_max)
+GRID_LINKS_SHAPES = [(m, n) for n in (100, 256, 512, 1024) for m in (16, 256, 1024, 4096)]
+GRID_LINKS_SETTINGS = {"ordered_fourteen_launches": (-1, 256), "ordered_lds_1_step_per_launch": (1, 1),
+                       "ordered_lds_256_steps_per_launch": (1, 256)}
 GABRIEL_SHAPES = [(m, n) for n in (100, 500, 2000, 10000) for m in (1, 8, 64, 512) if m * n <= 5000000]
 GABRIEL_LANES = (0,)  # (no lanes setting: one column)
 DT = 0.01
@@ -172,6 +185,33 @@ class Linked:
         self.ens.set_param("links_path", links_path)
         self.ens.set_param("whole_steps", whole_steps)
         self.ens.set_param("steps_per_launch", steps_per_launch)
+
+    def steps(self, k):
+        self.ens.take_step(DT, k)
+        self.ens.synchronize()
+
+    def close(self):
+        self.ens.close()
+
+
+class LinkedGrid:
+    """One LinkedGridEnsemble("relu_links", m, n, 2 n, grid_size fitted): cell i of every replica linked to two random
+    other cells of it."""
+
+    def __init__(self, m, n):
+        self.ens = LinkedGridEnsemble("relu_links", m, n, 2 * n, grid_size=grid_size_for(n))
+        rng = np.random.default_rng(m * 10007 + n)
+        for r in range(m):
+            self.ens.h_X[r] = ball(n, r)
+        a = np.broadcast_to(np.repeat(np.arange(n), 2), (m, 2 * n))
+        b = (a + 1 + rng.integers(0, n - 1, (m, 2 * n))) % n
+        self.ens.h_link[:] = np.stack([a, b], axis=2) + (np.arange(m) * n)[:, None, None]
+        self.ens.n_links = m * 2 * n
+        self.ens.copy_to_device()
+
+    def setting(self, lds_steps, lds_steps_max):
+        self.ens.set_param("lds_steps", lds_steps)
+        self.ens.set_param("lds_steps_max", lds_steps_max)
 
     def steps(self, k):
         self.ens.take_step(DT, k)
@@ -371,6 +411,62 @@ def main_links(args):
                       "max_ratio_whole_256": max(r["ratio_ordered_whole_256_steps_per_launch"] for r in rows)}))
 
 
+def measure_grid_links(m, n, window, repeats):
+    b = LinkedGrid(m, n)
+    try:
+        ks = {}
+        for key, setting in GRID_LINKS_SETTINGS.items():
+            b.setting(*setting)
+            b.steps(3)
+            ks[key] = calibrate(b, window)
+        samples = {key: [] for key in ks}
+        for _ in range(repeats):  # fourteen, lds 1, lds 256, fourteen, ...
+            for key, setting in GRID_LINKS_SETTINGS.items():
+                b.setting(*setting)
+                samples[key].append(timed(b, ks[key]))
+        launches = b.ens.lds_step_launches
+    finally:
+        b.close()
+    row = {"n_replicas": m, "n": n, "slots_per_replica": 2 * n, "grid_size": grid_size_for(n), "lds_step_launches": launches}
+    for key in GRID_LINKS_SETTINGS:
+        row[key] = summary(samples[key], m * n, ks[key])
+    baseline = list(GRID_LINKS_SETTINGS)[0]
+    for key in list(GRID_LINKS_SETTINGS)[1:]:
+        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row[baseline]["cell_updates_per_s"]
+    row["spread"] = max(row[key]["spread"] for key in GRID_LINKS_SETTINGS)  # of the worst side
+    return row
+
+
+def main_grid_links(args):
+    """--solver grid --links: linked launches that step from LDS against the 14-launch step of the same ensemble."""
+    shapes = GRID_LINKS_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting
+        run = LinkedGrid(m, n)
+        for setting in GRID_LINKS_SETTINGS.values():
+            run.setting(*setting)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n in shapes:
+        rows.append(measure_grid_links(m, n, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:9.1f}" for key in GRID_LINKS_SETTINGS)
+              + " us/step   ratios " + " ".join(f"{r['ratio_' + key]:.2f}" for key in list(GRID_LINKS_SETTINGS)[1:])
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --solver grid --links", "model": "relu_links", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows),
+                      "min_ratio_lds_1": min(r["ratio_ordered_lds_1_step_per_launch"] for r in rows),
+                      "max_ratio_lds_1": max(r["ratio_ordered_lds_1_step_per_launch"] for r in rows),
+                      "min_ratio_lds_256": min(r["ratio_ordered_lds_256_steps_per_launch"] for r in rows),
+                      "max_ratio_lds_256": max(r["ratio_ordered_lds_256_steps_per_launch"] for r in rows)}))
+
+
 def measure_whole_lanes(m, n, lanes_list, window, repeats):
     b = Together(m, n)
     try:
@@ -440,7 +536,8 @@ def main():
     ap.add_argument("--whole-step-lanes", default=None, metavar="L,L,...",
                     help="with --whole-steps: these whole_step_lanes settings against lanes 1 of the same Ensemble")
     ap.add_argument("--links", action="store_true",
-                    help="ordered link forces (six launches, whole steps) against link_forces with atomics")
+                    help="ordered link forces (six launches, whole steps) against link_forces with atomics; with "
+                         "--solver grid: ordered link forces from LDS against the 14-launch step of the same ensemble")
     ap.add_argument("--lds-steps", action="store_true",
                     help="with --solver grid: launches that step from LDS against the 14-launch step of the same ensemble")
     args = ap.parse_args()
@@ -452,9 +549,13 @@ def main():
         main_lds(args)
         return
     if args.links:
-        if args.solver != "tile" or args.trace_shape or args.whole_steps:
-            ap.error("--links measures the linked all-pairs ensemble on its own")
-        main_links(args)
+        if args.solver == "gabriel" or args.trace_shape or args.whole_steps:
+            ap.error("--links measures the linked all-pairs ensemble, or with --solver grid the linked grid ensemble, on its own")
+        if args.solver == "grid":
+            GRID = True
+            main_grid_links(args)
+        else:
+            main_links(args)
         return
     if args.whole_step_lanes and not args.whole_steps:
         ap.error("--whole-step-lanes goes with --whole-steps")

@@ -18,6 +18,7 @@ ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ense
 GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid.so")  # include/yalla_ensemble_grid.h
 GABRIEL_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel.so")  # include/yalla_ensemble_gabriel.h
 LINKED_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_links.so")  # include/yalla_ensemble_links.h
+LINKED_GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid_links.so")  # include/yalla_ensemble_grid_links.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -119,6 +120,17 @@ LINKED_ENSEMBLE_ABI["ya_lens_get_n_links"] = (C.c_int, [_ens])
 LINKED_ENSEMBLE_ABI["ya_lens_whole_step_lanes_used"] = (C.c_int, [_ens])
 LINKED_ENSEMBLE_ABI["ya_lens_lds_bytes"] = (C.c_long, [C.c_char_p, C.c_int, C.c_int, C.c_int])
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_grid_links.h one to one: the grid ensemble's functions
+# under another prefix, create with the slots per replica and the links' strength as well, the links' host mirror
+# and count, and the LDS rule.
+LINKED_GRID_ENSEMBLE_ABI = {name.replace("ya_gens_", "ya_glens_"): sig for name, sig in GRID_ENSEMBLE_ABI.items()}
+LINKED_GRID_ENSEMBLE_ABI["ya_glens_create"] = (
+    C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(_ens)])
+LINKED_GRID_ENSEMBLE_ABI["ya_glens_h_link"] = (_pi, [_ens])
+LINKED_GRID_ENSEMBLE_ABI["ya_glens_set_n_links"] = (C.c_int, [_ens, C.c_int])
+LINKED_GRID_ENSEMBLE_ABI["ya_glens_get_n_links"] = (C.c_int, [_ens])
+LINKED_GRID_ENSEMBLE_ABI["ya_glens_lds_bytes"] = (C.c_long, [C.c_char_p, C.c_int, C.c_int])
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -201,3 +213,11 @@ def linked_ensemble_lib():
     """The linked ensemble harness, yalla_amd/libyalla_ensemble_links.so (include/yalla_ensemble_links.h), every
     entry point typed.  Raises if it has not been built: there is no fallback."""
     return _load(LINKED_ENSEMBLE_LIB, LINKED_ENSEMBLE_ABI)
+
+
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
+def linked_grid_ensemble_lib():
+    """The linked grid ensemble harness, yalla_amd/libyalla_ensemble_grid_links.so
+    (include/yalla_ensemble_grid_links.h), every entry point typed.  Raises if it has not been built: there is no
+    fallback."""
+    return _load(LINKED_GRID_ENSEMBLE_LIB, LINKED_GRID_ENSEMBLE_ABI)

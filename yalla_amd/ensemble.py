@@ -26,7 +26,8 @@ largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
 build per stage (or whole steps from LDS, `lds_steps`); `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh);
-`LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh).
+`LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh);
+`LinkedGridEnsemble` the same for M Grid_solver systems, inside launches that step from LDS too.
 """
 import ctypes as C
 
@@ -332,6 +333,57 @@ class LinkedEnsemble(Ensemble):
         if code < 0:
             raise YallaError(f"ya_lens_lds_bytes({model!r}, {n_max}, {slots_per_replica}, {lanes}) failed with {code}")
         return code
+
+
+class LinkedGridEnsemble(GridEnsemble):
+    """Host-side mirror of `Ensemble<Pt, Grid_solver>` stepped with `ya::ens::Replica_links` (include/ensemble_grid.cuh,
+    include/ensemble_links.cuh) over include/yalla_ensemble_grid_links.h: M Grid_solver systems of one model, each with
+    `slots_per_replica` link slots of one `Links` object over the flat id space.  Everything `GridEnsemble` offers but
+    set_param("lanes", ...), and what `LinkedEnsemble` adds: `h_link` (an `(n_replicas, slots_per_replica, 2)` int32
+    view of ENSEMBLE-GLOBAL ids), `n_links` (the used-slot count), `copy_to_device()` hands both over,
+    set_param("links_path", 0 | 1).  A cell's link terms are added in ascending slot order; a slot with a == b is inert,
+    one with an end outside its own replica's rows is skipped.  `set_param("lds_steps", 1)` runs the steps as launches
+    of one workgroup per replica that step from LDS (ya::ens::grid_lds_steps_linked) where n_max <= 1024 and the
+    incidence list fits beside the keys (`LinkedGridEnsemble.lds_bytes(...) > 0`): the same bits, grid arrays and
+    status included; `lds_step_launches` counts the launches made.
+
+        with LinkedGridEnsemble("relu_links", 64, 200, slots_per_replica=400, grid_size=12) as cells:
+            cells.h_link[r, s] = (r * 200 + a, r * 200 + b); cells.copy_to_device()
+            cells.set_param("lds_steps", 1); cells.take_step(0.05, 100)
+    """
+    _PREFIX, _LOADER, _NOUN = "ya_glens_", "linked_grid_ensemble_lib", "linked grid ensemble"
+
+    def __init__(self, model, n_replicas, n_max, slots_per_replica, strength=0.2, grid_size=50, cube_size=1.0, lib=None):
+        self._create(lib, model, n_replicas, n_max, int(grid_size), C.c_float(cube_size), int(slots_per_replica),
+                     C.c_float(strength))
+        self.grid_size = int(grid_size)
+        self.slots_per_replica = int(slots_per_replica)
+        self.strength = float(strength)
+        shape = (self.n_replicas, self.slots_per_replica, 2)
+        if self.n_replicas * self.slots_per_replica > 0:
+            self.h_link = np.ctypeslib.as_array(self._f("h_link")(self._h), shape=shape)
+        else:
+            self.h_link = np.zeros(shape, np.int32)
+
+    def close(self):
+        self.h_link = None
+        super().close()
+
+    n_links = LinkedEnsemble.n_links
+
+    @staticmethod
+    def lds_bytes(model, n_max, slots_per_replica, lib=None):
+        """ya::ens::grid_lds_links_bytes for the model's point type: the dynamic LDS of a linked launch that steps
+        from LDS, 0 where there is no room.  Needs no GPU."""
+        lib = lib if lib is not None else _ffi.linked_grid_ensemble_lib()
+        code = lib.ya_glens_lds_bytes(model.encode(), int(n_max), int(slots_per_replica))
+        if code < 0:
+            raise YallaError(f"ya_glens_lds_bytes({model!r}, {n_max}, {slots_per_replica}) failed with {code}")
+        return code
+
+
+def linked_grid_models(lib=None):
+    return _models(lib if lib is not None else _ffi.linked_grid_ensemble_lib(), "ya_glens_")
 
 
 def _models(lib, prefix):
