@@ -27,7 +27,10 @@
 // lds_steps_max steps: a workgroup per replica sorts the replica's (cube, id) keys in LDS, finds the stencil rows by
 // searching that order and steps from LDS (ya::ens::grid_lds_steps) -- no counters, nothing of size grid_size^3 touched
 // in between.  The step itself is ya::ens::whole_steps_in_lds (ensemble.cuh), which the all-pairs whole steps call too.
-// Not built for these launches: several lanes per cell, the Gabriel form, the fast tier, graph capture.
+// SEVERAL LANES PER CELL  Inside such a launch `lds_step_lanes` = 4, 16 or 64 lanes share a cell's candidates
+// (ya::ens::grid_lds_walk_coop: terms into an LDS buffer behind the keys, one lane per component adds them in the walk's
+// order), for replicas of a few dozen cells, which leave most of the workgroup idle otherwise: the same bits.
+// Not built for these launches: the Gabriel form, the fast tier, graph capture.
 //
 // LINKS  cells.take_steps<my_force>(dt, K, ya::ens::Replica_links{links, S}) steps with the ORDERED link forces of a
 // Links object over the flat id space (ensemble_links.cuh: slot s belongs to replica s / S, a == b is inert, slots
@@ -36,9 +39,9 @@
 // as K calls of take_step(dt, gen) with gen calling ya::ens::link_forces_ordered<Pt>; where the replica and its
 // incidence list fit one workgroup's LDS (ya::ens::grid_lds_links_bytes<Pt>(n_max, S) != 0) and `lds_steps` allows
 // it, the call runs as launches that step from LDS (ya::ens::grid_lds_steps_linked), bit for bit alike, the public
-// grid arrays and d_status included.  Out of scope for these linked launches: the Gabriel form, several lanes per
-// cell in LDS-step launches, the fast tier, graph capture, links that change inside a launch (a launch reads the
-// links and their count at its start).
+// grid arrays and d_status included, with lds_step_lanes lanes per cell where the term buffer fits behind the list.
+// Out of scope for these linked launches: the Gabriel form, the fast tier, graph capture, links that change inside a
+// launch (a launch reads the links and their count at its start).
 //
 // COST  Every stage scans n_replicas * grid_size^3 counters (one workgroup per replica walks its cubes) whatever
 // the replicas hold: a sweep picks grid_size to fit its replicas, not the single system's default of 50.
@@ -284,6 +287,56 @@ constexpr size_t grid_lds_links_bytes(const int n_max, const int slots)
     return bytes + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP ? 0 : bytes;
 }
 
+// SEVERAL LANES PER CELL (grid_lds_walk_coop below) need a term buffer: it lies behind what the launch lays out anyway
+// -- the step's arrays and the keys, with links the incidence list too -- 16-byte aligned, and is sized by the all-pairs
+// whole steps' own rule with that start (whole_step_coop_bytes_behind, ensemble.cuh: a tile of candidates, n_max rounded
+// up to a multiple of 4, at most WHOLE_STEP_COOP_MAX_TILE, at most what WHOLE_STEP_COOP_BUDGET holds but no less than
+// WHOLE_STEP_COOP_MIN_TILE, at most what is left beside WHOLE_STEP_STATIC_LDS).  The answer is the launch's dynamic LDS;
+// 0 = no room for WHOLE_STEP_COOP_MIN_TILE candidates' terms: the call steps from LDS with one lane per cell (an
+// 8-float point's 1024 rows leave 896 bytes; a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4).
+// The rule may fill the LDS to the byte, so the kernels of several lanes keep their static LDS at
+// WHOLE_STEP_STATIC_LDS as the linked one does.  No bit depends on the tile length.
+template<typename Pt>
+constexpr size_t grid_lds_coop_base(const int n_max)  // where the term buffer starts
+{
+    return (grid_lds_bytes<Pt>(n_max) + 15) / 16 * 16;
+}
+template<typename Pt>
+constexpr size_t grid_lds_coop_bytes(const int n_max, const int lanes)
+{
+    return whole_step_coop_bytes_behind<Pt>(grid_lds_coop_base<Pt>(n_max), n_max, lanes);
+}
+template<typename Pt>
+constexpr size_t grid_lds_links_coop_base(const int n_max, const int slots)
+{
+    return (grid_lds_links_base<Pt>(n_max) + whole_step_links_list_bytes(n_max, slots) + 15) / 16 * 16;
+}
+template<typename Pt>
+constexpr size_t grid_lds_links_coop_bytes(const int n_max, const int slots, const int lanes)
+{
+    if (grid_lds_links_bytes<Pt>(n_max, slots) == 0) return 0;
+    const size_t base = grid_lds_links_coop_base<Pt>(n_max, slots);
+    if (base + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP) return 0;
+    return whole_step_coop_bytes_behind<Pt>(base, n_max, lanes);
+}
+// the tile length of that rule, in candidates, for a term buffer that starts at `base` and ends at `bytes`; 0 = no room
+template<typename Pt>
+constexpr int grid_lds_coop_tile_of(const size_t base, const size_t bytes, const int lanes)
+{
+    return bytes == 0 ? 0 : (int)((bytes - base) / whole_step_coop_bytes_per_partner<Pt>(lanes));
+}
+template<typename Pt>
+constexpr int grid_lds_coop_tile(const int n_max, const int lanes)
+{
+    return grid_lds_coop_tile_of<Pt>(grid_lds_coop_base<Pt>(n_max), grid_lds_coop_bytes<Pt>(n_max, lanes), lanes);
+}
+template<typename Pt>
+constexpr int grid_lds_links_coop_tile(const int n_max, const int slots, const int lanes)
+{
+    return grid_lds_coop_tile_of<Pt>(
+        grid_lds_links_coop_base<Pt>(n_max, slots), grid_lds_links_coop_bytes<Pt>(n_max, slots, lanes), lanes);
+}
+
 // The replica's cube ids (ya::cube_id_of, clamped as grid_count_batched clamps it) and THE ORDER: sh_key[0 .. n)
 // ascending in (cube, id), by a bitonic sort of P = the power of two from n up keys (the padding sorts last).  Every
 // thread calls it; its barriers are log2(P) (log2(P) + 1) / 2 + 1, a function of n.  Returns whether one of THIS
@@ -404,6 +457,211 @@ __device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, co
     }
 }
 
+// A cell's lanes meet in the term buffer without a workgroup barrier: LANES <= 64 lanes of consecutive threads lie in
+// ONE wavefront, whose LDS accesses complete in program order; the fences keep the compiler from moving an access
+// across the point where another lane's access is meant to lie.
+__device__ __forceinline__ void grid_lds_lanes_meet()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One candidate's NF + 4 terms {F (NF), friction, friction * old_v (3)}, handed to store(c, term): grid_lds_walk's
+// pair statements with each `sum += term` left to phase (b).  The default friction's coefficient is 0 or 1, so its
+// products are exact and `sum + f * v` is ya::pair_friction's `fmaf(f, v, sum)`, bit for bit, a non-finite old_v
+// included; any other friction adds its old_v terms only where it is not zero, as pair_friction does: a +0 term there
+// (see grid_lds_walk_coop on +0 terms).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Store>
+__device__ __forceinline__ void grid_lds_pair_terms(const Pt Xi, const Pt Xj, const float3 vj, const int i, const int j,
+    const Store& store)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    Pt r = Xi - Xj;
+    float dist = dist3(r.x, r.y, r.z);
+    Pt f = ya::zero<Pt>();
+    YA_CALL_INLINED f = pw_int(Xi, r, dist, i, j);
+#pragma unroll
+    for (int c = 0; c < NF; c++) store(c, field(f, c));
+    if constexpr (pw_friction == &friction_w_neighbour<Pt>) {
+        const bool nb = (i != j) & (dist < 1.f);
+        const float friction = nb ? 1.f : 0.f;
+        store(NF, friction);
+        store(NF + 1, friction * vj.x);
+        store(NF + 2, friction * vj.y);
+        store(NF + 3, friction * vj.z);
+    } else {
+        const float friction = pw_friction(Xi, r, dist, i, j);
+        store(NF, friction);
+        store(NF + 1, friction != 0 ? friction * vj.x : 0.f);
+        store(NF + 2, friction != 0 ? friction * vj.y : 0.f);
+        store(NF + 3, friction != 0 ? friction * vj.z : 0.f);
+    }
+}
+
+// Phase (b) of grid_lds_walk_coop: sum + terms[0] + terms[1] + ... + terms[n_terms - 1], added one after the other in
+// that order, for ONE component of a cell's term buffer: `column` is the component's float4 of the first group of four
+// candidates, the next group's lies STRIDE float4 further.  Sixteen terms per trip: four 16-byte LDS reads in flight,
+// then the adds in order.
+template<int STRIDE>
+__device__ __forceinline__ float grid_lds_ordered_sum(float sum, const float4* column, const int n_terms)
+{
+    int g = 0;
+    for (; 4 * (g + 4) <= n_terms; g += 4) {
+        float4 p[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) p[u] = column[(g + u) * STRIDE];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            sum += p[u].x;
+            sum += p[u].y;
+            sum += p[u].z;
+            sum += p[u].w;
+        }
+    }
+    for (; 4 * (g + 1) <= n_terms; g++) {
+        const float4 p = column[g * STRIDE];
+        sum += p.x;
+        sum += p.y;
+        sum += p.z;
+        sum += p.w;
+    }
+    const int rest = n_terms - 4 * g;  // (the group is laid out whole: the tile length is a multiple of 4)
+    if (rest > 0) {
+        const float4 p = column[g * STRIDE];
+        sum += p.x;
+        if (rest > 1) sum += p.y;
+        if (rest > 2) sum += p.z;
+    }
+    return sum;
+}
+
+// grid_lds_walk for functors that keep no per-cell state: LANES (4, 16 or 64) lanes per cell, the same bits.  The
+// workgroup serves 256 / LANES sorted slots per round, ceil(n / cells) rounds.  Per round:
+//   bounds   the cell's 18 row bounds are dealt to its lanes (search q = row + 9 * (is it the end) goes to lane
+//            q % LANES: with 16 or 64 lanes they are one parallel step) and handed round by wavefront shuffles; every
+//            lane then holds, per row, its first slot and the number of candidates in the rows before it.  THE WALK'S
+//            ORDER is the candidates numbered q = 0 .. T - 1 through rows 0 .. 8 ascending, slots ascending in a row.
+//   (a)      per tile of `tile` candidates (the term buffer: sh_part, [cell][group of four candidates][component][4],
+//            so that no address depends on the tile length and a component's four terms are one 16-byte read), lane l
+//            evaluates candidates l, l + LANES, ... of the tile: key -> position -> test, and for a hit (dist2 < cut2,
+//            i == j included, ids ensemble-global, old_v from sh_v) the pair's terms by grid_lds_pair_terms.
+//            A MISS IS RECORDED AS +0 IN EVERY COMPONENT, not compacted away: every running sum of (b) starts at +0
+//            and receives IEEE round-to-nearest additions only, and x + y is -0 only where x and y both are, so a
+//            running sum never is -0 and adding +0 to it changes no bit (tile_force_coop's argument for its masked
+//            friction products).
+//   (b)      one lane per component (components lane, lane + LANES, ...) adds the tile's terms in ascending q to a
+//            sum that started at +0 and is carried across tiles: no bit depends on `tile`.
+// by_plane: candidates [0, cum[3]) -- rows 0 - 2 -- and the rest are two such walks, each summed from +0, then added
+// as own + rest (grid_lds_walk's arithmetic, empty parts included).
+// Then the sums travel to the cell's first lane by shuffles, and it writes the right-hand side (HAS_GEN: adds to what
+// the row's owner left there; the caller's barrier -- grid_lds_order's -- lies in between).
+// NO WORKGROUP BARRIER IN HERE: a cell's lanes lie in one wavefront (grid_lds_lanes_meet), so the trip counts of a
+// cell's tiles concern that cell's lanes alone, a cube of 300 cells beside isolated ones included.  Every thread calls
+// it; the caller's barrier follows.  No atomics, no cooperative launch; the bounds and the running sums live in
+// registers indexed by unrolled loops (no scratch).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool HAS_GEN = false>
+__device__ __forceinline__ void grid_lds_walk_coop(const int n, const int id_base, const Pt* sh_in, const float3* sh_v,
+    Pt* sh_rhs, const unsigned long long* sh_key, const int gs, const int n_cubes, const float cut2, const bool by_plane,
+    float* sh_part, const int tile)
+{
+    static_assert(LANES == 4 || LANES == 16 || LANES == 64, "4, 16 or 64 lanes per cell");
+    constexpr int CELLS = UPDATE_BLOCK / LANES;
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int NC = NF + 4;
+    constexpr int SLOTS = (NC + LANES - 1) / LANES;   // components per lane
+    constexpr int SEARCHES = (18 + LANES - 1) / LANES;  // bounds per lane
+    const int cell = threadIdx.x / LANES, lane = threadIdx.x % LANES;
+    float* const my_terms = sh_part + (size_t)cell * NC * tile;  // this cell's [group][component][4] terms
+    for (int first = 0; first < n; first += CELLS) {
+        const int s = first + cell;
+        const bool active = s < n;
+        // (the lanes of a cell past n search too, for the replica's last slot: every lane takes part in the shuffles)
+        const unsigned long long mine = sh_key[active ? s : n - 1];
+        const int c = (int)(mine >> 32), local = (int)(unsigned)mine;
+        const int i = id_base + local;
+        int bound[SEARCHES];
+#pragma unroll
+        for (int a = 0; a < SEARCHES; a++) {
+            const int q = lane + LANES * a;
+            bound[a] = 0;
+            if (q < 18) {
+                const int off = stencil_row_offset(q < 9 ? q : q - 9, gs);
+                bound[a] = grid_lds_lower_bound(sh_key, n, min(max(c + off + (q < 9 ? -1 : 2), 0), n_cubes));
+            }
+        }
+        // candidate q of row `row` is slot q + shift[row], cum[row] <= q < cum[row + 1]
+        int shift[9], cum[10];
+        cum[0] = 0;
+#pragma unroll
+        for (int row = 0; row < 9; row++) {
+            const int begin = __shfl(bound[row / LANES], row % LANES, LANES);
+            const int end = __shfl(bound[(9 + row) / LANES], (9 + row) % LANES, LANES);
+            shift[row] = begin - cum[row];
+            cum[row + 1] = cum[row] + (end - begin);
+        }
+        float acc[SLOTS], own[SLOTS];
+#pragma unroll
+        for (int a = 0; a < SLOTS; a++) acc[a] = own[a] = 0.f;
+        if (active) {
+            const Pt Xi = sh_in[local];
+            const int split = by_plane ? cum[3] : 0;
+#pragma unroll 1
+            for (int part = 0; part < 2; part++) {
+                const int q_begin = part == 0 ? 0 : split, q_end = part == 0 ? split : cum[9];
+#pragma unroll 1
+                for (int tile_start = q_begin; tile_start < q_end; tile_start += tile) {
+                    const int n_tile = min(tile, q_end - tile_start);
+                    grid_lds_lanes_meet();  // (the term buffer's readers of the tile before are done)
+#pragma unroll 1
+                    for (int jj = lane; jj < n_tile; jj += LANES) {
+                        const int q = tile_start + jj;
+                        int t = q + shift[0];
+#pragma unroll
+                        for (int row = 1; row < 9; row++) t = q >= cum[row] ? q + shift[row] : t;
+                        const int other = (int)(unsigned)sh_key[t];
+                        const Pt Xj = sh_in[other];
+                        float* const mine_of_the_group = my_terms + (jj >> 2) * (4 * NC) + (jj & 3);
+                        if (dist2(Xi, Xj) < cut2) {
+                            grid_lds_pair_terms<Pt, pw_int, pw_friction>(Xi, Xj, sh_v[other], i, id_base + other,
+                                [&](const int k, const float term) { mine_of_the_group[4 * k] = term; });
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < NC; k++) mine_of_the_group[4 * k] = 0.f;
+                        }
+                    }
+                    grid_lds_lanes_meet();
+#pragma unroll
+                    for (int a = 0; a < SLOTS; a++) {
+                        const int k = lane + LANES * a;
+                        if (k < NC)
+                            acc[a] = grid_lds_ordered_sum<NC>(
+                                acc[a], reinterpret_cast<const float4*>(my_terms) + k, n_tile);
+                    }
+                }
+                if (part == 0 && by_plane) {  // the own plane's sums aside, the other two planes from +0
+#pragma unroll
+                    for (int a = 0; a < SLOTS; a++) own[a] = acc[a], acc[a] = 0.f;
+                }
+            }
+            if (by_plane) {  // S[dz = 0] + S[dz = -1, +1]
+#pragma unroll
+                for (int a = 0; a < SLOTS; a++) acc[a] = own[a] + acc[a];
+            }
+        }
+        // component k is with lane k % LANES; every lane of the wavefront takes part
+        float sum[NC];
+#pragma unroll
+        for (int k = 0; k < NC; k++) sum[k] = __shfl(acc[k / LANES], k % LANES, LANES);
+        if (active && lane == 0) {
+            Pt F;
+#pragma unroll
+            for (int k = 0; k < NF; k++) field(F, k) = sum[k];
+            store_rhs(sh_rhs, local, HAS_GEN, F, float3{sum[NF + 1], sum[NF + 2], sum[NF + 3]}, sum[NF]);
+        }
+    }
+}
+
 // n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS (dynamic LDS of
 // grid_lds_bytes<Pt>(n_max)): ya::ens::whole_steps_in_lds (ensemble.cuh) with a stage's forces = grid_lds_order +
 // grid_lds_walk of the stage's positions.  Bit for bit n_steps of the 14-launch take_step without generic forces.
@@ -419,8 +677,12 @@ __device__ __forceinline__ void grid_lds_walk(const int n, const int id_base, co
 // keys (whole_links_build, its scan scratch the fold's, as in whole_steps_of_a_replica); every stage starts with the
 // ordered link forces of its positions as the right-hand sides (whole_stage_links), the order's barriers follow, and
 // the walk adds the stage's forces to them.  Links do not change during a launch.
-// Not here: several lanes per cell (lanes_per_cell plays no part), the Gabriel form, the fast tier, graph capture.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
+// LANES (4, 16 or 64; Ensemble<Pt, Grid_solver>::lds_step_lanes): the walk is grid_lds_walk_coop, its term buffer
+// behind all that (dynamic LDS of grid_lds_coop_bytes<Pt>(n_max, LANES) > 0, LINKED: grid_lds_links_coop_bytes), the
+// tile length the rule's, read from the same constexpr functions as the host's.  LANES == 1 is the one-lane code as
+// it was.  (lanes_per_cell, the 14-launch step's knob, plays no part.)
+// Not here: the Gabriel form, the fast tier, graph capture.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED, int LANES = 1>
 __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
@@ -445,14 +707,30 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
         whole_links_build(links, replica, n, n_max, sh_off, sh_ent,
             reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max));
     }
+    float* sh_part = nullptr;  // the term buffer of several lanes per cell
+    int tile = 0;
+    if constexpr (LANES > 1) {
+        if constexpr (LINKED) {
+            sh_part = reinterpret_cast<float*>(
+                grid_step_lds + grid_lds_links_coop_base<Pt>(n_max, links.slots_per_replica));
+            tile = grid_lds_links_coop_tile<Pt>(n_max, links.slots_per_replica, LANES);
+        } else {
+            sh_part = reinterpret_cast<float*>(grid_step_lds + grid_lds_coop_base<Pt>(n_max));
+            tile = grid_lds_coop_tile<Pt>(n_max, LANES);
+        }
+    }
     const int id_base = replica * n_max;
     bool outside = false;
     whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
         [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
             if constexpr (LINKED) whole_stage_links<Pt>(n, sh_in, sh_rhs, sh_off, sh_ent, links.strength);
             outside |= grid_lds_order<Pt>(n, sh_in, cs, gs, n_cubes, sh_key);
-            grid_lds_walk<Pt, pw_int, pw_friction, LINKED>(
-                n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane);
+            if constexpr (LANES == 1)
+                grid_lds_walk<Pt, pw_int, pw_friction, LINKED>(
+                    n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane);
+            else
+                grid_lds_walk_coop<Pt, pw_int, pw_friction, LANES, LINKED>(
+                    n, id_base, sh_in, sh_v, sh_rhs, sh_key, gs, n_cubes, cut2, by_plane, sh_part, tile);
         });
     // (the keys are the last stage's: its walk was followed by barriers, and nothing has written them since)
     const size_t base = (size_t)replica * n_max;
@@ -462,9 +740,10 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
         d_point_id_all[base + s] = (int)(unsigned)key;
     }
     for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = grid_lds_lower_bound(sh_key, n, c);
-    if constexpr (LINKED) {
+    if constexpr (LINKED || LANES > 1) {
         // The threads' flags meet in the fold's scratch, which nothing uses after the last step: __syncthreads_or costs
-        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list that grid_lds_links_bytes admits may leave none.
+        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list that grid_lds_links_bytes admits may leave none
+        // (nor may a term buffer that grid_lds_coop_bytes admits).
         int* sh_flag =
             reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max);
         if (threadIdx.x == 0) *sh_flag = 0;
@@ -476,29 +755,29 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
         if (__syncthreads_or(outside) && threadIdx.x == 0) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
     }
 }
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status)
 {
-    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, false>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, false, LANES>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
         d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status);
 }
 // The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage: bit for
 // bit n_steps of the 14-launch take_step with ya::ens::link_forces_ordered as its generic force.  Dynamic LDS of
-// grid_lds_links_bytes<Pt>(n_max, links.slots_per_replica) > 0.  Besides what grid_lds_steps reads, the replica's
+// grid_lds_links_bytes<Pt>(n_max, links.slots_per_replica) > 0 (LANES > 1: grid_lds_links_coop_bytes).  Besides what grid_lds_steps reads, the replica's
 // slots of links.d_link and *links.d_n are read, at the start of the launch; what it writes is what grid_lds_steps
 // writes.  No atomics but the status bit, no scratch, no cooperative launch.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status, const Links_view links)
 {
-    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, true>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, true, LANES>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
         d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status,
         links);
 }
@@ -510,6 +789,24 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked(const int 
 inline bool lds_steps_pay(const int n_replicas, const int n_max, const int n_cubes)
 {
     return n_replicas >= 256;
+}
+
+// Lanes per cell inside these launches when the model leaves the choice to the engine and its functors are stateless
+// (Ensemble<Pt, Grid_solver>::lds_step_lanes == 0).  The derivation is ya::ens::whole_step_lanes_for's -- the largest L
+// of 64, 16, 4 with n_max * L <= 256, else 1: one round serves the whole replica, a lane evaluates ceil(T / L) of a
+// cell's T candidates and runs at most ceil(18 / L) of its searches, and the ordered adds are what they were -- and
+// THE TABLE CORRECTS IT TWICE (profiles/ensemble_grid_lds_lanes_bench.json, MI355X, relu, M = 1 .. 4096; DESIGN.md
+// section 4): at n = 32 two rounds of 16 lanes beat one round of 4 (1.09 - 1.23 x at every M), and at n = 4 16 lanes are
+// as fast as 64 or up to 6 % faster (beyond 16 lanes the 18 searches gain nothing and 7 components leave 57 lanes idle
+// in phase (b)).  So: 16 lanes up to 32 cells, 4 up to 64 (measured at 64: 4 lanes 1.6 - 2.8 x one lane, 16 lanes less),
+// else 1.  Every L > 1 it answers was at least 1.6 x one lane at every measured M, spreads <= 0.13.
+// ABOVE 64 CELLS THE ANSWER (1) IS A PLACEHOLDER: at n = 100 4 lanes are 1.5 x one lane up to M = 256 and 0.82 x from
+// M = 1024 on, at n >= 256 every L > 1 loses; a rule there needs n_replicas, which this one does not take.
+constexpr int grid_lds_lanes_for(const int n_max)
+{
+    if (n_max <= 32) return 16;
+    if (n_max <= 64) return 4;
+    return 1;
 }
 
 
@@ -672,6 +969,15 @@ public:
     int lds_steps_max = 256;
     // such launches made so far (which path ran)
     long lds_step_launches = 0;
+    // Lanes per cell inside such a launch: 0 (default) = the engine's choice -- one lane per cell unless the functors
+    // are declared stateless (YA_STATELESS), then ya::ens::grid_lds_lanes_for(n_max); 1 = one thread per cell
+    // (ya::ens::grid_lds_walk); 4, 16 or 64 = that many whatever the functor says (ya::ens::grid_lds_walk_coop: several
+    // lanes call the functor for one i at once).  A replica whose LDS has no room for the terms of 16 candidates
+    // (ya::ens::grid_lds_coop_bytes, with links grid_lds_links_coop_bytes) is stepped with one lane per cell, still
+    // from LDS.  Any choice gives the same bits.  No part in take_step, the 14-launch path or the Gabriel form.
+    int lds_step_lanes = 0;
+    // the lanes per cell of the last launch that stepped from LDS: 0 before any, 1 after that fallback
+    int lds_step_lanes_used = 0;
 
     Ensemble(int n_replicas, int n_max, int grid_size = 50, float cube_size = 1)
         : Base{"Grid_solver", n_replicas, n_max, grid_size, cube_size}
@@ -696,7 +1002,12 @@ public:
             for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
             return;
         }
-        launch_lds_steps<pw_int, pw_friction>(ya::ens::grid_lds_bytes<Pt>(n_max), dt, n_steps);
+        const int lanes = lds_lanes_wanted<pw_int, pw_friction>();
+        const size_t with_lanes = lanes > 1 ? ya::ens::grid_lds_coop_bytes<Pt>(n_max, lanes) : 0;
+        if (with_lanes != 0)
+            run_lds_steps<pw_int, pw_friction>(lanes, with_lanes, dt, n_steps);
+        else  // one lane, or no room for the term buffer
+            run_lds_steps<pw_int, pw_friction>(1, ya::ens::grid_lds_bytes<Pt>(n_max), dt, n_steps);
     }
 
     template<Pairwise_interaction<Pt> pw_int>
@@ -726,7 +1037,12 @@ public:
             for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
             return;
         }
-        launch_lds_steps<pw_int, pw_friction>(lds, dt, n_steps, ya::ens::view_of(links));
+        const int lanes = lds_lanes_wanted<pw_int, pw_friction>();
+        const size_t with_lanes = lanes > 1 ? ya::ens::grid_lds_links_coop_bytes<Pt>(n_max, slots, lanes) : 0;
+        if (with_lanes != 0)
+            run_lds_steps<pw_int, pw_friction>(lanes, with_lanes, dt, n_steps, ya::ens::view_of(links));
+        else  // one lane, or no room for the term buffer beside the list
+            run_lds_steps<pw_int, pw_friction>(1, lds, dt, n_steps, ya::ens::view_of(links));
     }
 
 protected:
@@ -736,17 +1052,40 @@ protected:
         return eligible && (lds_steps > 0 || (lds_steps == 0 && ya::ens::lds_steps_pay(
                                                                     this->n_replicas, this->n_max, this->n_cubes)));
     }
-    // n_steps steps as launches of at most lds_steps_max steps each with `lds` bytes of dynamic LDS: of grid_lds_steps,
-    // or of grid_lds_steps_linked with its Links_view as `more`.
+    // the lanes per cell a launch from LDS is asked to run with (lds_step_lanes; whether they fit is the caller's)
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    int lds_lanes_wanted() const
+    {
+        const int lanes = lds_step_lanes;
+        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
+        if (lanes != 0) return lanes;
+        return ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::grid_lds_lanes_for(this->n_max) : 1;
+    }
+    // launch_lds_steps of the kernel of `lanes` lanes per cell (1, 4, 16 or 64), which fit
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename... More>
+    void run_lds_steps(const int lanes, const size_t lds, const float dt, const int n_steps, const More... more)
+    {
+        lds_step_lanes_used = lanes;
+        if (lanes == 64)
+            launch_lds_steps<pw_int, pw_friction, 64>(lds, dt, n_steps, more...);
+        else if (lanes == 16)
+            launch_lds_steps<pw_int, pw_friction, 16>(lds, dt, n_steps, more...);
+        else if (lanes == 4)
+            launch_lds_steps<pw_int, pw_friction, 4>(lds, dt, n_steps, more...);
+        else
+            launch_lds_steps<pw_int, pw_friction, 1>(lds, dt, n_steps, more...);
+    }
+    // n_steps steps as launches of at most lds_steps_max steps each with `lds` bytes of dynamic LDS: of grid_lds_steps,
+    // or of grid_lds_steps_linked with its Links_view as `more`, with LANES lanes per cell.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, typename... More>
     void launch_lds_steps(const size_t lds, const float dt, const int n_steps, const More... more)
     {
         assert(lds_steps_max >= 1);
         const auto kernel = [] {
             if constexpr (sizeof...(More) == 0)
-                return &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction>;
+                return &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction, LANES>;
             else
-                return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction>;
+                return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction, LANES>;
         }();
         // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
         static size_t lds_allowed = 64 * 1024;

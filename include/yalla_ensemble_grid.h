@@ -76,8 +76,18 @@ int ya_gens_get_grid(ya_gens* ens, int replica, int* cube_id, int* point_id, int
  * "lds_steps": -1 (this harness's default) = ya_gens_take_steps always runs the 14 launches per step, 1 = launches of
  * one workgroup per replica that step from LDS (ya::ens::grid_lds_steps) whenever the call is eligible, 0 = the
  * engine's choice (ya::ens::lds_steps_pay); "lds_steps_max" (>= 1, default 256): the steps of one such launch.
- * Neither changes a bit of the positions, old_v, the grid arrays or the status.  Any other value of a known name, and
- * a known name on a NULL handle, is -3; an unknown name -2. */
+ * "lds_step_lanes": Ensemble<Pt, Grid_solver>::lds_step_lanes, the lanes per cell inside such a launch -- 1 (this
+ * harness's default) = one thread per cell, the kernel every caller ran before the setting existed; 4, 16 or 64 =
+ * that many lanes share a cell's candidates whatever the functor declares (ya::ens::grid_lds_walk_coop); 0 = the
+ * engine's choice: one lane unless the model's functors are declared YA_STATELESS, else
+ * ya::ens::grid_lds_lanes_for(n_max): 16 up to 32 cells, 4 up to 64, else 1 (measured).  Where the workgroup's LDS has no room
+ * for the terms of 16 candidates behind the keys (ya::ens::grid_lds_coop_bytes<Pt>(n_max, lanes) == 0: a 7-float
+ * point at n_max = 1024 with 4 lanes, an 8-float point there with any) the launch runs with one lane, still from LDS.
+ * None of them changes a bit of the positions, old_v, the grid arrays or the status.
+ * "lds_step_lanes_used" is THE GETTER of Ensemble<Pt, Grid_solver>::lds_step_lanes_used: with value 0 the call sets
+ * nothing and RETURNS the lanes per cell of the last launch that stepped from LDS -- 0 before any, 1 after the
+ * fallback to one lane, else 4, 16 or 64 (the list of exported functions stays as it was).
+ * Any other value of a known name, and a known name on a NULL handle, is -3; an unknown name -2. */
 int ya_gens_set_param(ya_gens* ens, const char* name, double value);
 
 #pragma GCC visibility pop

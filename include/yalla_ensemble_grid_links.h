@@ -60,7 +60,11 @@ int ya_glens_set_old_v(ya_glens* ens, const float* in);
 int ya_glens_status(ya_glens* ens, int replica, int clear);
 int ya_glens_get_grid(ya_glens* ens, int replica, int* cube_id, int* point_id, int* cube_start, int* cube_end);
 
-/* "sum_order", "lds_steps" (this harness's default: -1), "lds_steps_max": as ya_gens_set_param.  "links_path": 0
+/* "sum_order", "lds_steps" (this harness's default: -1), "lds_steps_max", "lds_step_lanes" (this harness's default:
+ * 1; the term buffer lies behind the incidence list: ya::ens::grid_lds_links_coop_bytes<Pt>(n_max, slots_per_replica,
+ * lanes), and where that is 0 -- a list that leaves no room for 16 candidates' terms -- the launch runs with one lane,
+ * still from LDS), "lds_step_lanes_used" (the getter: value 0, returns the lanes of the last launch from LDS, 0 before
+ * any, 1 after the fallback): as ya_gens_set_param.  "links_path": 0
  * (default) = the ordered link forces, inside launches that step from LDS where allowed and eligible, else as the
  * 14-launch step with ya::ens::link_forces_ordered; 1 = link_forces<Pt> (include/links.cuh: global atomics, no fixed
  * order, no skipping rule) as a Generic_forces lambda, never from LDS.  Path 0 gives the same bits whatever else is

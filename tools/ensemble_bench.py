@@ -9,6 +9,7 @@
     python tools/ensemble_bench.py --whole-steps [--out profiles/ensemble_whole_step_bench.json]
     python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
     python tools/ensemble_bench.py --solver grid --lds-steps [--out profiles/ensemble_grid_lds_steps_bench.json]
+    python tools/ensemble_bench.py --solver grid --lds-steps --lds-step-lanes 0,1,4,16,64 [--out profiles/ensemble_grid_lds_lanes_bench.json]
     python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
     python tools/ensemble_bench.py --solver grid --links [--out profiles/ensemble_grid_links_bench.json]
 
@@ -44,6 +45,12 @@ stays short.  ratio_* = the setting's rate over the baseline's.
 per launch), the same protocol, the listed whole_step_lanes settings alternating; lanes 1 (one thread per cell, the
 reference column) is always among them.  n in {4, 16, 32, 64, 100, 256, 1024} x the same M range, M * n^2 <= 2^28.
 ratio_lanes_L = the rate with L lanes per cell over the rate with 1.
+
+--solver grid --lds-steps --lds-step-lanes 0,1,4,16,64: ONE GridEnsemble("relu", M, n, grid_size fitted to the ball)
+per shape with lds_steps 1 (up to 256 steps per launch), the protocol of --whole-step-lanes, the listed lds_step_lanes
+settings alternating with each other and with the 14-launch step of the same object (lds_steps -1); lanes 1 is always
+among them.  n in {4, 16, 32, 64, 100, 256, 1024} x M in {1, 16, 64, 256, 1024, 4096}.  ratio_* = the setting's rate
+over the rate with one lane per cell; each lanes column records lds_step_lanes_used.
 
 --links: ONE LinkedEnsemble("relu_links", M, n, S = n) per shape (every cell holds one link to a random other cell of
 its replica), the same protocol, four settings alternating: link_forces with global atomics as a generic force of
@@ -84,6 +91,8 @@ WHOLE_SETTINGS = {"six_launches": (-1, 256), "whole_1_step_per_launch": (1, 1), 
 # --solver grid --lds-steps: one GridEnsemble("relu", M, n), (lds_steps, lds_steps_max)
 LDS_SHAPES = [(m, n) for n in (32, 100, 256, 512, 1024) for m in (1, 16, 64, 256, 1024, 4096)]
 LDS_SETTINGS = {"fourteen_launches": (-1, 256), "lds_1_step_per_launch": (1, 1), "lds_256_steps_per_launch": (1, 256)}
+# --solver grid --lds-steps --lds-step-lanes: one GridEnsemble("relu", M, n), lds_step_lanes settings and the 14 launches
+LDS_LANES_SHAPES = [(m, n) for n in (4, 16, 32, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)]
 WHOLE_LANES_SHAPES = [(m, n) for n in (4, 16, 32, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)
                       if m * n * n <= 2 ** 28]
 LINKS_SHAPES = [(m, n) for n in (32, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096) if m * n * n <= 2 ** 28]
@@ -493,6 +502,76 @@ def measure_whole_lanes(m, n, lanes_list, window, repeats):
     return row
 
 
+def measure_lds_lanes(m, n, lanes_list, window, repeats):
+    """One GridEnsemble: launches that step from LDS (up to 256 steps each) with every lds_step_lanes setting of
+    lanes_list, and the 14-launch step of the same object, alternated."""
+    b = Together(m, n)
+    settings = [("lanes_%d" % lanes, 1, lanes) for lanes in lanes_list] + [("fourteen_launches", -1, 1)]
+
+    def apply(lds_steps, lanes):
+        b.lds(lds_steps, 256)
+        b.ens.set_param("lds_step_lanes", lanes)
+    try:
+        ks, used = {}, {}
+        for key, lds_steps, lanes in settings:
+            apply(lds_steps, lanes)
+            b.steps(3)
+            if lds_steps == 1:
+                used[key] = b.ens.lds_step_lanes_used
+            ks[key] = calibrate(b, window)
+        samples = {key: [] for key in ks}
+        for _ in range(repeats):  # L0, L1, L4, ..., the 14 launches, L0, ...
+            for key, lds_steps, lanes in settings:
+                apply(lds_steps, lanes)
+                samples[key].append(timed(b, ks[key]))
+        launches = b.ens.lds_step_launches
+    finally:
+        b.close()
+    row = {"n_replicas": m, "n": n, "grid_size": grid_size_for(n), "lds_step_launches": launches}
+    for key, _, _ in settings:
+        row[key] = summary(samples[key], m * n, ks[key])
+        if key in used:
+            row[key]["lds_step_lanes_used"] = used[key]
+    for key, _, _ in settings:
+        row["ratio_" + key] = row[key]["cell_updates_per_s"] / row["lanes_1"]["cell_updates_per_s"]
+    row["spread"] = max(row[key]["spread"] for key, _, _ in settings)  # of the worst side
+    return row
+
+
+def main_lds_lanes(args):
+    """--solver grid --lds-steps --lds-step-lanes: several lanes per cell inside the launches that step from LDS against
+    one lane per cell, and the 14-launch step beside them, of the same GridEnsemble."""
+    lanes_list = sorted({int(v) for v in args.lds_step_lanes.split(",")} | {1})
+    shapes = LDS_LANES_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    for m, n in shapes:  # the warm-up of every shape and setting
+        run = Together(m, n)
+        for lanes in lanes_list:
+            run.lds(1, 256)
+            run.ens.set_param("lds_step_lanes", lanes)
+            run.steps(5)
+        run.lds(-1, 256)
+        run.steps(5)
+        run.close()
+    rows = []
+    keys = ["lanes_%d" % lanes for lanes in lanes_list] + ["fourteen_launches"]
+    for m, n in shapes:
+        rows.append(measure_lds_lanes(m, n, lanes_list, args.window, args.repeats))
+        r = rows[-1]
+        print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:9.2f}" for key in keys)
+              + " us/step   ratios " + " ".join(f"{r['ratio_' + key]:.2f}" for key in keys)
+              + f"  spread {r['spread']:.3f}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --solver grid --lds-steps --lds-step-lanes " + args.lds_step_lanes,
+                      "model": "relu", "dt": DT, "window_s": args.window, "repeats": args.repeats,
+                      "ratios": "cell updates per second against lanes_1 of the same object", "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio_lanes_0": min(r.get("ratio_lanes_0", 1.0) for r in rows),
+                      "max_ratio_lanes_0": max(r.get("ratio_lanes_0", 1.0) for r in rows)}))
+
+
 def main_whole_lanes(args):
     lanes_list = sorted({int(v) for v in args.whole_step_lanes.split(",")} | {1})
     shapes = WHOLE_LANES_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
@@ -540,13 +619,23 @@ def main():
                          "--solver grid: ordered link forces from LDS against the 14-launch step of the same ensemble")
     ap.add_argument("--lds-steps", action="store_true",
                     help="with --solver grid: launches that step from LDS against the 14-launch step of the same ensemble")
+    ap.add_argument("--lds-step-lanes", default=None, metavar="L,L,...",
+                    help="with --solver grid --lds-steps: these lds_step_lanes settings against lanes 1 of the same "
+                         "ensemble, the 14-launch step beside them")
     args = ap.parse_args()
     global GRID, GABRIEL, LANES, SHAPES
+    if args.lds_step_lanes and not args.lds_steps:
+        ap.error("--lds-step-lanes goes with --solver grid --lds-steps")
     if args.lds_steps:
         if args.solver != "grid" or args.trace_shape or args.whole_steps or args.links:
             ap.error("--lds-steps measures the grid ensemble (--solver grid) on its own")
         GRID = True
-        main_lds(args)
+        if args.lds_step_lanes:
+            if not set(args.lds_step_lanes.split(",")) <= {"0", "1", "4", "16", "64"}:
+                ap.error("--lds-step-lanes takes a list out of 0,1,4,16,64")
+            main_lds_lanes(args)
+        else:
+            main_lds(args)
         return
     if args.links:
         if args.solver == "gabriel" or args.trace_shape or args.whole_steps:

@@ -33,16 +33,20 @@ struct Base : public Grid_replicas {
     virtual void set_sum_order(int order) = 0;
     virtual void set_lds_steps(int mode) = 0;
     virtual void set_lds_steps_max(int steps) = 0;
+    virtual void set_lds_step_lanes(int lanes) = 0;
+    virtual int lds_step_lanes_used() = 0;
 };
 
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Policy>
 struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     using Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>::cells;
-    // the harness's own default: the 14-launch step, so that every caller runs what it ran before "lds_steps" existed
+    // the harness's own defaults: the 14-launch step and one lane per cell in launches that step from LDS, so that
+    // every caller runs what it ran before "lds_steps" and "lds_step_lanes" existed
     template<typename... Args>
     explicit Sim(Args... args) : Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>{args...}
     {
         cells.lds_steps = -1;
+        cells.lds_step_lanes = 1;
     }
     long take_steps(float dt, int n_steps) override
     {
@@ -53,6 +57,8 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     }
     void set_lds_steps(int mode) override { cells.lds_steps = mode; }
     void set_lds_steps_max(int steps) override { cells.lds_steps_max = steps; }
+    void set_lds_step_lanes(int lanes) override { cells.lds_step_lanes = lanes; }
+    int lds_step_lanes_used() override { return cells.lds_step_lanes_used; }
     void set_lanes(int lanes) override { cells.lanes_per_cell = lanes; }
     void set_sum_order(int order) override { cells.sum_order = order ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE; }
 };
@@ -123,8 +129,11 @@ int ya_gens_set_param(ya_gens* e, const char* name, double v)
 {
     if (!name) return -3;
     const std::string which = name;
-    if (which != "lanes" && which != "sum_order" && which != "lds_steps" && which != "lds_steps_max") return -2;
+    if (which != "lanes" && which != "sum_order" && which != "lds_steps" && which != "lds_steps_max" &&
+        !ens_harness::lds_lanes_name(which))
+        return -2;
     if (!e) return -3;
+    if (ens_harness::lds_lanes_name(which)) return ens_harness::lds_lanes_param(*e->p, which, v);
     if (which == "lds_steps") {
         if (v != -1 && v != 0 && v != 1) return -3;
         e->p->set_lds_steps((int)v);
@@ -146,5 +155,4 @@ int ya_gens_set_param(ya_gens* e, const char* name, double v)
     e->p->set_sum_order(order);
     return 0;
 }
-
 }  // extern "C"

@@ -37,6 +37,8 @@ struct Base : public Grid_replicas {
     virtual void set_sum_order(int order) = 0;
     virtual void set_lds_steps(int mode) = 0;
     virtual void set_lds_steps_max(int steps) = 0;
+    virtual void set_lds_step_lanes(int lanes) = 0;
+    virtual int lds_step_lanes_used() = 0;
     virtual void set_links_path(int path) = 0;
     virtual int* h_link() = 0;
     virtual int* h_n_links() = 0;
@@ -51,7 +53,7 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     const int slots_per_replica;
     Links links;  // (at least one slot: an object of no slots has nothing to allocate or launch)
     int links_path = 0;
-    // The default of the grid harness: the 14-launch step.
+    // The defaults of the grid harness: the 14-launch step, one lane per cell in launches that step from LDS.
     Sim(int n_replicas, int n_max, int grid_size, float cube_size, int slots_per_replica, float strength)
         : Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base>{n_replicas, n_max, grid_size, cube_size},
           slots_per_replica{slots_per_replica},
@@ -59,6 +61,7 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     {
         static_assert(sizeof(Link) == 2 * sizeof(int), "h_link is handed out as pairs of ints");
         cells.lds_steps = -1;
+        cells.lds_step_lanes = 1;
         *links.h_n = n_slots();
         links.set_d_n(n_slots());
     }
@@ -84,6 +87,8 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     void set_sum_order(int order) override { cells.sum_order = order ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE; }
     void set_lds_steps(int mode) override { cells.lds_steps = mode; }
     void set_lds_steps_max(int steps) override { cells.lds_steps_max = steps; }
+    void set_lds_step_lanes(int lanes) override { cells.lds_step_lanes = lanes; }
+    int lds_step_lanes_used() override { return cells.lds_step_lanes_used; }
     void set_links_path(int path) override { links_path = path; }
     int* h_link() override { return reinterpret_cast<int*>(links.h_link); }
     int* h_n_links() override { return links.h_n; }
@@ -173,8 +178,11 @@ int ya_glens_set_param(ya_glens* e, const char* name, double v)
 {
     if (!name) return -3;
     const std::string which = name;
-    if (which != "sum_order" && which != "lds_steps" && which != "lds_steps_max" && which != "links_path") return -2;
+    if (which != "sum_order" && which != "lds_steps" && which != "lds_steps_max" && which != "links_path" &&
+        !ens_harness::lds_lanes_name(which))
+        return -2;
     if (!e) return -3;
+    if (ens_harness::lds_lanes_name(which)) return ens_harness::lds_lanes_param(*e->p, which, v);
     if (which == "lds_steps") {
         if (v != -1 && v != 0 && v != 1) return -3;
         e->p->set_lds_steps((int)v);

@@ -274,6 +274,20 @@ inline int set_tile_param(Tile_replicas& s, const char* name, double v)
     }
     return -2;
 }
+// "lds_step_lanes" and "lds_step_lanes_used" of the two grid forms that step from LDS (Ensemble<Pt, Grid_solver>::
+// lds_step_lanes, lds_step_lanes_used): Interface declares set_lds_step_lanes and lds_step_lanes_used.  The second
+// name is THE GETTER: set_param with it sets nothing and returns the lanes of the last launch from LDS (0, 1, 4, 16 or
+// 64; the value handed over must be 0).  It travels through set_param because the libraries' exported functions are
+// held to an exact list.
+inline bool lds_lanes_name(const std::string& name) { return name == "lds_step_lanes" || name == "lds_step_lanes_used"; }
+template<typename Interface>
+int lds_lanes_param(Interface& s, const std::string& name, double v)
+{
+    if (name == "lds_step_lanes_used") return v == 0 ? s.lds_step_lanes_used() : -3;
+    if (v != 0 && v != 1 && v != 4 && v != 16 && v != 64) return -3;
+    s.set_lds_step_lanes((int)v);
+    return 0;
+}
 inline int set_cube_size(Grid_replicas& s, float cube_size)
 {
     if (!(cube_size > 0)) return -3;

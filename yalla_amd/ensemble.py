@@ -202,6 +202,13 @@ class GridEnsemble(Ensemble):
     size grid_size**3 touched in between) wherever the model has no generic forces and n_max is at most 1024; 0 leaves
     the choice to the engine, -1 (this harness's default) never does.  The bits are the same either way, grid arrays
     and status included; `lds_step_launches` counts the launches made.
+
+    `set_param("lds_step_lanes", L)` sets the lanes per cell inside such a launch (Ensemble<Pt, Grid_solver>::
+    lds_step_lanes): 1 (this harness's default) is one thread per cell; 4, 16 or 64 share a cell's candidates among that
+    many lanes whatever the functor declares (ya::ens::grid_lds_walk_coop; for replicas of a few dozen cells, which leave
+    most of a workgroup idle otherwise); 0 leaves it to the engine: one lane unless the model's functors are declared
+    YA_STATELESS, else 16 lanes up to n_max = 32, 4 up to 64, 1 beyond (ya::ens::grid_lds_lanes_for).  Any other value is refused (-3).  Every choice gives the
+    same bits.  `lds_step_lanes_used` is what the last such launch ran with: 1 where the term buffer did not fit.
     """
     _PREFIX, _LOADER, _NOUN = "ya_gens_", "grid_ensemble_lib", "grid ensemble"
 
@@ -226,6 +233,15 @@ class GridEnsemble(Ensemble):
         """Launches that stepped from LDS so far (Ensemble<Pt, Grid_solver>::lds_step_launches): 0 unless
         set_param("lds_steps", 0 | 1) allowed them and the call was eligible."""
         return self._whole_step_launches
+
+    @property
+    def lds_step_lanes_used(self):
+        """The lanes per cell of the last launch that stepped from LDS (Ensemble<Pt, Grid_solver>::lds_step_lanes_used):
+        0 before any, 1 where the term buffer of several lanes did not fit the workgroup's LDS."""
+        lanes = self._f("set_param")(self._h, b"lds_step_lanes_used", 0.0)  # (the getter: it sets nothing)
+        if lanes < 0:
+            raise YallaError(f"lds_step_lanes_used failed with harness code {lanes}")
+        return lanes
 
     def status(self, r, clear=True):
         bits = self._f("status")(self._h, int(r), int(bool(clear)))
@@ -267,6 +283,10 @@ class GabrielEnsemble(GridEnsemble):
 
     @property
     def lds_step_launches(self):
+        raise AttributeError("a Gabriel ensemble has no launches that step from LDS")
+
+    @property
+    def lds_step_lanes_used(self):
         raise AttributeError("a Gabriel ensemble has no launches that step from LDS")
 
     def dense_cells(self):
@@ -345,7 +365,9 @@ class LinkedGridEnsemble(GridEnsemble):
     one with an end outside its own replica's rows is skipped.  `set_param("lds_steps", 1)` runs the steps as launches
     of one workgroup per replica that step from LDS (ya::ens::grid_lds_steps_linked) where n_max <= 1024 and the
     incidence list fits beside the keys (`LinkedGridEnsemble.lds_bytes(...) > 0`): the same bits, grid arrays and
-    status included; `lds_step_launches` counts the launches made.
+    status included; `lds_step_launches` counts the launches made.  `set_param("lds_step_lanes", L)` and
+    `lds_step_lanes_used` as `GridEnsemble`'s; the term buffer lies behind the incidence list, and a list that leaves
+    no room for 16 candidates' terms leaves the launch one lane per cell.
 
         with LinkedGridEnsemble("relu_links", 64, 200, slots_per_replica=400, grid_size=12) as cells:
             cells.h_link[r, s] = (r * 200 + a, r * 200 + b); cells.copy_to_device()
