@@ -56,6 +56,8 @@
 // gabriel_coefficient, slabs.
 #pragma once
 
+#include <tuple>
+
 #include "solvers.cuh"
 
 namespace ya {
@@ -220,79 +222,131 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_ma
 
 // ---- whole steps in one launch ---------------------------------------------------------------------------
 // A replica of at most whole_step_capacity<Pt>() rows fits ONE workgroup's LDS with everything a Heun step
-// touches: X, X1, dX, dX1 (sizeof(Pt) per row each), old_v (12 B per row), the fold's scratch and the <= 4
-// partial sums.  ya::ens::whole_steps then runs n_steps whole steps there -- no launch boundary, no global
-// traffic in between -- in the order and the arithmetic of the six launches above, so that every bit agrees.
+// touches.  ya::ens::whole_steps then runs n_steps whole steps there -- no launch boundary, no global traffic in
+// between -- in the order and the arithmetic of the six launches above, so that every bit agrees.  The grid form's
+// launches that step from LDS (ensemble_grid.cuh) do the same with a grid's stencil walk as a stage's forces.
 // The arrays are laid out for n_max rows (dynamic LDS: small replicas share a CU).
 constexpr int WHOLE_STEP_MAX_ROWS = 1024;  // B_r = ceil(n_r / 256) <= 4: a lane's share of a partial sum is ONE row
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;  // gfx950: a workgroup may take the CU's whole LDS
 // ya::fixed_velocity_from_partials' own (static) fold scratch, which comes on top of the dynamic arrays
 constexpr size_t WHOLE_STEP_STATIC_LDS = 3 * UPDATE_BLOCK * sizeof(float);
-template<typename Pt>
-constexpr size_t whole_step_lds_bytes(const int n_max)
-{
-    return (size_t)n_max * (4 * sizeof(Pt) + sizeof(float3))                 // X, X1, dX, dX1, old_v
-           + (size_t)N_floats<Pt>::value * UPDATE_BLOCK * sizeof(float)      // fold256's scratch
-           + (size_t)N_floats<Pt>::value * (WHOLE_STEP_MAX_ROWS / UPDATE_BLOCK) * sizeof(float);  // the partial sums
-}
-// The largest n_max whose arrays fit one workgroup (1024 for every point type up to 8 floats).
-template<typename Pt>
-constexpr int whole_step_capacity()
-{
-    constexpr size_t fixed = whole_step_lds_bytes<Pt>(0) + WHOLE_STEP_STATIC_LDS;
-    static_assert(fixed < LDS_PER_WORKGROUP, "a point type whose fold scratch alone overflows the LDS");
-    constexpr size_t rows = (LDS_PER_WORKGROUP - fixed) / (4 * sizeof(Pt) + sizeof(float3));
-    return rows < (size_t)WHOLE_STEP_MAX_ROWS ? (int)rows : WHOLE_STEP_MAX_ROWS;
-}
-
-// Several lanes per cell (whole_stage_force_coop below) need a term buffer on top of that: one tile's pair terms,
-// [cell][component][j] floats for the 256 / lanes cells of a round and the NF + 4 components of a cell.  THE RULE for
-// the tile length, in partners: n_max rounded up to a multiple of 4 (phase (b) reads 16 bytes at a time; no replica
-// has more partners), at most WHOLE_STEP_COOP_MAX_TILE, at most what WHOLE_STEP_COOP_BUDGET bytes hold (small
-// replicas keep sharing a CU: with 4 lanes a partner costs 64 cells' terms) but no less than
-// WHOLE_STEP_COOP_MIN_TILE for that reason, and at most what is left of the workgroup's LDS.  Where the LDS has no
-// room for WHOLE_STEP_COOP_MIN_TILE partners the answer is 0: the launch runs with one lane per cell.  Otherwise the
-// answer is the launch's dynamic LDS, the term buffer 16-byte aligned behind whole_step_lds_bytes.  No bit depends
-// on the tile length: a cell's terms are added in ascending j into one running sum, tile after tile.
-// The budget is not measured.
+// the term buffer's tile length (lds_layout below); the budget is not measured
 constexpr int WHOLE_STEP_COOP_MIN_TILE = 16;
 constexpr int WHOLE_STEP_COOP_MAX_TILE = 256;
 constexpr size_t WHOLE_STEP_COOP_BUDGET = 32 * 1024;
-template<typename Pt>
-constexpr size_t whole_step_coop_base(const int n_max)  // where the term buffer starts
+
+// the grid form's bitonic sort needs a power of two of keys
+constexpr int grid_lds_key_rows(const int n_max)
 {
-    return (whole_step_lds_bytes<Pt>(n_max) + 15) / 16 * 16;
+    int p = 1;
+    while (p < n_max) p <<= 1;
+    return p;
 }
+// one partner's (candidate's) terms in the term buffer: NF + 4 components for each of the 256 / lanes cells of a round
 template<typename Pt>
 constexpr size_t whole_step_coop_bytes_per_partner(const int lanes)
 {
     return (size_t)(UPDATE_BLOCK / lanes) * (N_floats<Pt>::value + 4) * sizeof(float);
 }
-// (the rule for a term buffer that starts at `base`, a multiple of 16: with links a list lies in between)
-template<typename Pt>
-constexpr size_t whole_step_coop_bytes_behind(const size_t base, const int n_max, const int lanes)
+constexpr size_t lds_rounded_up(const size_t bytes, const size_t to) { return (bytes + to - 1) / to * to; }
+
+// THE LDS LAYOUT of a launch that steps a replica from LDS, all-pairs (whole_steps*, KEYS = false) or grid
+// (grid_lds_steps*, KEYS = true): byte offsets from the start of the dynamic LDS, the term buffer's tile length and
+// the launch's dynamic LDS.  Host plans and kernels both read it; the kernels compute it once, at their start.
+struct Lds_layout {
+    size_t X, X1, dX, dX1;  // the step's arrays: n_max rows of sizeof(Pt) each,
+    size_t old_v;           // n_max rows of 12 bytes,
+    size_t fold;            // fold256's scratch, NF * 256 floats (whole_links_build's scan and the grid kernels' status
+                            // flag borrow it while no fold runs),
+    size_t partials;        // the <= 4 partial sums, NF floats each
+    size_t keys;            // KEYS: one 64-bit (cube, id) key per row of grid_lds_key_rows(n_max)
+    size_t list;            // LINKED: the incidence list, n_max + 1 offsets and at most 2 `slots` entries of 4 bytes
+    size_t terms;           // lanes > 1: the term buffer, `tile` partners' terms
+    int tile;               // the term buffer's tile length in partners (candidates); 0 with one lane or without room
+    size_t bytes;           // the launch's dynamic LDS; 0 = no room (for lanes > 1: run with one lane per cell)
+};
+// THE RULE, region after region in their order.  LINKED (a compile-time fact, not a slot count: a linked launch of
+// no slots still lays out the list's n_max + 1 offsets) and `slots` = the links' slots per replica; lanes = lanes per
+// cell (1, 4, 16 or 64).
+//   the step's arrays   X, X1, dX, dX1, old_v, the fold's scratch, the partial sums: no padding in between.
+//   the keys            8-byte aligned; after the sort, slot s holds the cube of the cell in sorted slot s and the
+//                       slot -> id map at once, 8 bytes per row and no sorted copy of the entries.
+//   the list            THE TWO FORMS DIFFER HERE, and stay as they are: the all-pairs list starts 16-byte aligned and
+//                       its end is rounded up to 16, so that a linked all-pairs launch's bytes are a multiple of 16 even
+//                       with one lane; the grid list starts right behind the keys (whose end is 8-byte aligned; the
+//                       list needs 4) and its end is not rounded.  No room where that end and WHOLE_STEP_STATIC_LDS
+//                       exceed the workgroup's LDS (an 8-float point's 1024 rows and keys leave 896 bytes: no list of
+//                       1025 offsets, whatever `slots` is).
+//   the term buffer     16-byte aligned behind all that: one tile's pair terms for the 256 / lanes cells of a round.
+//                       The tile length, in partners: n_max rounded up to a multiple of 4 (phase (b) reads 16 bytes at
+//                       a time; no replica has more partners), at most WHOLE_STEP_COOP_MAX_TILE, at most what
+//                       WHOLE_STEP_COOP_BUDGET bytes hold (small replicas keep sharing a CU: with 4 lanes a partner
+//                       costs 64 cells' terms) but no less than WHOLE_STEP_COOP_MIN_TILE for that reason, and at most
+//                       what is left of the workgroup's LDS beside WHOLE_STEP_STATIC_LDS.  No room where
+//                       WHOLE_STEP_COOP_MIN_TILE partners do not fit (an 8-float point's 1024 rows and keys leave 896
+//                       bytes; a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4).  No bit depends on
+//                       the tile length: a cell's terms are added in ascending order into one running sum, tile
+//                       after tile.
+// The rule may fill the LDS to the byte: kernels with a list or a term buffer keep their static LDS at
+// WHOLE_STEP_STATIC_LDS (the one-lane unlinked grid kernel's __syncthreads_or takes 256 bytes on top, which its
+// launches spare).  Whether the step's arrays (and keys) fit at all is whole_step_capacity's question
+// (grid_lds_capacity's), not this function's: without a list and with one lane `bytes` is never 0.
+template<typename Pt, bool KEYS, bool LINKED>
+constexpr Lds_layout lds_layout(const int n_max, const int slots, const int lanes)
 {
+    constexpr size_t NF = N_floats<Pt>::value;
+    const size_t n = (size_t)n_max;
+    Lds_layout l{};
+    l.X1 = n * sizeof(Pt);
+    l.dX = 2 * n * sizeof(Pt);
+    l.dX1 = 3 * n * sizeof(Pt);
+    l.old_v = 4 * n * sizeof(Pt);
+    l.fold = n * (4 * sizeof(Pt) + sizeof(float3));
+    l.partials = l.fold + NF * UPDATE_BLOCK * sizeof(float);
+    size_t end = l.partials + NF * (WHOLE_STEP_MAX_ROWS / UPDATE_BLOCK) * sizeof(float);
+    if (KEYS) {
+        l.keys = lds_rounded_up(end, 8);
+        end = l.keys + (size_t)grid_lds_key_rows(n_max) * sizeof(unsigned long long);
+    }
+    if (LINKED) {
+        l.list = KEYS ? end : lds_rounded_up(end, 16);
+        end = l.list + 4 * (n + 1) + 8 * (size_t)slots;
+    }
+    l.terms = lds_rounded_up(end, 16);
+    if (LINKED && !KEYS) end = l.terms;  // (the all-pairs list's end is rounded)
+    if (LINKED && end + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP) return l;  // no room for the list
+    if (lanes <= 1) {
+        l.bytes = end;
+        return l;
+    }
     const size_t per_partner = whole_step_coop_bytes_per_partner<Pt>(lanes);
-    if (base + WHOLE_STEP_STATIC_LDS + WHOLE_STEP_COOP_MIN_TILE * per_partner > LDS_PER_WORKGROUP) return 0;
-    const size_t room = (LDS_PER_WORKGROUP - WHOLE_STEP_STATIC_LDS - base) / per_partner / 4 * 4;
+    if (l.terms + WHOLE_STEP_STATIC_LDS + WHOLE_STEP_COOP_MIN_TILE * per_partner > LDS_PER_WORKGROUP) return l;
+    const size_t room = (LDS_PER_WORKGROUP - WHOLE_STEP_STATIC_LDS - l.terms) / per_partner / 4 * 4;
     const size_t budget = WHOLE_STEP_COOP_BUDGET / per_partner / 4 * 4;
-    size_t tile = ((size_t)n_max + 3) / 4 * 4;
+    size_t tile = (n + 3) / 4 * 4;
     if (tile > (size_t)WHOLE_STEP_COOP_MAX_TILE) tile = WHOLE_STEP_COOP_MAX_TILE;
     if (tile > budget) tile = budget < (size_t)WHOLE_STEP_COOP_MIN_TILE ? WHOLE_STEP_COOP_MIN_TILE : budget;
     if (tile > room) tile = room;
-    return base + tile * per_partner;
+    l.tile = (int)tile;
+    l.bytes = l.terms + tile * per_partner;
+    return l;
 }
+// Lds_layout::fold for those who borrow it while no fold runs (whole_links_build's scan, the grid kernels' status flag)
 template<typename Pt>
-constexpr size_t whole_step_coop_lds_bytes(const int n_max, const int lanes)
+__device__ __forceinline__ int* lds_fold_scratch(unsigned char* lds, const int n_max)
 {
-    return whole_step_coop_bytes_behind<Pt>(whole_step_coop_base<Pt>(n_max), n_max, lanes);
+    return reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(lds) + 4 * n_max) + n_max);
 }
-// the tile length of that rule, in partners; 0 = no room
+
+// The largest n_max whose step arrays fit one workgroup, the static fold scratch included; at most
+// WHOLE_STEP_MAX_ROWS (1024 for every point type up to 8 floats).
 template<typename Pt>
-constexpr int whole_step_coop_tile(const int n_max, const int lanes)
+constexpr int whole_step_capacity()
 {
-    const size_t bytes = whole_step_coop_lds_bytes<Pt>(n_max, lanes);
-    return bytes == 0 ? 0 : (int)((bytes - whole_step_coop_base<Pt>(n_max)) / whole_step_coop_bytes_per_partner<Pt>(lanes));
+    constexpr size_t fixed = lds_layout<Pt, false, false>(0, 0, 1).bytes + WHOLE_STEP_STATIC_LDS;
+    static_assert(fixed < LDS_PER_WORKGROUP, "a point type whose fold scratch alone overflows the LDS");
+    constexpr size_t rows = (LDS_PER_WORKGROUP - fixed) / (lds_layout<Pt, false, false>(1, 0, 1).bytes + WHOLE_STEP_STATIC_LDS - fixed);
+    return rows < (size_t)WHOLE_STEP_MAX_ROWS ? (int)rows : WHOLE_STEP_MAX_ROWS;
 }
 
 }  // namespace ens
@@ -441,7 +495,7 @@ __device__ __forceinline__ void whole_stage_forces(const int n, const int id_bas
 }
 
 // THE STEP IN LDS, written once: n_steps Heun steps of a replica of n > 0 rows by ONE 256-thread workgroup whose
-// dynamic LDS starts with the arrays of whole_step_lds_bytes<Pt>(n_max).  Rows [0, n) of the replica's d_X and d_old_v
+// dynamic LDS starts with the step's arrays of lds_layout.  Rows [0, n) of the replica's d_X and d_old_v
 // are read at the start and written at the end; in between, per stage: stage_forces(sh_in, sh_v, sh_rhs) -- every
 // thread calls it; it leaves the right-hand sides of the positions sh_in (X, then X1) in sh_rhs and may have barriers
 // of its own, the barrier after it is here -- then the mean or fixed point (whole_stage_fix), the predictor or
@@ -452,6 +506,9 @@ __device__ __forceinline__ void whole_steps_in_lds(const int n_max, const int n,
     const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, unsigned char* lds, const Stage_forces& stage_forces)
 {
+    // Lds_layout's X .. partials as typed pointer steps, one running sum of n_max rows each.  (Byte offsets taken from a
+    // layout computed in the kernel give the same addresses through other instructions, in every kernel's prologue;
+    // the kernels keep the code they had.)
     constexpr int NF = N_floats<Pt>::value;
     Pt* sh_X = reinterpret_cast<Pt*>(lds);
     Pt* sh_X1 = sh_X + n_max;
@@ -512,20 +569,12 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
     const int replica = blockIdx.x;
     const int n = count_of(d_n, replica, n_max);
     if (n <= 0) return;  // (the whole workgroup; an empty replica is left alone)
-    float* sh_part = nullptr;  // the term buffer of several lanes per cell
-    if constexpr (LANES > 1 && !LINKED) sh_part = reinterpret_cast<float*>(whole_step_lds + whole_step_coop_base<Pt>(n_max));
-    int* sh_off = nullptr;        // the incidence list: n_max + 1 offsets,
-    unsigned* sh_ent = nullptr;   // at most 2 slots_per_replica entries
-    if constexpr (LINKED) {
-        sh_off = reinterpret_cast<int*>(whole_step_lds + whole_step_links_base<Pt>(n_max));
-        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
-        if constexpr (LANES > 1)
-            sh_part = reinterpret_cast<float*>(
-                whole_step_lds + whole_step_links_part_base<Pt>(n_max, links.slots_per_replica));
-        // (its scratch is the fold's, behind the step's arrays)
-        whole_links_build(links, replica, n, n_max, sh_off, sh_ent,
-            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(whole_step_lds) + 4 * n_max) + n_max));
-    }
+    const Lds_layout layout = lds_layout<Pt, false, LINKED>(n_max, links.slots_per_replica, LANES);
+    float* const sh_part = reinterpret_cast<float*>(whole_step_lds + layout.terms);  // (used with several lanes per cell)
+    int* const sh_off = reinterpret_cast<int*>(whole_step_lds + layout.list);  // LINKED: n_max + 1 offsets,
+    unsigned* const sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);  // at most 2 slots_per_replica entries
+    if constexpr (LINKED)  // (its scratch is the fold's)
+        whole_links_build(links, replica, n, n_max, sh_off, sh_ent, lds_fold_scratch<Pt>(whole_step_lds, n_max));
 
     const size_t base = (size_t)replica * n_max;
     whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, whole_step_lds,
@@ -537,7 +586,7 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
             whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_in, sh_v, sh_rhs, sh_part, tile);
         });
 }
-// One thread per cell: dynamic LDS of whole_step_lds_bytes<Pt>(n_max).
+// One thread per cell: dynamic LDS of lds_layout<Pt, false, false>(n_max, 0, 1).bytes.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, const int* __restrict__ d_n, const float dt,
     const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
@@ -546,8 +595,8 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, con
     whole_steps_of_a_replica<Pt, pw_int, pw_friction, 1>(
         n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, 0);
 }
-// COOP_LANES (4, 16 or 64) lanes per cell, for functors that keep no per-cell state: dynamic LDS of
-// whole_step_coop_lds_bytes<Pt>(n_max, COOP_LANES), tile = whole_step_coop_tile<Pt>(n_max, COOP_LANES) > 0.
+// COOP_LANES (4, 16 or 64) lanes per cell, for functors that keep no per-cell state: dynamic LDS and tile of
+// lds_layout<Pt, false, false>(n_max, 0, COOP_LANES), which has room (.bytes > 0).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_coop(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
@@ -557,8 +606,8 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_coop(const int n_max
         n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile);
 }
 // The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage; LANES = 1,
-// 4, 16 or 64: dynamic LDS of whole_step_links_lds_bytes<Pt>(n_max, links.slots_per_replica, LANES) > 0, tile =
-// whole_step_links_tile<Pt>(n_max, links.slots_per_replica, LANES).  Besides what whole_steps reads, the replica's
+// 4, 16 or 64: dynamic LDS and tile of lds_layout<Pt, false, true>(n_max, links.slots_per_replica, LANES), which has
+// room.  Besides what whole_steps reads, the replica's
 // slots of links.d_link and *links.d_n are read, at the start of the launch.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_linked(const int n_max, const int* __restrict__ d_n,
@@ -784,6 +833,123 @@ protected:
     }
     int max_blocks() const { return ya::ens::reduce_blocks(n_max); }
     dim3 grid_of(int blocks_per_replica) const { return dim3((unsigned)((size_t)n_replicas * blocks_per_replica)); }
+
+    // ---- take_steps: from LDS or as the loop of take_step, decided and launched once for every form ---------------
+    // A form whose replicas can be stepped from one workgroup's LDS (the all-pairs form's whole steps, the grid
+    // form's lds steps) supplies
+    //     static constexpr bool lds_keys                      its lds_layout has keys
+    //     Lds_knobs lds_knobs()                               its capacity, settings and rules, as below
+    //     template<pw_int, pw_friction, int LANES, bool LINKED> static auto lds_kernel()
+    //     template<int LANES, bool LINKED> auto lds_kernel_args(const Lds_layout&)    a tuple: the kernel's arguments
+    //                                                         behind d_old_v (LINKED: the Links_view follows them)
+    struct Lds_knobs {
+        int capacity;          // the largest n_max that fits (whole_step_capacity / grid_lds_capacity)
+        int allowed;           // -1 = never, 1 = whenever eligible, 0 = where `pays` (whole_steps / lds_steps)
+        bool pays;             // the form's *_pay rule
+        int steps_per_launch;  // a launch runs at most this many steps
+        int lanes;             // lanes per cell: 0 = the engine's choice, 1, 4, 16 or 64 (whole_step_lanes / lds_step_lanes)
+        int lanes_for;         // the form's *_lanes_for rule for stateless functors
+        long* launches;        // counted here (whole_step_launches / lds_step_launches)
+        int* lanes_used;       // the lanes per cell of the last such launch (whole_step_lanes_used / lds_step_lanes_used)
+    };
+    // THE PLAN of a take_steps call (LINKED: with the ordered links of `slots` slots per replica; has_gen: with other
+    // generic forces).  From LDS where the call is eligible -- the replica fits (capacity), there are no generic
+    // forces but the links, whose incidence list fits the workgroup's LDS too -- and `allowed` says so; with `lanes`
+    // lanes per cell (0: one unless the functors are stateless, then lanes_for) where the term buffer fits, with one
+    // otherwise.  (An unlinked launch and a linked one of no slots differ: the list's n_max + 1 offsets are in the
+    // linked one.)
+    struct Lds_plan {
+        bool from_lds;
+        int lanes;
+        Lds_layout layout;  // of that many lanes: tile and bytes
+    };
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
+    Lds_plan plan_lds_steps(const Lds_knobs& k, const int slots, const bool has_gen) const
+    {
+        const auto layout_of = [&](const int lanes) { return lds_layout<Pt, Form::lds_keys, LINKED>(n_max, slots, lanes); };
+        const bool eligible = n_max <= k.capacity && !has_gen && layout_of(1).bytes != 0;
+        if (!eligible || k.allowed < 0 || (k.allowed == 0 && !k.pays)) return {false, 0, Lds_layout{}};
+        assert(k.steps_per_launch >= 1);
+        int lanes = k.lanes;
+        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
+        if (lanes == 0) lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? k.lanes_for : 1;
+        if (lanes > 1 && layout_of(lanes).bytes == 0) lanes = 1;  // no room for the term buffer
+        const Lds_plan plan{true, lanes, layout_of(lanes)};
+        assert(plan.layout.bytes > 0 && (lanes == 1 || plan.layout.tile >= 4));
+        return plan;
+    }
+    // from a run-time lane count to a template parameter (as ya::coop::with_lanes)
+    template<typename F>
+    static void with_lds_lanes(const int lanes, F&& f)
+    {
+        if (lanes == 64) return f(std::integral_constant<int, 64>{});
+        if (lanes == 16) return f(std::integral_constant<int, 16>{});
+        if (lanes == 4) return f(std::integral_constant<int, 4>{});
+        f(std::integral_constant<int, 1>{});
+    }
+    // n_steps steps as launches of at most steps_per_launch steps each of the form's kernel of the plan's lanes, if
+    // the plan is to step from LDS; false: nothing was launched.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
+    bool steps_from_lds(const float dt, const int n_steps, const bool has_gen, const Links_view links = Links_view{})
+    {
+        Form& form = *static_cast<Form*>(this);
+        const Lds_knobs k = form.lds_knobs();
+        const Lds_plan plan = plan_lds_steps<pw_int, pw_friction, LINKED>(k, links.slots_per_replica, has_gen);
+        if (!plan.from_lds) return false;
+        *k.lanes_used = plan.lanes;
+        const size_t lds = plan.layout.bytes;
+        with_lds_lanes(plan.lanes, [&](auto lanes) {
+            constexpr int LANES = decltype(lanes)::value;
+            const auto kernel = Form::template lds_kernel<pw_int, pw_friction, LANES, LINKED>();
+            // beyond 64 KiB of dynamic LDS a kernel has to be told once (per kernel: the static is this instance's)
+            static size_t lds_allowed = 64 * 1024;
+            if (lds > lds_allowed) {
+                YA_CHECK((int)hipFuncSetAttribute(
+                    reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                lds_allowed = lds;
+            }
+            const auto launch = [&](const int steps, auto... more) {
+                kernel<<<dim3((unsigned)n_replicas), ya::UPDATE_BLOCK, lds>>>(n_max, d_n, dt, steps, fix_kind_of(1),
+                    fix_kind_of(2), fix_point, d_X, d_old_v, more...);
+                (*k.launches)++;
+            };
+            const auto args = form.template lds_kernel_args<LANES, LINKED>(plan.layout);
+            for (int done = 0; done < n_steps;) {
+                const int steps = n_steps - done < k.steps_per_launch ? n_steps - done : k.steps_per_launch;
+                if constexpr (LINKED)
+                    std::apply([&](auto... more) { launch(steps, more..., links); }, args);
+                else
+                    std::apply([&](auto... more) { launch(steps, more...); }, args);
+                done += steps;
+            }
+        });
+        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
+        rhs_zeroed[0] = rhs_zeroed[1] = false;
+        return true;
+    }
+    // take_steps(dt, n_steps, gen_forces) of such a form: from LDS, or n_steps calls of take_step
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void steps(const float dt, const int n_steps, Generic_forces<Pt> gen_forces)
+    {
+        if (steps_from_lds<pw_int, pw_friction, false>(dt, n_steps, !ya::is_no_gen_forces<Pt>(gen_forces))) return;
+        for (int s = 0; s < n_steps; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
+    }
+    // take_steps(dt, n_steps, links): from LDS, or n_steps calls of take_step with ya::ens::link_forces_ordered as the
+    // generic force
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void steps(const float dt, const int n_steps, const Replica_links links)
+    {
+        const int slots = links.slots_per_replica;
+        assert(slots >= 0 && (size_t)n_replicas * (size_t)slots <= (size_t)links.links.n_max);
+        if (steps_from_lds<pw_int, pw_friction, true>(dt, n_steps, false, view_of(links))) return;
+        const int n_max = this->n_max;
+        const int* d_n = this->d_n;
+        Links* l = &links.links;
+        Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
+            link_forces_ordered<Pt>(Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
+        };
+        for (int s = 0; s < n_steps; s++) take_step<pw_int, pw_friction>(dt, gen);
+    }
 };
 
 }  // namespace ens
@@ -826,7 +992,7 @@ public:
     // Lanes per cell inside a whole-step launch: 0 (default) = the engine's choice -- one lane per cell unless the
     // functors are declared stateless (YA_STATELESS), then ya::ens::whole_step_lanes_for(n_max); 1, 4, 16 or 64 = that
     // many whatever the functor says (several lanes call the functor for one i at once, as with lanes_per_cell).  A
-    // replica whose LDS has no room for the terms of 16 partners (ya::ens::whole_step_coop_lds_bytes) is stepped with
+    // replica whose LDS has no room for the terms of 16 partners (ya::ens::lds_layout's .bytes == 0) is stepped with
     // one lane per cell, still as whole-step launches.  Any choice gives the same bits.
     int whole_step_lanes = 0;
     // the lanes per cell of the last whole-step launch: 0 before any, 1 after that fallback
@@ -844,16 +1010,12 @@ public:
         take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
     }
     // n_steps Heun steps of every replica, bit for bit n_steps calls of take_step: as whole-step launches of at
-    // most steps_per_launch steps each where the call is eligible and whole_steps allows it, as that loop otherwise.
+    // most steps_per_launch steps each where the call is eligible and whole_steps allows it, as that loop otherwise
+    // (ya::ens::Stepper::steps).
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
-        const Whole_plan plan = plan_whole<pw_int, pw_friction>(-1, !ya::is_no_gen_forces<Pt>(gen_forces));
-        if (!plan.whole) {
-            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
-            return;
-        }
-        run_whole<pw_int, pw_friction, false>(dt, n_steps, plan, ya::ens::Links_view{});
+        this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
     }
 
     template<Pairwise_interaction<Pt> pw_int>
@@ -867,116 +1029,41 @@ public:
     // take_step(dt, gen) where gen calls ya::ens::link_forces_ordered, and that loop unless the call runs whole:
     // as whole-step launches (ya::ens::whole_steps_linked) where whole_steps allows it, n_max <=
     // ya::ens::whole_step_capacity<Pt>() and the incidence list fits the workgroup's LDS
-    // (ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots_per_replica, 1) > 0); with whole_step_lanes lanes per
+    // (ya::ens::lds_layout<Pt, false, true>(n_max, slots_per_replica, 1).bytes > 0); with whole_step_lanes lanes per
     // cell where the term buffer fits beside the list, with one otherwise.  A launch reads the links and their
     // count at its start: what a model's kernel left there before the call is what the call sees.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
     {
-        const int slots = links.slots_per_replica;
-        assert(slots >= 0 && (size_t)this->n_replicas * (size_t)slots <= (size_t)links.links.n_max);
-        const Whole_plan plan = plan_whole<pw_int, pw_friction>(slots);
-        if (!plan.whole) {
-            const int n_max = this->n_max;
-            const int* d_n = this->d_n;
-            Links* l = &links.links;
-            Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
-                ya::ens::link_forces_ordered<Pt>(ya::ens::Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
-            };
-            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
-            return;
-        }
-        run_whole<pw_int, pw_friction, true>(dt, n_steps, plan, ya::ens::view_of(links));
+        this->template steps<pw_int, pw_friction>(dt, n_steps, links);
     }
 
 protected:
-    // How a take_steps call runs: as whole-step launches or not; if so, with how many lanes per cell, the term
-    // buffer's tile length in partners (0 with one lane) and the launch's dynamic LDS.
-    struct Whole_plan {
-        bool whole;
-        int lanes;
-        int tile;
-        size_t lds;
-    };
-    // THE PLAN of a take_steps call with the ordered links of `slots` slots per replica (slots < 0: without links,
-    // and has_gen says whether the call has generic forces).  Whole where the call is eligible -- the replica fits
-    // (whole_step_capacity), and without links there are no generic forces, with links the incidence list fits the
-    // workgroup's LDS too -- and whole_steps allows it; with whole_step_lanes lanes per cell (0: the engine's choice)
-    // where the term buffer fits, with one otherwise.
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    Whole_plan plan_whole(const int slots, const bool has_gen = false) const
+    // What ya::ens::Stepper's launches from LDS ask of a form: the layout has no keys; the settings above; the kernels.
+    static constexpr bool lds_keys = false;
+    typename Base::Lds_knobs lds_knobs()
     {
-        const int n_max = this->n_max;
-        const bool linked = slots >= 0;
-        const bool eligible = n_max <= ya::ens::whole_step_capacity<Pt>() &&
-                              (linked ? ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots, 1) != 0 : !has_gen);
-        const bool whole = eligible && (whole_steps > 0 ||
-                                        (whole_steps == 0 && ya::ens::whole_steps_pay(this->n_replicas, n_max)));
-        if (!whole) return {false, 0, 0, 0};
-        assert(steps_per_launch >= 1);
-        int lanes = whole_step_lanes;
-        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
-        if (lanes == 0)
-            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::whole_step_lanes_for(n_max) : 1;
-        // (an unlinked launch and a linked one of no slots differ: the list's n_max + 1 offsets are in the linked one)
-        const auto lds_with = [=](const int l) {
-            return linked  ? ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots, l)
-                   : l > 1 ? ya::ens::whole_step_coop_lds_bytes<Pt>(n_max, l)
-                           : ya::ens::whole_step_lds_bytes<Pt>(n_max);
-        };
-        if (lanes > 1 && lds_with(lanes) == 0) lanes = 1;  // no room
-        const int tile = linked      ? ya::ens::whole_step_links_tile<Pt>(n_max, slots, lanes)
-                         : lanes > 1 ? ya::ens::whole_step_coop_tile<Pt>(n_max, lanes)
-                                     : 0;
-        const size_t lds = lds_with(lanes);
-        assert(lds > 0 && (lanes == 1 || tile >= 4));
-        return {true, lanes, tile, lds};
+        constexpr int capacity = ya::ens::whole_step_capacity<Pt>();
+        return {capacity, whole_steps, ya::ens::whole_steps_pay(this->n_replicas, this->n_max), steps_per_launch, whole_step_lanes, ya::ens::whole_step_lanes_for(this->n_max), &whole_step_launches,
+            &whole_step_lanes_used};
     }
-
-    // A planned whole run: the kernel of the plan's lanes.
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
-    void run_whole(const float dt, const int n_steps, const Whole_plan plan, const ya::ens::Links_view links)
-    {
-        whole_step_lanes_used = plan.lanes;
-        if (plan.lanes == 64)
-            launch_whole<pw_int, pw_friction, 64, LINKED>(dt, n_steps, plan, links);
-        else if (plan.lanes == 16)
-            launch_whole<pw_int, pw_friction, 16, LINKED>(dt, n_steps, plan, links);
-        else if (plan.lanes == 4)
-            launch_whole<pw_int, pw_friction, 4, LINKED>(dt, n_steps, plan, links);
-        else
-            launch_whole<pw_int, pw_friction, 1, LINKED>(dt, n_steps, plan, links);
-        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
-        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
-    }
-
-    // n_steps whole steps as launches of at most steps_per_launch steps each, LANES lanes per cell (which fit); LINKED:
-    // with the ordered link forces of `links` in every stage (ya::ens::whole_steps_linked).
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
-    void launch_whole(const float dt, const int n_steps, const Whole_plan plan, const ya::ens::Links_view links)
+    static auto lds_kernel()
     {
-        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
-        static size_t lds_allowed = 64 * 1024;
-        const auto launch = [&](auto kernel, auto... more) {
-            if (plan.lds > lds_allowed) {
-                YA_CHECK((int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-                lds_allowed = plan.lds;
-            }
-            for (int done = 0; done < n_steps;) {
-                const int k = n_steps - done < steps_per_launch ? n_steps - done : steps_per_launch;
-                kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, plan.lds>>>(this->n_max, this->d_n, dt, k,
-                    this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v, more...);
-                whole_step_launches++;
-                done += k;
-            }
-        };
         if constexpr (LINKED)
-            launch(&ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>, plan.tile, links);
+            return &ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>;
         else if constexpr (LANES > 1)
-            launch(&ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>, plan.tile);
+            return &ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>;
         else
-            launch(&ya::ens::whole_steps<Pt, pw_int, pw_friction>);
+            return &ya::ens::whole_steps<Pt, pw_int, pw_friction>;
+    }
+    template<int LANES, bool LINKED>
+    auto lds_kernel_args(const ya::ens::Lds_layout& layout) const
+    {
+        if constexpr (LINKED || LANES > 1)
+            return std::tuple<int>{layout.tile};
+        else
+            return std::tuple<>{};
     }
 
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>

@@ -37,7 +37,7 @@
 // from *links.d_n on are unused, a slot with an end outside its own replica's rows is skipped, a cell's terms are
 // added in ascending slot order from +0, the right-hand side is "zero, links, force kernel").  The result is DEFINED
 // as K calls of take_step(dt, gen) with gen calling ya::ens::link_forces_ordered<Pt>; where the replica and its
-// incidence list fit one workgroup's LDS (ya::ens::grid_lds_links_bytes<Pt>(n_max, S) != 0) and `lds_steps` allows
+// incidence list fit one workgroup's LDS (ya::ens::lds_layout<Pt, true, true>(n_max, S, 1).bytes != 0) and `lds_steps` allows
 // it, the call runs as launches that step from LDS (ya::ens::grid_lds_steps_linked), bit for bit alike, the public
 // grid arrays and d_status included, with lds_step_lanes lanes per cell where the term buffer fits behind the list.
 // Out of scope for these linked launches: the Gabriel form, the fast tier, graph capture, links that change inside a
@@ -238,26 +238,10 @@ inline int grid_lanes_for(const int n_replicas, const int n_max)
 // a cube), and offs[k] -- the number of cells in cubes below k -- is a binary search of that order.  Nothing of size
 // grid_size^3 is touched between the launch's first load and its last stores.
 //
-// THE LDS RULE  The step's own arrays (whole_step_lds_bytes<Pt>(n_max), ensemble.cuh), 8-byte aligned, then ONE 64-bit
-// key per row: cube id in the high word, local id in the low word; after the sort, slot s holds the cube of the
-// cell in sorted slot s and the slot -> id map at once, 8 bytes per row and no sorted copy of the entries.  The
-// bitonic sort needs a power of two of keys, so the array is laid out for n_max rounded up to one.
-constexpr int grid_lds_key_rows(const int n_max)
-{
-    int p = 1;
-    while (p < n_max) p <<= 1;
-    return p;
-}
-template<typename Pt>
-constexpr size_t grid_lds_keys_base(const int n_max)  // where the keys start
-{
-    return (whole_step_lds_bytes<Pt>(n_max) + 7) / 8 * 8;
-}
-template<typename Pt>
-constexpr size_t grid_lds_bytes(const int n_max)
-{
-    return grid_lds_keys_base<Pt>(n_max) + (size_t)grid_lds_key_rows(n_max) * sizeof(unsigned long long);
-}
+// THE LDS RULE is ya::ens::lds_layout<Pt, true, LINKED> (ensemble.cuh): the step's own arrays, then ONE 64-bit key per
+// row: cube id in the high word, local id in the low word; the array is laid out for grid_lds_key_rows(n_max), n_max
+// rounded up to a power of two, which the bitonic sort needs.  With ordered links the replica's incidence list lies
+// right behind the keys; the term buffer of several lanes per cell (grid_lds_walk_coop below) behind all that.
 // The largest n_max whose launch fits one workgroup, ya::fixed_velocity_from_partials' static fold scratch included;
 // at most WHOLE_STEP_MAX_ROWS (1024 for every point type up to 8 floats: an 8-float point's 1024 rows leave 896 bytes).
 template<typename Pt>
@@ -265,76 +249,8 @@ constexpr int grid_lds_capacity()
 {
     int rows = 0;
     for (int n = 1; n <= WHOLE_STEP_MAX_ROWS; n++)
-        if (grid_lds_bytes<Pt>(n) + WHOLE_STEP_STATIC_LDS <= LDS_PER_WORKGROUP) rows = n;  // (the rule never falls)
+        if (lds_layout<Pt, true, false>(n, 0, 1).bytes + WHOLE_STEP_STATIC_LDS <= LDS_PER_WORKGROUP) rows = n;  // (the rule never falls)
     return rows;
-}
-
-// With ordered links (grid_lds_steps_linked) the replica's incidence list (ensemble_links.cuh: n_max + 1 offsets and
-// at most 2 S entries of 4 bytes, whole_step_links_list_bytes) lies behind the keys, whose end is 8-byte aligned (the
-// list needs 4): the step's arrays, then the keys, then the list.  The answer is the launch's dynamic LDS; 0 = no room
-// within the workgroup's LDS beside the fold's static scratch (an 8-float point's 1024 rows leave 896 bytes: no
-// list of 1025 offsets, whatever S is).  The rule may fill the LDS to the byte: grid_lds_steps_linked's static LDS is
-// WHOLE_STEP_STATIC_LDS and no more (grid_lds_steps' __syncthreads_or takes 256 bytes on top, which its launches spare).
-template<typename Pt>
-constexpr size_t grid_lds_links_base(const int n_max)  // where the list starts
-{
-    return grid_lds_bytes<Pt>(n_max);
-}
-template<typename Pt>
-constexpr size_t grid_lds_links_bytes(const int n_max, const int slots)
-{
-    const size_t bytes = grid_lds_links_base<Pt>(n_max) + whole_step_links_list_bytes(n_max, slots);
-    return bytes + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP ? 0 : bytes;
-}
-
-// SEVERAL LANES PER CELL (grid_lds_walk_coop below) need a term buffer: it lies behind what the launch lays out anyway
-// -- the step's arrays and the keys, with links the incidence list too -- 16-byte aligned, and is sized by the all-pairs
-// whole steps' own rule with that start (whole_step_coop_bytes_behind, ensemble.cuh: a tile of candidates, n_max rounded
-// up to a multiple of 4, at most WHOLE_STEP_COOP_MAX_TILE, at most what WHOLE_STEP_COOP_BUDGET holds but no less than
-// WHOLE_STEP_COOP_MIN_TILE, at most what is left beside WHOLE_STEP_STATIC_LDS).  The answer is the launch's dynamic LDS;
-// 0 = no room for WHOLE_STEP_COOP_MIN_TILE candidates' terms: the call steps from LDS with one lane per cell (an
-// 8-float point's 1024 rows leave 896 bytes; a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4).
-// The rule may fill the LDS to the byte, so the kernels of several lanes keep their static LDS at
-// WHOLE_STEP_STATIC_LDS as the linked one does.  No bit depends on the tile length.
-template<typename Pt>
-constexpr size_t grid_lds_coop_base(const int n_max)  // where the term buffer starts
-{
-    return (grid_lds_bytes<Pt>(n_max) + 15) / 16 * 16;
-}
-template<typename Pt>
-constexpr size_t grid_lds_coop_bytes(const int n_max, const int lanes)
-{
-    return whole_step_coop_bytes_behind<Pt>(grid_lds_coop_base<Pt>(n_max), n_max, lanes);
-}
-template<typename Pt>
-constexpr size_t grid_lds_links_coop_base(const int n_max, const int slots)
-{
-    return (grid_lds_links_base<Pt>(n_max) + whole_step_links_list_bytes(n_max, slots) + 15) / 16 * 16;
-}
-template<typename Pt>
-constexpr size_t grid_lds_links_coop_bytes(const int n_max, const int slots, const int lanes)
-{
-    if (grid_lds_links_bytes<Pt>(n_max, slots) == 0) return 0;
-    const size_t base = grid_lds_links_coop_base<Pt>(n_max, slots);
-    if (base + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP) return 0;
-    return whole_step_coop_bytes_behind<Pt>(base, n_max, lanes);
-}
-// the tile length of that rule, in candidates, for a term buffer that starts at `base` and ends at `bytes`; 0 = no room
-template<typename Pt>
-constexpr int grid_lds_coop_tile_of(const size_t base, const size_t bytes, const int lanes)
-{
-    return bytes == 0 ? 0 : (int)((bytes - base) / whole_step_coop_bytes_per_partner<Pt>(lanes));
-}
-template<typename Pt>
-constexpr int grid_lds_coop_tile(const int n_max, const int lanes)
-{
-    return grid_lds_coop_tile_of<Pt>(grid_lds_coop_base<Pt>(n_max), grid_lds_coop_bytes<Pt>(n_max, lanes), lanes);
-}
-template<typename Pt>
-constexpr int grid_lds_links_coop_tile(const int n_max, const int slots, const int lanes)
-{
-    return grid_lds_coop_tile_of<Pt>(
-        grid_lds_links_coop_base<Pt>(n_max, slots), grid_lds_links_coop_bytes<Pt>(n_max, slots, lanes), lanes);
 }
 
 // The replica's cube ids (ya::cube_id_of, clamped as grid_count_batched clamps it) and THE ORDER: sh_key[0 .. n)
@@ -663,7 +579,7 @@ __device__ __forceinline__ void grid_lds_walk_coop(const int n, const int id_bas
 }
 
 // n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS (dynamic LDS of
-// grid_lds_bytes<Pt>(n_max)): ya::ens::whole_steps_in_lds (ensemble.cuh) with a stage's forces = grid_lds_order +
+// lds_layout<Pt, true, LINKED>(n_max, slots, LANES).bytes): ya::ens::whole_steps_in_lds (ensemble.cuh) with a stage's forces = grid_lds_order +
 // grid_lds_walk of the stage's positions.  Bit for bit n_steps of the 14-launch take_step without generic forces.
 // Global memory: d_n[r] is read once; rows [0, n_r) of d_X and d_old_v are read at the start and written at the end;
 // at the end the grid arrays of the LAST stage's order, as the 14-launch path leaves them -- d_cube_id and d_point_id
@@ -678,9 +594,8 @@ __device__ __forceinline__ void grid_lds_walk_coop(const int n, const int id_bas
 // ordered link forces of its positions as the right-hand sides (whole_stage_links), the order's barriers follow, and
 // the walk adds the stage's forces to them.  Links do not change during a launch.
 // LANES (4, 16 or 64; Ensemble<Pt, Grid_solver>::lds_step_lanes): the walk is grid_lds_walk_coop, its term buffer
-// behind all that (dynamic LDS of grid_lds_coop_bytes<Pt>(n_max, LANES) > 0, LINKED: grid_lds_links_coop_bytes), the
-// tile length the rule's, read from the same constexpr functions as the host's.  LANES == 1 is the one-lane code as
-// it was.  (lanes_per_cell, the 14-launch step's knob, plays no part.)
+// behind all that, the tile length the layout's, read from the same constexpr function as the host's.  LANES == 1 is
+// the one-lane code as it was.  (lanes_per_cell, the 14-launch step's knob, plays no part.)
 // Not here: the Gabriel form, the fast tier, graph capture.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED, int LANES = 1>
 __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, const int* __restrict__ d_n,
@@ -697,28 +612,14 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
         for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = 0;
         return;
     }
-    unsigned long long* sh_key = reinterpret_cast<unsigned long long*>(grid_step_lds + grid_lds_keys_base<Pt>(n_max));
-    int* sh_off = nullptr;       // the incidence list: n_max + 1 offsets,
-    unsigned* sh_ent = nullptr;  // at most 2 slots_per_replica entries
-    if constexpr (LINKED) {
-        sh_off = reinterpret_cast<int*>(grid_step_lds + grid_lds_links_base<Pt>(n_max));
-        sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);
-        // (its scratch is the fold's, behind the step's arrays)
-        whole_links_build(links, replica, n, n_max, sh_off, sh_ent,
-            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max));
-    }
-    float* sh_part = nullptr;  // the term buffer of several lanes per cell
-    int tile = 0;
-    if constexpr (LANES > 1) {
-        if constexpr (LINKED) {
-            sh_part = reinterpret_cast<float*>(
-                grid_step_lds + grid_lds_links_coop_base<Pt>(n_max, links.slots_per_replica));
-            tile = grid_lds_links_coop_tile<Pt>(n_max, links.slots_per_replica, LANES);
-        } else {
-            sh_part = reinterpret_cast<float*>(grid_step_lds + grid_lds_coop_base<Pt>(n_max));
-            tile = grid_lds_coop_tile<Pt>(n_max, LANES);
-        }
-    }
+    const Lds_layout layout = lds_layout<Pt, true, LINKED>(n_max, links.slots_per_replica, LANES);
+    unsigned long long* const sh_key = reinterpret_cast<unsigned long long*>(grid_step_lds + layout.keys);
+    int* const sh_off = reinterpret_cast<int*>(grid_step_lds + layout.list);   // LINKED: n_max + 1 offsets,
+    unsigned* const sh_ent = reinterpret_cast<unsigned*>(sh_off + n_max + 1);  // at most 2 slots_per_replica entries
+    if constexpr (LINKED)  // (its scratch is the fold's)
+        whole_links_build(links, replica, n, n_max, sh_off, sh_ent, lds_fold_scratch<Pt>(grid_step_lds, n_max));
+    float* const sh_part = reinterpret_cast<float*>(grid_step_lds + layout.terms);  // (used with several lanes per cell)
+    const int tile = layout.tile;
     const int id_base = replica * n_max;
     bool outside = false;
     whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
@@ -742,10 +643,9 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
     for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = grid_lds_lower_bound(sh_key, n, c);
     if constexpr (LINKED || LANES > 1) {
         // The threads' flags meet in the fold's scratch, which nothing uses after the last step: __syncthreads_or costs
-        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list that grid_lds_links_bytes admits may leave none
-        // (nor may a term buffer that grid_lds_coop_bytes admits).
-        int* sh_flag =
-            reinterpret_cast<int*>(reinterpret_cast<float3*>(reinterpret_cast<Pt*>(grid_step_lds) + 4 * n_max) + n_max);
+        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list or a term buffer that lds_layout admits may
+        // leave none.
+        int* sh_flag = lds_fold_scratch<Pt>(grid_step_lds, n_max);
         if (threadIdx.x == 0) *sh_flag = 0;
         __syncthreads();
         if (outside) *sh_flag = 1;  // (every writer writes the same value)
@@ -767,8 +667,8 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, 
 }
 // The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage: bit for
 // bit n_steps of the 14-launch take_step with ya::ens::link_forces_ordered as its generic force.  Dynamic LDS of
-// grid_lds_links_bytes<Pt>(n_max, links.slots_per_replica) > 0 (LANES > 1: grid_lds_links_coop_bytes).  Besides what grid_lds_steps reads, the replica's
-// slots of links.d_link and *links.d_n are read, at the start of the launch; what it writes is what grid_lds_steps
+// lds_layout<Pt, true, true>(n_max, links.slots_per_replica, LANES).bytes > 0.  Besides what grid_lds_steps reads, the
+// replica's slots of links.d_link and *links.d_n are read, at the start of the launch; what it writes is what grid_lds_steps
 // writes.  No atomics but the status bit, no scratch, no cooperative launch.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked(const int n_max, const int* __restrict__ d_n,
@@ -962,7 +862,7 @@ public:
     // 1 = whenever the call is eligible, 0 (default) = the engine's choice, eligible and
     // ya::ens::lds_steps_pay(n_replicas, n_max, n_cubes).  Eligible: n_max <= ya::ens::grid_lds_capacity<Pt>() and
     // either no generic forces, or ya::ens::Replica_links whose incidence list fits
-    // (ya::ens::grid_lds_links_bytes<Pt>(n_max, slots_per_replica) != 0).  Any choice gives the same bits.
+    // (ya::ens::lds_layout<Pt, true, true>(n_max, slots_per_replica, 1).bytes != 0).  Any choice gives the same bits.
     int lds_steps = 0;
     // Such a launch runs at most this many steps (no single kernel runs unboundedly long); take_steps splits longer
     // requests.
@@ -973,8 +873,7 @@ public:
     // are declared stateless (YA_STATELESS), then ya::ens::grid_lds_lanes_for(n_max); 1 = one thread per cell
     // (ya::ens::grid_lds_walk); 4, 16 or 64 = that many whatever the functor says (ya::ens::grid_lds_walk_coop: several
     // lanes call the functor for one i at once).  A replica whose LDS has no room for the terms of 16 candidates
-    // (ya::ens::grid_lds_coop_bytes, with links grid_lds_links_coop_bytes) is stepped with one lane per cell, still
-    // from LDS.  Any choice gives the same bits.  No part in take_step, the 14-launch path or the Gabriel form.
+    // (ya::ens::lds_layout's .bytes == 0) is stepped with one lane per cell, still from LDS.  Any choice gives the same bits.  No part in take_step, the 14-launch path or the Gabriel form.
     int lds_step_lanes = 0;
     // the lanes per cell of the last launch that stepped from LDS: 0 before any, 1 after that fallback
     int lds_step_lanes_used = 0;
@@ -990,24 +889,13 @@ public:
         take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
     }
     // n_steps Heun steps of every replica, bit for bit n_steps calls of take_step: as launches of at most lds_steps_max
-    // steps each that step from LDS where the call is eligible and lds_steps allows it, as that loop otherwise.  After
-    // such launches the public grid arrays and d_status hold what the loop would have left; d_dX / d_X1 / d_dX1 and
-    // the build's private arrays are left as they were.
+    // steps each that step from LDS where the call is eligible and lds_steps allows it, as that loop otherwise
+    // (ya::ens::Stepper::steps).  After such launches the public grid arrays and d_status hold what the loop would have
+    // left; d_dX / d_X1 / d_dX1 and the build's private arrays are left as they were.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
-        const int n_max = this->n_max;
-        const bool eligible = ya::is_no_gen_forces<Pt>(gen_forces) && n_max <= ya::ens::grid_lds_capacity<Pt>();
-        if (!from_lds(eligible)) {
-            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen_forces);
-            return;
-        }
-        const int lanes = lds_lanes_wanted<pw_int, pw_friction>();
-        const size_t with_lanes = lanes > 1 ? ya::ens::grid_lds_coop_bytes<Pt>(n_max, lanes) : 0;
-        if (with_lanes != 0)
-            run_lds_steps<pw_int, pw_friction>(lanes, with_lanes, dt, n_steps);
-        else  // one lane, or no room for the term buffer
-            run_lds_steps<pw_int, pw_friction>(1, ya::ens::grid_lds_bytes<Pt>(n_max), dt, n_steps);
+        this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
     }
 
     template<Pairwise_interaction<Pt> pw_int>
@@ -1019,93 +907,39 @@ public:
     // (ensemble_links.cuh's contract; this file's header).  Bit for bit n_steps calls of take_step(dt, gen) where gen
     // calls ya::ens::link_forces_ordered, and that loop unless the call steps from LDS: as launches of
     // ya::ens::grid_lds_steps_linked where lds_steps allows it, n_max <= ya::ens::grid_lds_capacity<Pt>() and the
-    // incidence list fits the workgroup's LDS beside the keys (ya::ens::grid_lds_links_bytes<Pt>(n_max,
-    // slots_per_replica) != 0).  A launch reads the links and their count at its start: what a model's kernel left
-    // there before the call is what the call sees.
+    // incidence list fits the workgroup's LDS beside the keys (ya::ens::lds_layout<Pt, true, true>(n_max,
+    // slots_per_replica, 1).bytes != 0).  A launch reads the links and their count at its start: what a model's kernel
+    // left there before the call is what the call sees.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, ya::ens::Replica_links links)
     {
-        const int n_max = this->n_max, slots = links.slots_per_replica;
-        assert(slots >= 0 && (size_t)this->n_replicas * (size_t)slots <= (size_t)links.links.n_max);
-        const size_t lds = ya::ens::grid_lds_links_bytes<Pt>(n_max, slots);
-        if (!from_lds(n_max <= ya::ens::grid_lds_capacity<Pt>() && lds != 0)) {
-            const int* d_n = this->d_n;
-            Links* l = &links.links;
-            Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
-                ya::ens::link_forces_ordered<Pt>(ya::ens::Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
-            };
-            for (int s = 0; s < n_steps; s++) this->template take_step<pw_int, pw_friction>(dt, gen);
-            return;
-        }
-        const int lanes = lds_lanes_wanted<pw_int, pw_friction>();
-        const size_t with_lanes = lanes > 1 ? ya::ens::grid_lds_links_coop_bytes<Pt>(n_max, slots, lanes) : 0;
-        if (with_lanes != 0)
-            run_lds_steps<pw_int, pw_friction>(lanes, with_lanes, dt, n_steps, ya::ens::view_of(links));
-        else  // one lane, or no room for the term buffer beside the list
-            run_lds_steps<pw_int, pw_friction>(1, lds, dt, n_steps, ya::ens::view_of(links));
+        this->template steps<pw_int, pw_friction>(dt, n_steps, links);
     }
 
 protected:
-    // whether an eligible take_steps call steps from LDS (lds_steps)
-    bool from_lds(const bool eligible) const
+    // What ya::ens::Stepper's launches from LDS ask of a form: the layout has keys; the settings above; the kernels,
+    // which read the tile length from the layout themselves.
+    static constexpr bool lds_keys = true;
+    typename ya::ens::Stepper<Pt, Ensemble<Pt, Solver>>::Lds_knobs lds_knobs()
     {
-        return eligible && (lds_steps > 0 || (lds_steps == 0 && ya::ens::lds_steps_pay(
-                                                                    this->n_replicas, this->n_max, this->n_cubes)));
+        constexpr int capacity = ya::ens::grid_lds_capacity<Pt>();
+        return {capacity, lds_steps,
+            ya::ens::lds_steps_pay(this->n_replicas, this->n_max, this->n_cubes), lds_steps_max, lds_step_lanes,
+            ya::ens::grid_lds_lanes_for(this->n_max), &lds_step_launches, &lds_step_lanes_used};
     }
-    // the lanes per cell a launch from LDS is asked to run with (lds_step_lanes; whether they fit is the caller's)
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    int lds_lanes_wanted() const
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
+    static auto lds_kernel()
     {
-        const int lanes = lds_step_lanes;
-        assert(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64);
-        if (lanes != 0) return lanes;
-        return ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::grid_lds_lanes_for(this->n_max) : 1;
-    }
-    // launch_lds_steps of the kernel of `lanes` lanes per cell (1, 4, 16 or 64), which fit
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename... More>
-    void run_lds_steps(const int lanes, const size_t lds, const float dt, const int n_steps, const More... more)
-    {
-        lds_step_lanes_used = lanes;
-        if (lanes == 64)
-            launch_lds_steps<pw_int, pw_friction, 64>(lds, dt, n_steps, more...);
-        else if (lanes == 16)
-            launch_lds_steps<pw_int, pw_friction, 16>(lds, dt, n_steps, more...);
-        else if (lanes == 4)
-            launch_lds_steps<pw_int, pw_friction, 4>(lds, dt, n_steps, more...);
+        if constexpr (LINKED)
+            return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction, LANES>;
         else
-            launch_lds_steps<pw_int, pw_friction, 1>(lds, dt, n_steps, more...);
+            return &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction, LANES>;
     }
-    // n_steps steps as launches of at most lds_steps_max steps each with `lds` bytes of dynamic LDS: of grid_lds_steps,
-    // or of grid_lds_steps_linked with its Links_view as `more`, with LANES lanes per cell.
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, typename... More>
-    void launch_lds_steps(const size_t lds, const float dt, const int n_steps, const More... more)
+    template<int LANES, bool LINKED>
+    auto lds_kernel_args(const ya::ens::Lds_layout&) const
     {
-        assert(lds_steps_max >= 1);
-        const auto kernel = [] {
-            if constexpr (sizeof...(More) == 0)
-                return &ya::ens::grid_lds_steps<Pt, pw_int, pw_friction, LANES>;
-            else
-                return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction, LANES>;
-        }();
-        // beyond 64 KiB of dynamic LDS a kernel has to be told once (per instance: the static is this template's)
-        static size_t lds_allowed = 64 * 1024;
-        if (lds > lds_allowed) {
-            YA_CHECK((int)hipFuncSetAttribute(
-                reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_allowed = lds;
-        }
-        const float cut2 = ya::cutoff_squared(this->cube_size);
-        for (int done = 0; done < n_steps;) {
-            const int k = n_steps - done < lds_steps_max ? n_steps - done : lds_steps_max;
-            kernel<<<dim3((unsigned)this->n_replicas), ya::UPDATE_BLOCK, lds>>>(this->n_max, this->d_n, dt, k,
-                this->fix_kind_of(1), this->fix_kind_of(2), this->fix_point, this->d_X, this->d_old_v, this->cube_size,
-                this->grid_size, this->n_cubes, cut2, sum_order == YA_SUM_BY_PLANE, this->d_cube_id, this->d_point_id,
-                this->d_offs, this->d_status, more...);
-            lds_step_launches++;
-            done += k;
-        }
-        // d_dX / d_dX1 were neither written nor zeroed: a later take_step with generic forces zeroes them itself
-        this->rhs_zeroed[0] = this->rhs_zeroed[1] = false;
+        return std::make_tuple(this->cube_size, this->grid_size, this->n_cubes, ya::cutoff_squared(this->cube_size),
+            sum_order == YA_SUM_BY_PLANE, this->d_cube_id, this->d_point_id, this->d_offs, this->d_status);
     }
 
     // Five launches: the grid of every replica from d_in, then the forces.

@@ -1,7 +1,7 @@
 // Ordered link forces for Ensemble<Pt, Tile_solver> and Ensemble<Pt, Grid_solver> (ensemble_grid.cuh: inside its
 // launches that step from LDS too) and, as a generic force, for the Gabriel form.
-// Part of ensemble.cuh, which includes it between the whole-step pieces it builds on and the whole-step kernels
-// that use it; a model includes ensemble.cuh.
+// Part of ensemble.cuh, which includes it behind the LDS layout and before the whole-step kernels that use it; a
+// model includes ensemble.cuh.
 //
 //     Links protrusions{n_replicas * S, strength};      // the reference's own Links, over the flat id space
 //     cells.take_steps<my_force>(dt, K, ya::ens::Replica_links{protrusions, S});
@@ -128,40 +128,7 @@ void link_forces_ordered(const Replica_links rl, const int n_rows, const int n_m
 }
 
 // ---- inside a whole-step launch --------------------------------------------------------------------------
-// THE LDS RULE.  Behind the step's arrays (whole_step_lds_bytes, 16-byte aligned) lies the incidence list:
-// n_max + 1 offsets and at most 2 S entries of 4 bytes; behind the list, 16-byte aligned, the term buffer of
-// several lanes per cell, its tile length by whole_step_coop_lds_bytes' own rule with that start.  The answer is
-// the launch's dynamic LDS, a multiple of 16; 0 = no room within the workgroup's LDS (for lanes > 1: run with one).
-constexpr size_t whole_step_links_list_bytes(const int n_max, const int slots)
-{
-    return 4 * ((size_t)n_max + 1) + 8 * (size_t)slots;
-}
-template<typename Pt>
-constexpr size_t whole_step_links_base(const int n_max)  // where the list starts
-{
-    return whole_step_coop_base<Pt>(n_max);
-}
-template<typename Pt>
-constexpr size_t whole_step_links_part_base(const int n_max, const int slots)  // where the term buffer starts
-{
-    return (whole_step_links_base<Pt>(n_max) + whole_step_links_list_bytes(n_max, slots) + 15) / 16 * 16;
-}
-template<typename Pt>
-constexpr size_t whole_step_links_lds_bytes(const int n_max, const int slots, const int lanes)
-{
-    const size_t base = whole_step_links_part_base<Pt>(n_max, slots);
-    if (base + WHOLE_STEP_STATIC_LDS > LDS_PER_WORKGROUP) return 0;
-    if (lanes <= 1) return base;
-    return whole_step_coop_bytes_behind<Pt>(base, n_max, lanes);
-}
-// the tile length of that rule, in partners; 0 = no room (or one lane per cell)
-template<typename Pt>
-constexpr int whole_step_links_tile(const int n_max, const int slots, const int lanes)
-{
-    const size_t bytes = whole_step_links_lds_bytes<Pt>(n_max, slots, lanes);
-    return (bytes == 0 || lanes <= 1) ? 0
-        : (int)((bytes - whole_step_links_part_base<Pt>(n_max, slots)) / whole_step_coop_bytes_per_partner<Pt>(lanes));
-}
+// Where the incidence list lies in the launch's LDS is ya::ens::lds_layout's (ensemble.cuh): Lds_layout::list.
 
 // The replica's incidence list, built once per launch by the whole workgroup (every thread calls it: barriers).
 // sh_off[c] .. sh_off[c + 1] are cell c's entries in sh_ent, in slot order; an entry is the other end's local row,

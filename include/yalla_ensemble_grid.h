@@ -81,7 +81,7 @@ int ya_gens_get_grid(ya_gens* ens, int replica, int* cube_id, int* point_id, int
  * that many lanes share a cell's candidates whatever the functor declares (ya::ens::grid_lds_walk_coop); 0 = the
  * engine's choice: one lane unless the model's functors are declared YA_STATELESS, else
  * ya::ens::grid_lds_lanes_for(n_max): 16 up to 32 cells, 4 up to 64, else 1 (measured).  Where the workgroup's LDS has no room
- * for the terms of 16 candidates behind the keys (ya::ens::grid_lds_coop_bytes<Pt>(n_max, lanes) == 0: a 7-float
+ * for the terms of 16 candidates behind the keys (ya::ens::lds_layout<Pt, true, false>(n_max, 0, lanes).bytes == 0: a 7-float
  * point at n_max = 1024 with 4 lanes, an 8-float point there with any) the launch runs with one lane, still from LDS.
  * None of them changes a bit of the positions, old_v, the grid arrays or the status.
  * "lds_step_lanes_used" is THE GETTER of Ensemble<Pt, Grid_solver>::lds_step_lanes_used: with value 0 the call sets

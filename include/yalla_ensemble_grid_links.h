@@ -61,8 +61,8 @@ int ya_glens_status(ya_glens* ens, int replica, int clear);
 int ya_glens_get_grid(ya_glens* ens, int replica, int* cube_id, int* point_id, int* cube_start, int* cube_end);
 
 /* "sum_order", "lds_steps" (this harness's default: -1), "lds_steps_max", "lds_step_lanes" (this harness's default:
- * 1; the term buffer lies behind the incidence list: ya::ens::grid_lds_links_coop_bytes<Pt>(n_max, slots_per_replica,
- * lanes), and where that is 0 -- a list that leaves no room for 16 candidates' terms -- the launch runs with one lane,
+ * 1; the term buffer lies behind the incidence list: ya::ens::lds_layout<Pt, true, true>(n_max, slots_per_replica,
+ * lanes).bytes, and where that is 0 -- a list that leaves no room for 16 candidates' terms -- the launch runs with one lane,
  * still from LDS), "lds_step_lanes_used" (the getter: value 0, returns the lanes of the last launch from LDS, 0 before
  * any, 1 after the fallback): as ya_gens_set_param.  "links_path": 0
  * (default) = the ordered link forces, inside launches that step from LDS where allowed and eligible, else as the
@@ -71,8 +71,8 @@ int ya_glens_get_grid(ya_glens* ens, int replica, int* cube_id, int* point_id, i
  * set.  Any other value of a known name, and a known name on a NULL handle, is -3; an unknown name -2. */
 int ya_glens_set_param(ya_glens* ens, const char* name, double value);
 
-/* ya::ens::grid_lds_links_bytes<Pt>(n_max, slots_per_replica) for the model's point type: the dynamic LDS of a linked
- * launch that steps from LDS (the step's arrays, the keys, the incidence list), 0 = no room.  Host arithmetic only:
+/* ya::ens::lds_layout<Pt, true, true>(n_max, slots_per_replica, 1).bytes for the model's point type: the dynamic LDS of a
+ * linked launch that steps from LDS (the step's arrays, the keys, the incidence list), 0 = no room.  Host arithmetic only:
  * callable without a GPU.  -1 unknown model, -3 bad argument (n_max <= 0, slots_per_replica < 0). */
 long ya_glens_lds_bytes(const char* model, int n_max, int slots_per_replica);
 

@@ -61,7 +61,7 @@ int ya_lens_set_param(ya_lens* ens, const char* name, double value);
 /* Ensemble::whole_step_lanes_used: the lanes per cell of the last whole-step launch (0 before any). */
 int ya_lens_whole_step_lanes_used(ya_lens* ens);
 
-/* ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots_per_replica, lanes) for the model's point type: the dynamic
+/* ya::ens::lds_layout<Pt, false, true>(n_max, slots_per_replica, lanes).bytes for the model's point type: the dynamic
  * LDS of a linked whole-step launch, 0 = no room.  Host arithmetic only: callable without a GPU.  -1 unknown model,
  * -3 bad argument (n_max <= 0, slots_per_replica < 0, lanes not 1, 4, 16 or 64). */
 long ya_lens_lds_bytes(const char* model, int n_max, int slots_per_replica, int lanes);

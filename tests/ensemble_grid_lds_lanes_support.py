@@ -1,12 +1,11 @@
 """What the tests of several lanes per cell inside the grid ensemble's launches that step from LDS share
-(tests/test_ensemble_grid_lds_lanes*.py): the LDS rule of the term buffer restated from include/ensemble_grid.cuh
-(ya::ens::grid_lds_coop_bytes, grid_lds_links_coop_bytes), and `Lanes`: one GridEnsemble per lane setting, fed the
+(tests/test_ensemble_grid_lds_lanes*.py): which term of the LDS rule (ensemble_support.lds_layout) decides the
+term buffer's tile and where that changes, and `Lanes`: one GridEnsemble per lane setting, fed the
 same rows, beside THE REFERENCES -- the same object type with lds_step_lanes = 1 (today's kernel) and the 14-launch
 twin (GridTwins).  A plain module, imported as tests/ensemble_support.py is."""
 import numpy as np
-from ensemble_grid_lds_support import GridTwins, grid_lds_bytes
-from ensemble_grid_links_support import grid_links_lds_bytes
-from ensemble_support import LDS, STATIC_LDS, bits, same_grid, tile_behind, up16
+from ensemble_grid_lds_support import GridTwins
+from ensemble_support import LDS, STATIC_LDS, bits, lds_layout, same_grid, tile_behind
 
 from yalla_amd.ensemble import GridEnsemble
 
@@ -14,29 +13,11 @@ LANES = (4, 16, 64)
 
 
 # ---- the rule -------------------------------------------------------------------------------------------------------
-def coop_base(n_floats, n_max):
-    """ya::ens::grid_lds_coop_base: the term buffer starts behind the step's arrays and the keys, 16-byte aligned."""
-    return up16(grid_lds_bytes(n_floats, n_max))
-
-
-def coop_bytes(n_floats, n_max, lanes):
-    """ya::ens::grid_lds_coop_bytes: the dynamic LDS of a launch with `lanes` lanes per cell; 0 = no room for the
-    terms of 16 candidates (one lane per cell)."""
-    base = coop_base(n_floats, n_max)
-    per_candidate, tile, _, _ = tile_behind(base, n_floats, n_max, lanes)
-    return base + tile * per_candidate if tile else 0
-
-
-def coop_tile(n_floats, n_max, lanes):
-    """ya::ens::grid_lds_coop_tile, in candidates; 0 = no room."""
-    return tile_behind(coop_base(n_floats, n_max), n_floats, n_max, lanes)[1]
-
-
 def coop_binding(n_floats, n_max, lanes):
     """Which term of the rule decides the tile length: 0 = n_max rounded up to 4, 1 = the longest tile, 2 = the budget
     (or the shortest tile in its place), 3 = the room left in the workgroup's LDS (the first of those that are equal),
     -1 = no room at all."""
-    _, tile, _, bounds = tile_behind(coop_base(n_floats, n_max), n_floats, n_max, lanes)
+    _, tile, _, bounds = tile_behind(lds_layout(n_floats, n_max, keys=True).terms, n_floats, n_max, lanes)
     return bounds.index(min(bounds)) if tile else -1
 
 
@@ -54,9 +35,9 @@ def links_rule_binding(n_floats, n_max, slots_of, lanes):
     """What decides the linked rule at slots_of(n_max) slots: -2 = the list does not fit (never from LDS), -1 = not 16
     candidates' terms behind it (one lane), 0 .. 3 = the bound that cut the tile length last."""
     slots = slots_of(n_max)
-    if grid_links_lds_bytes(n_floats, n_max, slots) == 0:
+    if lds_layout(n_floats, n_max, True, slots).bytes == 0:
         return -2
-    base = links_coop_base(n_floats, n_max, slots)
+    base = lds_layout(n_floats, n_max, True, slots).terms
     if base + STATIC_LDS > LDS:
         return -1
     return tile_behind(base, n_floats, n_max, lanes)[2]
@@ -71,22 +52,6 @@ def links_rule_edges(n_floats, slots_of, lanes_of=LANES, up_to=1024):
                     n_floats, n_max - 1, slots_of, lanes):
                 edges |= {n_max - 1, n_max}
     return sorted(edges)
-
-
-def links_coop_base(n_floats, n_max, slots):
-    """ya::ens::grid_lds_links_coop_base: behind the incidence list, 16-byte aligned."""
-    return up16(grid_lds_bytes(n_floats, n_max) + 4 * (n_max + 1) + 8 * slots)
-
-
-def links_coop_bytes(n_floats, n_max, slots, lanes):
-    """ya::ens::grid_lds_links_coop_bytes; 0 = the list does not fit, or not 16 candidates' terms behind it."""
-    if grid_links_lds_bytes(n_floats, n_max, slots) == 0:
-        return 0
-    base = links_coop_base(n_floats, n_max, slots)
-    if base + STATIC_LDS > LDS:
-        return 0
-    per_candidate, tile, _, _ = tile_behind(base, n_floats, n_max, lanes)
-    return base + tile * per_candidate if tile else 0
 
 
 def lanes_for(n_max):
@@ -108,7 +73,7 @@ def lanes_expected(model, n_floats, n_max, setting, slots=None):
         lanes = lanes_for(n_max) if model in STATELESS else 1
     if lanes == 1:
         return 1
-    room = coop_bytes(n_floats, n_max, lanes) if slots is None else links_coop_bytes(n_floats, n_max, slots, lanes)
+    room = lds_layout(n_floats, n_max, True, slots, lanes).bytes
     return lanes if room else 1
 
 

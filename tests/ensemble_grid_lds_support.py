@@ -1,8 +1,8 @@
 """What the tests of the grid ensemble's launches that step from LDS share (tests/test_ensemble_grid_lds_steps*.py): the
-LDS rule of include/ensemble_grid.cuh restated, and a GridEnsemble with lds_steps = 1 beside its twin with
+capacity by the LDS rule (ensemble_support.lds_layout), and a GridEnsemble with lds_steps = 1 beside its twin with
 lds_steps = -1 (and lone Solutions where asked for).  A plain module, imported as tests/ensemble_support.py is."""
 import numpy as np
-from ensemble_support import LDS, STATIC_LDS, Lockstep, bits, same_grid, whole_step_bytes
+from ensemble_support import LDS, STATIC_LDS, Lockstep, bits, lds_layout, same_grid
 
 from yalla_amd.ensemble import GridEnsemble
 
@@ -10,24 +10,10 @@ MAX_ROWS = 1024
 UNUSED = np.float32(-7.25)  # what rows past a replica's count hold, to be found again
 
 
-def key_rows(n_max):
-    """ya::ens::grid_lds_key_rows: the bitonic sort's power of two of keys."""
-    p = 1
-    while p < n_max:
-        p *= 2
-    return p
-
-
-def grid_lds_bytes(n_floats, n_max):
-    """ya::ens::grid_lds_bytes: the step's arrays, 8-byte aligned, then one 64-bit (cube, id) key per row of the
-    power of two from n_max up."""
-    return -(-whole_step_bytes(n_floats, n_max) // 8) * 8 + 8 * key_rows(n_max)
-
-
 def grid_lds_capacity(n_floats):
     """ya::ens::grid_lds_capacity: the largest n_max <= 1024 whose launch, the fold's static scratch included, fits a
     workgroup's 160 KiB."""
-    return max(n for n in range(1, MAX_ROWS + 1) if grid_lds_bytes(n_floats, n) + STATIC_LDS <= LDS)
+    return max(n for n in range(1, MAX_ROWS + 1) if lds_layout(n_floats, n, keys=True).bytes + STATIC_LDS <= LDS)
 
 
 def launches_of(model, steps, n_max, n_floats=3, lds_steps_max=256):

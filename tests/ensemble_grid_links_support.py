@@ -1,32 +1,12 @@
-"""What the tests of linked grid ensembles share (tests/test_ensemble_grid_links*.py): the model table, the LDS rule
-of include/ensemble_grid.cuh's linked launches restated, and a LinkedGridEnsemble with lds_steps = 1 beside its twin
+"""What the tests of linked grid ensembles share (tests/test_ensemble_grid_links*.py): the model table and a
+LinkedGridEnsemble with lds_steps = 1 beside its twin
 with lds_steps = -1.  A plain module, imported as tests/ensemble_support.py is."""
 import numpy as np
-from ensemble_grid_lds_support import UNUSED, grid_lds_bytes
-from ensemble_support import LDS, STATIC_LDS, bits, same_grid
+from ensemble_grid_lds_support import UNUSED
+from ensemble_support import bits, same_grid
 
 MODELS = ["links", "links4", "springs_links", "relu_links", "relu_po_links", "relu_cell8_links"]
 N_FLOATS = {"links": 3, "links4": 4, "springs_links": 3, "relu_links": 3, "relu_po_links": 5, "relu_cell8_links": 8}
-
-
-def grid_links_lds_bytes(n_floats, n_max, slots):
-    """ya::ens::grid_lds_links_bytes: the step's arrays, then the keys (grid_lds_bytes, a multiple of 8), then the
-    incidence list of n_max + 1 offsets and 2 S entries of 4 bytes; 0 where that and the fold's static scratch exceed
-    the workgroup's LDS."""
-    total = grid_lds_bytes(n_floats, n_max) + 4 * (n_max + 1) + 8 * slots
-    return 0 if total + STATIC_LDS > LDS else total
-
-
-def largest_grid_slots(n_floats, n_max):
-    """The largest S whose launch fits (the rule falls monotonically to 0 in S); None where not even S = 0 does."""
-    if grid_links_lds_bytes(n_floats, n_max, 0) == 0:
-        return None
-    lo, hi = 0, LDS  # fits, does not
-    assert grid_links_lds_bytes(n_floats, n_max, hi) == 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if grid_links_lds_bytes(n_floats, n_max, mid) > 0 else (lo, mid)
-    return lo
 
 
 def box_rows(n, n_floats, grid_size, seed, shrink=0.92, cube_size=1.0):

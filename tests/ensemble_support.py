@@ -1,7 +1,8 @@
 """What the ensemble suites (tests/test_ensemble*.py) share: seeded rows and bit comparisons, an ensemble and its
-lone Solutions in lock-step, the whole-step twins, the LDS rules of the whole-step launches restated from the headers,
+lone Solutions in lock-step, the whole-step twins, THE LDS RULE of every launch that steps from LDS restated once,
 the three checks of a harness library's C ABI, and the runner of the native programs.  A plain module, imported as
 tests/kats.py is; the suites keep their cases, shapes and literal expectations."""
+import collections
 import os
 import re
 import subprocess
@@ -209,8 +210,10 @@ class Twins(Lockstep):
         self.six.close()
 
 
-# ---- the LDS rules of the whole-step launches, restated from include/ensemble.cuh and ensemble_links.cuh -----------
+# ---- THE LDS RULE of the launches that step a replica from LDS, restated once from ya::ens::lds_layout's comment -------
+# (include/ensemble.cuh; the all-pairs whole steps and the grid form's lds steps, with links and several lanes per cell)
 LDS, STATIC_LDS, MIN_TILE, MAX_TILE, BUDGET = 160 * 1024, 3 * 256 * 4, 16, 256, 32 * 1024
+Layout = collections.namedtuple("Layout", "X1 dX dX1 old_v fold partials keys list terms tile bytes")
 
 
 def up16(x):
@@ -218,15 +221,15 @@ def up16(x):
 
 
 def whole_step_bytes(n_floats, n_max):
-    """ya::ens::whole_step_lds_bytes: the step's arrays (X, X1, dX, dX1, old_v), fold256's scratch, 4 partial sums."""
+    """The step's arrays (X, X1, dX, dX1, old_v), fold256's scratch, 4 partial sums."""
     return n_max * (4 * 4 * n_floats + 12) + n_floats * 256 * 4 + n_floats * 4 * 4
 
 
 def tile_behind(base, n_floats, n_max, lanes):
-    """ya::ens::whole_step_coop_bytes_behind for a term buffer that starts at `base`, by its statements in their
-    order: (bytes per partner, tile length, which bound cut last, the four bounds).  The tile is n_max rounded up to
-    4 (0); at most the longest tile (1); at most what the budget holds but no less than the shortest tile where it
-    cuts (2); at most the room left in the workgroup's LDS (3).  Tile 0 and which -1: the shortest tile has no room."""
+    """The term buffer's rule for a buffer that starts at `base`, by its statements in their order: (bytes per partner,
+    tile length, which bound cut last, the four bounds).  The tile is n_max rounded up to 4 (0); at most the longest
+    tile (1); at most what the budget holds but no less than the shortest tile where it cuts (2); at most the room left
+    in the workgroup's LDS (3).  Tile 0 and which -1: the shortest tile has no room."""
     per_partner = (256 // lanes) * (n_floats + 4) * 4
     room = (LDS - STATIC_LDS - base) // per_partner // 4 * 4
     budget = BUDGET // per_partner // 4 * 4
@@ -243,26 +246,48 @@ def tile_behind(base, n_floats, n_max, lanes):
     return per_partner, tile, which, bounds
 
 
-def coop_base(n_floats, n_max):
-    """Where an unlinked launch's term buffer starts, and a linked launch's incidence list."""
-    return up16(whole_step_bytes(n_floats, n_max))
+def lds_layout(n_floats, n_max, keys=False, slots=None, lanes=1):
+    """ya::ens::lds_layout<Pt, keys, slots is not None>(n_max, slots, lanes): byte offsets of the regions in their
+    order -- the step's arrays; the keys, 8-byte aligned, one 64-bit key per row of the power of two from n_max up; the
+    incidence list of n_max + 1 offsets and 2 `slots` entries of 4 bytes (all-pairs: 16-byte aligned, its end rounded up
+    to 16; grid: right behind the keys, its end not rounded; no room where the end and the static fold scratch exceed
+    the workgroup's LDS); the term buffer, 16-byte aligned, of tile_behind's length -- the tile and the launch's
+    dynamic LDS, 0 = no room.  keys and list are 0 where the launch has none; tile is 0 with one lane."""
+    row = 4 * n_floats
+    fold = n_max * (4 * row + 12)
+    partials = fold + n_floats * 256 * 4
+    end = partials + n_floats * 4 * 4
+    assert end == whole_step_bytes(n_floats, n_max)
+    at_keys = at_list = 0
+    if keys:
+        key_rows = 1
+        while key_rows < n_max:
+            key_rows *= 2
+        at_keys = -(-end // 8) * 8
+        end = at_keys + 8 * key_rows
+    if slots is not None:
+        at_list = end if keys else up16(end)
+        end = at_list + 4 * (n_max + 1) + 8 * slots
+    terms = up16(end)
+    if slots is not None and not keys:
+        end = terms
 
+    def done(tile, total):
+        return Layout(n_max * row, 2 * n_max * row, 3 * n_max * row, 4 * n_max * row, fold, partials, at_keys, at_list,
+                      terms, tile, total)
 
-def coop_tile(n_floats, n_max, lanes):
-    """ya::ens::whole_step_coop_tile; 0 = no room."""
-    return tile_behind(coop_base(n_floats, n_max), n_floats, n_max, lanes)[1]
-
-
-def coop_lds_bytes(n_floats, n_max, lanes):
-    """ya::ens::whole_step_coop_lds_bytes; 0 = no room."""
-    per_partner, tile, _, _ = tile_behind(coop_base(n_floats, n_max), n_floats, n_max, lanes)
-    return coop_base(n_floats, n_max) + tile * per_partner if tile else 0
+    if slots is not None and end + STATIC_LDS > LDS:
+        return done(0, 0)
+    if lanes <= 1:
+        return done(0, end)
+    per_partner, tile, _, _ = tile_behind(terms, n_floats, n_max, lanes)
+    return done(tile, terms + tile * per_partner if tile else 0)
 
 
 def coop_binding(n_floats, n_max, lanes):
     """Which of the rule's terms decides the tile length: 0 = n_max, 1 = the longest tile, 2 = the budget, 3 = the
     room left in the LDS (the first of those that are equal), -1 = no room at all (one lane per cell)."""
-    _, tile, _, bounds = tile_behind(coop_base(n_floats, n_max), n_floats, n_max, lanes)
+    _, tile, _, bounds = tile_behind(lds_layout(n_floats, n_max).terms, n_floats, n_max, lanes)
     return bounds.index(min(bounds)) if tile else -1
 
 
@@ -276,36 +301,28 @@ def coop_rule_edges(n_floats, n_max_up_to, lanes_of=(4, 16, 64)):
     return sorted(edges)
 
 
-def part_base(n_floats, n_max, slots):
-    """Where a linked launch's term buffer starts: the step's arrays, 16-byte aligned, then the incidence list of
-    n_max + 1 offsets and 2 S entries, 16-byte aligned."""
-    return up16(coop_base(n_floats, n_max) + 4 * (n_max + 1) + 8 * slots)
-
-
 def links_binding(n_floats, n_max, slots, lanes):
-    """What decides ya::ens::whole_step_links_lds_bytes: -2 = the list does not fit (0), -1 = the shortest tile does
+    """What decides a linked all-pairs launch's LDS: -2 = the list does not fit (0), -1 = the shortest tile does
     not fit beside it (0), 4 = one lane per cell (the list's end), 0 .. 3 = the bound that cut the tile length last."""
-    base = part_base(n_floats, n_max, slots)
+    base = lds_layout(n_floats, n_max, False, slots).terms
     if base + STATIC_LDS > LDS:
         return -2
     return 4 if lanes == 1 else tile_behind(base, n_floats, n_max, lanes)[2]
 
 
-def links_lds_bytes(n_floats, n_max, slots, lanes):
-    if links_binding(n_floats, n_max, slots, lanes) < 0:
-        return 0
-    base = part_base(n_floats, n_max, slots)
-    per_partner, tile, _, _ = tile_behind(base, n_floats, n_max, lanes)
-    return base if lanes == 1 else base + tile * per_partner
-
-
-def largest_slots(n_floats, n_max, lanes=1):
-    """The largest S whose launch fits (the rule falls monotonically to 0 in S)."""
+def largest_slots(n_floats, n_max, lanes=1, keys=False):
+    """The largest S whose launch fits (the rule falls monotonically to 0 in S); None where not even S = 0 does."""
     lo, hi = 0, LDS  # fits, does not
-    assert links_lds_bytes(n_floats, n_max, lo, lanes) > 0 and links_lds_bytes(n_floats, n_max, hi, lanes) == 0
+
+    def fits(slots):
+        return lds_layout(n_floats, n_max, keys, slots, lanes).bytes > 0
+
+    if not fits(lo):
+        return None
+    assert not fits(hi)
     while hi - lo > 1:
         mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if links_lds_bytes(n_floats, n_max, mid, lanes) > 0 else (lo, mid)
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
     return lo
 
 

@@ -134,9 +134,9 @@ static Run small_run(const float* d_rests, const bool whole)
 
 int main()
 {
-    static_assert(ya::ens::whole_step_links_lds_bytes<float3>(N_MAX, 3 * N_MAX, 1) > 0, "the list of 3 protrusions per cell fits");
-    static_assert(ya::ens::whole_step_links_lds_bytes<float3>(N_MAX, 3 * N_MAX, 1) % 16 == 0, "16-byte aligned");
-    static_assert(ya::ens::whole_step_links_lds_bytes<float3>(1024, 20000, 1) == 0, "and a list beyond the LDS does not");
+    static_assert(ya::ens::lds_layout<float3, false, true>(N_MAX, 3 * N_MAX, 1).bytes > 0, "the list of 3 protrusions per cell fits");
+    static_assert(ya::ens::lds_layout<float3, false, true>(N_MAX, 3 * N_MAX, 1).bytes % 16 == 0, "16-byte aligned");
+    static_assert(ya::ens::lds_layout<float3, false, true>(1024, 20000, 1).bytes == 0, "and a list beyond the LDS does not");
     float* d_rests = on_device(rests, M);
     for (int prots_per_cell : {1, 3}) {
         Run first;

@@ -5,7 +5,7 @@
 //   * a functor that is NOT declared stateless and counts neighbours without atomics keeps one lane per cell under
 //     the default, and its counters are those of a twin that only calls take_step;
 //   * a MAKE_PT type of 8 floats leaves no room for the terms of 16 lanes at n_max = 1024: one lane per cell, still
-//     whole-step launches; the largest n_max at which 16 lanes fit comes from ya::ens::whole_step_coop_lds_bytes;
+//     whole-step launches; the largest n_max at which 16 lanes fit comes from ya::ens::lds_layout;
 //   * ONE Ensemble alternates take_steps with 16 lanes per cell with take_step carrying Links, a kernel bumping
 //     d_n[r] in between, against a twin that only calls take_step.
 // Every comparison is of bit patterns.
@@ -135,7 +135,7 @@ constexpr int largest_pt8_with_16_lanes()
 {
     int best = 0;
     for (int n_max = 1; n_max <= ya::ens::whole_step_capacity<Pt8>(); n_max++)
-        if (ya::ens::whole_step_coop_lds_bytes<Pt8>(n_max, 16) != 0) best = n_max;
+        if (ya::ens::lds_layout<Pt8, false, false>(n_max, 0, 16).bytes != 0) best = n_max;
     return best;
 }
 
@@ -274,11 +274,11 @@ int main()
     // 3. 8 floats per point
     {
         static_assert(ya::ens::whole_step_capacity<Pt8>() == 1024, "Pt8 replicas of up to 1024 cells fit");
-        static_assert(ya::ens::whole_step_coop_lds_bytes<Pt8>(1024, 16) == 0, "but not with the terms of 16 lanes");
+        static_assert(ya::ens::lds_layout<Pt8, false, false>(1024, 0, 16).bytes == 0, "but not with the terms of 16 lanes");
         constexpr int fits = largest_pt8_with_16_lanes();
         static_assert(fits > 64 && fits < 1024, "");
-        static_assert(ya::ens::whole_step_coop_tile<Pt8>(fits, 16) >= 16, "");
-        static_assert(ya::ens::whole_step_coop_lds_bytes<Pt8>(fits, 16) + ya::ens::WHOLE_STEP_STATIC_LDS <=
+        static_assert(ya::ens::lds_layout<Pt8, false, false>(fits, 0, 16).tile >= 16, "");
+        static_assert(ya::ens::lds_layout<Pt8, false, false>(fits, 0, 16).bytes + ya::ens::WHOLE_STEP_STATIC_LDS <=
                           ya::ens::LDS_PER_WORKGROUP, "");
         pt8_case(1024, 1);
         pt8_case(fits, 16);

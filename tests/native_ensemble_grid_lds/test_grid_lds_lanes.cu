@@ -172,7 +172,7 @@ constexpr int largest_n_max_with_lanes(const int lanes)
 {
     int rows = 0;
     for (int n = 1; n <= ya::ens::WHOLE_STEP_MAX_ROWS; n++)
-        if (ya::ens::grid_lds_coop_bytes<Pt8>(n, lanes) != 0) rows = n;
+        if (ya::ens::lds_layout<Pt8, true, false>(n, 0, lanes).bytes != 0) rows = n;
     return rows;
 }
 
@@ -265,13 +265,14 @@ int main()
     // 3
     {
         static_assert(ya::ens::grid_lds_capacity<Pt8>() == 1024, "");
-        static_assert(ya::ens::grid_lds_coop_bytes<Pt8>(1024, 4) == 0 && ya::ens::grid_lds_coop_bytes<Pt8>(1024, 16) == 0 &&
-                          ya::ens::grid_lds_coop_bytes<Pt8>(1024, 64) == 0,
+        static_assert(ya::ens::lds_layout<Pt8, true, false>(1024, 0, 4).bytes == 0 &&
+                          ya::ens::lds_layout<Pt8, true, false>(1024, 0, 16).bytes == 0 &&
+                          ya::ens::lds_layout<Pt8, true, false>(1024, 0, 64).bytes == 0,
             "896 bytes: no room for 16 candidates' terms");
         constexpr int largest = largest_n_max_with_lanes(16);
         static_assert(largest == 942, "tests/test_ensemble_grid_lds_lanes_abi.py names the same point");
-        static_assert(ya::ens::grid_lds_coop_tile<Pt8>(largest, 16) == 16, "the shortest tile");
-        static_assert(ya::ens::grid_lds_coop_bytes<Pt8>(largest, 16) + ya::ens::WHOLE_STEP_STATIC_LDS <= ya::ens::LDS_PER_WORKGROUP, "");
+        static_assert(ya::ens::lds_layout<Pt8, true, false>(largest, 0, 16).tile == 16, "the shortest tile");
+        static_assert(ya::ens::lds_layout<Pt8, true, false>(largest, 0, 16).bytes + ya::ens::WHOLE_STEP_STATIC_LDS <= ya::ens::LDS_PER_WORKGROUP, "");
         pt8_case(1024, 16, 1);
         pt8_case(largest, 16, 16);
         pt8_case(largest + 1, 16, 1);

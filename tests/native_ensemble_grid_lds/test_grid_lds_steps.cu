@@ -211,7 +211,7 @@ int main()
 
     constexpr int capacity = ya::ens::grid_lds_capacity<Pt8>();
     static_assert(capacity >= 256 && capacity <= ya::ens::WHOLE_STEP_MAX_ROWS, "a replica of 8-float points fits");
-    static_assert(ya::ens::grid_lds_bytes<Pt8>(capacity) + ya::ens::WHOLE_STEP_STATIC_LDS <= ya::ens::LDS_PER_WORKGROUP, "");
+    static_assert(ya::ens::lds_layout<Pt8, true, false>(capacity, 0, 1).bytes + ya::ens::WHOLE_STEP_STATIC_LDS <= ya::ens::LDS_PER_WORKGROUP, "");
     static_assert(ya::ens::grid_lds_capacity<float3>() == ya::ens::WHOLE_STEP_MAX_ROWS, "");
     pt8_case(capacity, 1);
     pt8_case(capacity + 1, 0);  // one row beyond: the 14 launches, the same bits

@@ -114,11 +114,11 @@ static Grid_run run(const float* d_strengths, const bool from_lds, const int fix
 
 int main()
 {
-    static_assert(ya::ens::grid_lds_links_bytes<float3>(N_MAX, 3 * N_MAX) > 0, "the list of 3 protrusions per cell fits");
-    static_assert(ya::ens::grid_lds_links_bytes<float3>(N_MAX, 3 * N_MAX) ==
-                      ya::ens::grid_lds_bytes<float3>(N_MAX) + ya::ens::whole_step_links_list_bytes(N_MAX, 3 * N_MAX),
+    static_assert(ya::ens::lds_layout<float3, true, true>(N_MAX, 3 * N_MAX, 1).bytes > 0, "the list of 3 protrusions per cell fits");
+    static_assert(ya::ens::lds_layout<float3, true, true>(N_MAX, 3 * N_MAX, 1).bytes ==
+                      ya::ens::lds_layout<float3, true, false>(N_MAX, 0, 1).bytes + 4 * (N_MAX + 1) + 8 * (3 * N_MAX),
         "the step's arrays, the keys, the list");
-    static_assert(ya::ens::grid_lds_links_bytes<float3>(1024, 20000) == 0, "and a list beyond the LDS does not");
+    static_assert(ya::ens::lds_layout<float3, true, true>(1024, 20000, 1).bytes == 0, "and a list beyond the LDS does not");
     static_assert(!ya::stateless_pair<float3, counting_spring, friction_w_neighbour<float3>>(), "not declared");
     float* d_strengths = on_device(strengths, M);
     for (int prots_per_cell : {1, 3}) {

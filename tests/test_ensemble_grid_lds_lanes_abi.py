@@ -8,7 +8,7 @@ runs."""
 import os
 
 import ensemble_grid_lds_lanes_support as ls
-from ensemble_support import LDS, STATIC_LDS
+from ensemble_support import LDS, STATIC_LDS, lds_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -75,8 +75,8 @@ def test_both_headers_document_the_name_and_the_getter():
     for harness in ("ensemble_grid.hip", "ensemble_grid_links.hip"):
         assert "cells.lds_step_lanes = 1;" in text("yalla_amd", "csrc", harness), "the harness keeps one lane as its default"
     engine = text("include", "ensemble_grid.cuh")
-    for piece in ("int lds_step_lanes = 0;", "int lds_step_lanes_used = 0;", "constexpr size_t grid_lds_coop_bytes(",
-                  "constexpr size_t grid_lds_links_coop_bytes(", "constexpr int grid_lds_lanes_for(",
+    for piece in ("int lds_step_lanes = 0;", "int lds_step_lanes_used = 0;", "lds_layout<Pt, true, LINKED>(n_max, links.slots_per_replica, LANES)",
+                  "const int tile = layout.tile;", "constexpr int grid_lds_lanes_for(",
                   "void grid_lds_walk_coop(", "int LANES = 1>\n__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(",
                   "int LANES = 1>\n__global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked("):
         assert piece in engine, piece
@@ -85,37 +85,39 @@ def test_both_headers_document_the_name_and_the_getter():
 
 def test_the_restated_rule_agrees_with_what_the_comments_quote():
     """include/yalla_ensemble_grid.h: "a 7-float point at n_max = 1024 with 4 lanes, an 8-float point there with any";
-    include/ensemble_grid.cuh: "an 8-float point's 1024 rows leave 896 bytes; a 7-float point's leave 18320: room for
+    include/ensemble.cuh (ya::ens::lds_layout): "an 8-float point's 1024 rows and keys leave 896 bytes; a 7-float point's leave 18320: room for
     16 and 64 lanes, none for 4"; the issue of the rule: tile of candidates, 32 KiB budget, minimum 16."""
     assert "a 7-float\n * point at n_max = 1024 with 4 lanes, an 8-float point there with any" in text(
         "include", "yalla_ensemble_grid.h")
-    assert "a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4" in text("include", "ensemble_grid.cuh")
-    assert LDS - STATIC_LDS - ls.coop_base(8, 1024) == 896
-    assert LDS - STATIC_LDS - ls.coop_base(7, 1024) == 18320
-    assert [ls.coop_bytes(8, 1024, lanes) for lanes in ls.LANES] == [0, 0, 0]
-    assert ls.coop_bytes(7, 1024, 4) == 0 and ls.coop_tile(7, 1024, 16) == 24 and ls.coop_tile(7, 1024, 64) == 104
+    assert "a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4" in text("include", "ensemble.cuh")
+    assert LDS - STATIC_LDS - lds_layout(8, 1024, True).terms == 896
+    assert LDS - STATIC_LDS - lds_layout(7, 1024, True).terms == 18320
+    assert [lds_layout(8, 1024, True, lanes=lanes).bytes for lanes in ls.LANES] == [0, 0, 0]
+    assert lds_layout(7, 1024, True, lanes=4).bytes == 0
+    assert lds_layout(7, 1024, True, lanes=16).tile == 24 and lds_layout(7, 1024, True, lanes=64).tile == 104
     for n_floats in (3, 4, 5):
-        assert all(ls.coop_bytes(n_floats, 1024, lanes) > 0 for lanes in ls.LANES)
+        assert all(lds_layout(n_floats, 1024, True, lanes=lanes).bytes > 0 for lanes in ls.LANES)
     # a tile is a multiple of 4 candidates, 16 at the least, 256 at the most, within the budget unless that is the 16
     for n_floats in (3, 4, 5, 7, 8):
         for lanes in ls.LANES:
             per_candidate = (256 // lanes) * (n_floats + 4) * 4
             for n_max in range(1, 1025):
-                tile, total = ls.coop_tile(n_floats, n_max, lanes), ls.coop_bytes(n_floats, n_max, lanes)
+                layout = lds_layout(n_floats, n_max, True, lanes=lanes)
+                tile, total = layout.tile, layout.bytes
                 if tile == 0:
-                    assert total == 0 and ls.coop_base(n_floats, n_max) + STATIC_LDS + 16 * per_candidate > LDS
+                    assert total == 0 and lds_layout(n_floats, n_max, True).terms + STATIC_LDS + 16 * per_candidate > LDS
                     continue
                 assert tile % 4 == 0 and min(16, -(-n_max // 4) * 4) <= tile <= 256
-                assert ls.coop_base(n_floats, n_max) % 16 == 0
+                assert lds_layout(n_floats, n_max, True).terms % 16 == 0
                 assert tile == 16 or tile * per_candidate <= 32 * 1024
-                assert total == ls.coop_base(n_floats, n_max) + tile * per_candidate and total + STATIC_LDS <= LDS
+                assert total == lds_layout(n_floats, n_max, True).terms + tile * per_candidate and total + STATIC_LDS <= LDS
     # the engine's choice for stateless functors: 16 lanes up to 32 cells, 4 up to 64, else 1 (the measured table)
     assert [ls.lanes_for(n) for n in (1, 4, 5, 16, 17, 32, 33, 64, 65, 1024)] == [16, 16, 16, 16, 16, 16, 4, 4, 1, 1]
     engine = text("include", "ensemble_grid.cuh")
     assert "if (n_max <= 32) return 16;\n    if (n_max <= 64) return 4;\n    return 1;" in engine
     # with links, the list lies in between: two slots per cell at 1024 rows of 3 floats cost 4100 + 16384 bytes
-    assert ls.links_coop_base(3, 1024, 2048) - ls.coop_base(3, 1024) == 20496
-    assert ls.links_coop_bytes(8, 1024, 0, 64) == 0  # (no room for the list itself)
+    assert lds_layout(3, 1024, True, 2048).terms - lds_layout(3, 1024, True).terms == 20496
+    assert lds_layout(8, 1024, True, 0, 64).bytes == 0  # (no room for the list itself)
 
 
 # The n_max either side of every point where another term of the rule starts to decide (0 = n_max, 1 = the longest
@@ -143,6 +145,6 @@ def test_the_points_where_another_term_of_the_rule_starts_to_decide():
     assert [(ls.coop_binding(8, n, 4), ls.coop_binding(8, n + 1, 4)) for n in (16, 679)] == [(0, 2), (2, -1)]
     assert [(ls.coop_binding(8, n, 16), ls.coop_binding(8, n + 1, 16)) for n in (40, 810, 942)] == [(0, 2), (2, 3), (3, -1)]
     assert [(ls.coop_binding(8, n, 64), ls.coop_binding(8, n + 1, 64)) for n in (168, 800, 1008)] == [(0, 2), (2, 3), (3, -1)]
-    assert ls.coop_tile(8, 942, 16) == 16 and ls.coop_tile(8, 1008, 64) == 16
+    assert lds_layout(8, 942, True, lanes=16).tile == 16 and lds_layout(8, 1008, True, lanes=64).tile == 16
     # for three floats only n_max, the budget and the longest tile ever decide
     assert {ls.coop_binding(3, n, lanes) for n in range(1, 1025) for lanes in ls.LANES} == {0, 1, 2}

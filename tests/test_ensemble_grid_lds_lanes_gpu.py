@@ -12,7 +12,7 @@ from ensemble_grid_links_support import N_FLOATS as LINKED_N_FLOATS
 from ensemble_grid_links_support import Run, box_rows as linked_box_rows, no_nan, random_links, same
 from ensemble_grid_lds_lanes_support import LANES, Lanes
 from ensemble_grid_lds_support import UNUSED
-from ensemble_support import DT, FRICTION_MODELS, bits, seeded_rows
+from ensemble_support import DT, FRICTION_MODELS, bits, lds_layout, seeded_rows
 from test_ensemble_grid_gpu import MODELS
 from test_ensemble_grid_lds_lanes_abi import LINKED_RULE_POINTS, RULE_POINTS
 from test_ensemble_grid_lds_steps_gpu import (N_FLOATS, SMALL_DT, assert_the_inputs_can_show_a_wrong_order,
@@ -115,7 +115,7 @@ def test_one_cube_of_300_cells_isolated_cells_and_cells_that_all_miss_each_other
     rows = [seeded_rows(n_floats, 200, 6), dense, lonely, seeded_rows(n_floats, 64, 7)]
     counts = [len(X) for X in rows]
     assert len(np.unique(ge.cube_of(dense[:, :3], 1.0, 10))) == 1
-    assert all(ls.coop_tile(n_floats, 300, lanes) < 300 for lanes in LANES)  # (more than one tile per row)
+    assert all(lds_layout(n_floats, 300, True, lanes=lanes).tile < 300 for lanes in LANES)  # (more than one tile per row)
     d2, _ = ge.d2_of(lonely[:, None, :3], lonely[None, :, :3])
     assert (d2 + 9 * np.eye(125) >= 4).all()
     run = Lanes(model, counts, 300, 10, rows=rows)
@@ -401,7 +401,7 @@ def test_linked_launches_either_side_of_the_points_of_the_rule(model):
     for n_max in points:
         slots = 2 * n_max
         counts, rows, links = linked_case(model, n_max, seed=n_max)
-        fits = ls.grid_links_lds_bytes(n_floats, n_max, slots) > 0
+        fits = lds_layout(n_floats, n_max, True, slots).bytes > 0
         want, launches, used = linked_state(model, rows, n_max, slots, links, 9, 2, lds_steps=-1)
         assert launches == 0 and used == 0
         for setting in (1,) + LANES:

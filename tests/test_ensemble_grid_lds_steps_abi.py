@@ -8,8 +8,8 @@ import os
 
 import numpy as np
 import pytest
-from ensemble_grid_lds_support import grid_lds_bytes, grid_lds_capacity
-from ensemble_support import LDS, STATIC_LDS
+from ensemble_grid_lds_support import grid_lds_capacity
+from ensemble_support import LDS, STATIC_LDS, lds_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,7 +52,7 @@ def test_the_header_documents_the_settings_and_the_count():
 
 def test_the_engine_header_defines_the_pieces():
     engine = text("include", "ensemble_grid.cuh")
-    for piece in ("void grid_lds_steps(", "constexpr size_t grid_lds_bytes(", "constexpr int grid_lds_capacity()",
+    for piece in ("void grid_lds_steps(", "lds_layout<Pt, true, LINKED>(", "constexpr int grid_lds_capacity()",
                   "inline bool lds_steps_pay(const int n_replicas, const int n_max, const int n_cubes)",
                   "int lds_steps = 0;", "int lds_steps_max = 256;", "long lds_step_launches = 0;",
                   "void take_steps(float dt, int n_steps"):
@@ -60,6 +60,8 @@ def test_the_engine_header_defines_the_pieces():
     # the step in LDS exists once: the all-pairs kernels and the grid kernel call the same function
     shared = text("include", "ensemble.cuh")
     assert shared.count("void whole_steps_in_lds(") == 1 and engine.count("whole_steps_in_lds<Pt>(") == 1
+    # ... and so does the LDS rule, for both forms
+    assert shared.count("constexpr Lds_layout lds_layout(") == 1 and "constexpr Lds_layout" not in engine
     assert shared.count("ya::heun_row(local, dt, fix_first") == 1 and "heun_row" not in engine
 
 
@@ -67,9 +69,9 @@ def test_the_lds_rule_restated():
     """3-, 5-, 7- and 8-float points: all of them fit 1024 rows, the 8-float one with 896 bytes to spare."""
     for n_floats in (3, 4, 5, 7, 8):
         assert grid_lds_capacity(n_floats) == 1024
-    assert LDS - STATIC_LDS - grid_lds_bytes(8, 1024) == 896
-    assert grid_lds_bytes(3, 600) - grid_lds_bytes(3, 514) == 86 * 60  # (both lay out 1024 keys)
-    assert grid_lds_bytes(3, 514) - grid_lds_bytes(3, 512) == 2 * 60 + 8 * 512  # (512 rows lay out 512)
+    assert LDS - STATIC_LDS - lds_layout(8, 1024, keys=True).bytes == 896
+    assert lds_layout(3, 600, keys=True).bytes - lds_layout(3, 514, keys=True).bytes == 86 * 60  # (both lay out 1024 keys)
+    assert lds_layout(3, 514, keys=True).bytes - lds_layout(3, 512, keys=True).bytes == 2 * 60 + 8 * 512  # (512 rows lay out 512)
 
 
 class StandInLibrary:

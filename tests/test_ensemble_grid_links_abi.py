@@ -6,10 +6,10 @@ import ctypes
 import os
 
 import pytest
-from ensemble_grid_links_support import MODELS, N_FLOATS, grid_links_lds_bytes, largest_grid_slots
-from ensemble_grid_lds_support import grid_lds_bytes, grid_lds_capacity
+from ensemble_grid_links_support import MODELS, N_FLOATS
+from ensemble_grid_lds_support import grid_lds_capacity
 from ensemble_support import (LDS, ROOT, STATIC_LDS, check_abi, check_models_name_bounds,
-                              check_only_the_c_abi_is_exported)
+                              check_only_the_c_abi_is_exported, largest_slots, lds_layout)
 
 LIB = os.path.join(ROOT, "yalla_amd", "libyalla_ensemble_grid_links.so")
 
@@ -81,11 +81,11 @@ def test_the_restated_rule():
         assert grid_lds_capacity(n_floats) == 1024
         for n_max in (1, 16, 100, 256, 512, 1023):
             for slots in (0, 1, n_max, 3 * n_max):
-                got = grid_links_lds_bytes(n_floats, n_max, slots)
-                whole = grid_lds_bytes(n_floats, n_max) + 4 * (n_max + 1) + 8 * slots
+                got = lds_layout(n_floats, n_max, True, slots).bytes
+                whole = lds_layout(n_floats, n_max, keys=True).bytes + 4 * (n_max + 1) + 8 * slots
                 assert got == (whole if whole + STATIC_LDS <= LDS else 0)
                 assert (got > 0) == (n_floats < 8 or n_max < 1023)  # (these shapes: only the widest point runs out)
-                assert got % 4 == 0 and grid_lds_bytes(n_floats, n_max) % 8 == 0
+                assert got % 4 == 0 and lds_layout(n_floats, n_max, keys=True).bytes % 8 == 0
 
 
 @pytest.mark.parametrize("model", MODELS)
@@ -96,17 +96,17 @@ def test_lds_bytes_is_the_rule_and_zero_exactly_where_it_should_be(model):
     n_floats = N_FLOATS[model]
     for n_max in (1, 2, 63, 64, 65, 255, 256, 257, 512, 513, 1023, 1024):
         for slots in (0, 1, n_max, 3 * n_max):
-            assert LinkedGridEnsemble.lds_bytes(model, n_max, slots) == grid_links_lds_bytes(n_floats, n_max, slots), \
+            assert LinkedGridEnsemble.lds_bytes(model, n_max, slots) == lds_layout(n_floats, n_max, True, slots).bytes, \
                 (n_max, slots)
     for n_max in (1, 1023, 1024):
-        fits = largest_grid_slots(n_floats, n_max)
+        fits = largest_slots(n_floats, n_max, keys=True)
         if fits is None:  # not even the offsets of a list of no slots
             assert n_floats == 8 and n_max >= 1023
             assert LinkedGridEnsemble.lds_bytes(model, n_max, 0) == 0
             continue
-        room = LDS - STATIC_LDS - grid_lds_bytes(n_floats, n_max) - 4 * (n_max + 1)
+        room = LDS - STATIC_LDS - lds_layout(n_floats, n_max, keys=True).bytes - 4 * (n_max + 1)
         assert fits == room // 8 and 0 <= room - 8 * fits < 8
-        want = grid_lds_bytes(n_floats, n_max) + 4 * (n_max + 1) + 8 * fits
+        want = lds_layout(n_floats, n_max, keys=True).bytes + 4 * (n_max + 1) + 8 * fits
         assert LinkedGridEnsemble.lds_bytes(model, n_max, fits) == want > 0, (n_max, fits)
         assert LinkedGridEnsemble.lds_bytes(model, n_max, fits + 1) == 0, (n_max, fits + 1)
         assert LinkedGridEnsemble.lds_bytes(model, n_max, 2 ** 31 - 1) == 0
@@ -117,15 +117,15 @@ def test_an_eight_float_point_at_1024_rows_has_no_room_for_a_list():
     do not fit, so the rule is 0 for S = 0 (and every S); at 1023 rows the keys are as many and the arrays one row of
     140 bytes shorter, no room either.  The GPU tests pick their shapes by this: relu_cell8_links at n_max = 1024 never steps from LDS."""
     from yalla_amd.ensemble import LinkedGridEnsemble
-    assert LDS - STATIC_LDS - grid_lds_bytes(8, 1024) == 896 < 4 * 1025
-    assert grid_links_lds_bytes(8, 1024, 0) == 0
+    assert LDS - STATIC_LDS - lds_layout(8, 1024, keys=True).bytes == 896 < 4 * 1025
+    assert lds_layout(8, 1024, True, 0).bytes == 0
     assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", 1024, 0) == 0
     assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", 1024, 1024) == 0
-    assert 896 < LDS - STATIC_LDS - grid_lds_bytes(8, 1023) <= 896 + 140 < 4 * 1024
+    assert 896 < LDS - STATIC_LDS - lds_layout(8, 1023, keys=True).bytes <= 896 + 140 < 4 * 1024
     assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", 1023, 0) == 0
     # the largest n_max of 8 floats with room for a list of one slot per cell, found on the CPU
-    n_max = max(n for n in range(1, 1025) if grid_links_lds_bytes(8, n, n) > 0)
-    assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", n_max, n_max) == grid_links_lds_bytes(8, n_max, n_max) > 0
+    n_max = max(n for n in range(1, 1025) if lds_layout(8, n, True, n).bytes > 0)
+    assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", n_max, n_max) == lds_layout(8, n_max, True, n_max).bytes > 0
     assert LinkedGridEnsemble.lds_bytes("relu_cell8_links", n_max + 1, n_max + 1) == 0
     # the 7-float and smaller points keep room at 1024 rows
     for model in MODELS[:-1]:

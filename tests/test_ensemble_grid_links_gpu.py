@@ -12,10 +12,9 @@ import functools
 
 import numpy as np
 import pytest
-from ensemble_grid_links_support import (MODELS, N_FLOATS, Pair, Run, box_rows, grid_links_lds_bytes,
-                                         largest_grid_slots, no_nan, random_links, same)
+from ensemble_grid_links_support import MODELS, N_FLOATS, Pair, Run, box_rows, no_nan, random_links, same
 from ensemble_grid_lds_support import UNUSED
-from ensemble_support import DT, bits, same_grid, seeded_rows
+from ensemble_support import DT, bits, largest_slots, lds_layout, same_grid, seeded_rows
 
 from yalla_amd.ensemble import LinkedGridEnsemble, YallaError
 from yalla_amd.solution import Solution
@@ -35,7 +34,7 @@ def chain_shape(model):
     """(n_max, counts): n_max = S = 1024 where a list of 1024 slots fits beside the keys; for the 8-float point the
     largest n_max with room for a list of n_max slots (found here, on the CPU), the two largest counts cut to it."""
     n_floats = N_FLOATS[model]
-    n_max = max(n for n in range(1, 1025) if grid_links_lds_bytes(n_floats, n, n) > 0)
+    n_max = max(n for n in range(1, 1025) if lds_layout(n_floats, n, True, n).bytes > 0)
     assert (n_max == 1024) == (n_floats < 8) and n_max > 900
     return n_max, [n if n < 1023 else n_max - (1024 - n) for n in CHAIN_COUNTS]
 
@@ -132,7 +131,7 @@ def test_chains_bit_for_bit(model):
 def test_an_eight_float_point_of_1024_rows_never_steps_from_lds():
     """relu_cell8_links at n_max = 1024: the rule gives 0 even for a list of no slots, so lds_steps = 1 runs the 14
     launches -- 0 launches counted, the twin's bits -- whatever S is."""
-    assert grid_links_lds_bytes(8, 1024, 0) == 0 and LinkedGridEnsemble.lds_bytes("relu_cell8_links", 1024, 0) == 0
+    assert lds_layout(8, 1024, True, 0).bytes == 0 and LinkedGridEnsemble.lds_bytes("relu_cell8_links", 1024, 0) == 0
     rows = [box_rows(n, 8, CHAIN_GRID, 40 + r) for r, n in enumerate([1024, 70])]
     for slots in (0, 64):
         pair = Pair("relu_cell8_links", rows, 1024, slots, [random_links(len(X), slots, 3) for X in rows], CHAIN_GRID)
@@ -327,14 +326,14 @@ def test_seven_steps_split_into_launches_equal_one_call(lds_steps_max):
 def test_the_largest_list_that_fits_and_one_beyond():
     """n_max = 1024 of float3: the largest S the rule admits -- the workgroup's whole LDS -- runs from LDS; one slot
     more is the 14-launch loop with link_forces_ordered, 0 launches counted; both give the twin's bits."""
-    fits = largest_grid_slots(3, 1024)
-    assert grid_links_lds_bytes(3, 1024, fits) > 0 and grid_links_lds_bytes(3, 1024, fits + 1) == 0
+    fits = largest_slots(3, 1024, keys=True)
+    assert lds_layout(3, 1024, True, fits).bytes > 0 and lds_layout(3, 1024, True, fits + 1).bytes == 0
     counts = [1024, 500]
     rows = [box_rows(n, 3, CHAIN_GRID, 80 + r) for r, n in enumerate(counts)]
     links = [random_links(n, fits, 20 + r) for r, n in enumerate(counts)]  # every slot in use: ten links per cell
     states = []
     for slots, launches in ((fits, 1), (fits + 1, 0)):
-        assert LinkedGridEnsemble.lds_bytes("links", 1024, slots) == grid_links_lds_bytes(3, 1024, slots)
+        assert LinkedGridEnsemble.lds_bytes("links", 1024, slots) == lds_layout(3, 1024, True, slots).bytes
         pair = Pair("links", rows, 1024, slots, links, CHAIN_GRID, strength=0.01)
         try:
             states.append(pair.step(SMALL_DT, 2, launches, ("S", slots)))

@@ -1,13 +1,13 @@
 """libyalla_ensemble_links.so (include/yalla_ensemble_links.h) loads without a GPU, exports exactly the C ABI its
 header declares and the ctypes table mirrors, refuses what it does not know, and answers ya_lens_lds_bytes -- host
-arithmetic only -- with ya::ens::whole_step_links_lds_bytes, held here against a Python restatement of the rule (no
+arithmetic only -- with ya::ens::lds_layout's bytes, held here against a Python restatement of the rule (no
 compute calls here)."""
 import ctypes
 import os
 
 import pytest
 from ensemble_support import (LDS, LINKED_MODELS, ROOT, STATIC_LDS, check_abi, check_models_name_bounds,
-                              check_only_the_c_abi_is_exported, largest_slots, links_lds_bytes, up16)
+                              check_only_the_c_abi_is_exported, largest_slots, lds_layout, up16)
 from ensemble_support import LINKED_N_FLOATS as N_FLOATS
 from ensemble_support import links_binding as binding
 
@@ -58,24 +58,24 @@ def test_unknown_models_and_bad_arguments_are_refused_before_the_device_is_touch
         LinkedEnsemble.lds_bytes("links", 100, 10, 2)
 
 
-# ---- ya::ens::whole_step_links_lds_bytes<Pt>(n_max, S, lanes) against its restatement (ensemble_support) -------------
+# ---- ya::ens::lds_layout<Pt, false, true>(n_max, S, lanes).bytes against its restatement (ensemble_support) ---------
 def test_the_restated_rule():
     """What the header promises of the rule, on the restatement: 16-byte aligned, within the workgroup's LDS, the
     list's 4 (n_max + 1) + 8 S bytes behind the step's arrays, a tile of at least 4 partners where lanes fit."""
     for n_floats in (3, 4, 5):
         for n_max in (1, 16, 100, 256, 1024):
             for slots in (0, 1, n_max, 3 * n_max):
-                one = links_lds_bytes(n_floats, n_max, slots, 1)
+                one = lds_layout(n_floats, n_max, False, slots, 1).bytes
                 assert one > 0 and one % 16 == 0 and one + STATIC_LDS <= LDS
                 assert 0 <= one - up16(n_max * (16 * n_floats + 12) + n_floats * 1040) - 4 * (n_max + 1) - 8 * slots < 16
                 for lanes in (4, 16, 64):
-                    many = links_lds_bytes(n_floats, n_max, slots, lanes)
+                    many = lds_layout(n_floats, n_max, False, slots, lanes).bytes
                     assert many == 0 or (many % 16 == 0 and many + STATIC_LDS <= LDS
                                          and (many - one) // ((256 // lanes) * (n_floats + 4) * 4) >= 4)
     # Po_cell at the capacity with three slots per cell: the list fits, the terms of 4 lanes do not, those of 16 do
-    assert links_lds_bytes(5, 1024, 3072, 1) > 0 and links_lds_bytes(5, 1024, 3072, 4) == 0
-    assert links_lds_bytes(5, 1024, 3072, 16) > 0
-    assert links_lds_bytes(3, 1024, largest_slots(3, 1024) + 1, 1) == 0
+    assert lds_layout(5, 1024, False, 3072, 1).bytes > 0 and lds_layout(5, 1024, False, 3072, 4).bytes == 0
+    assert lds_layout(5, 1024, False, 3072, 16).bytes > 0
+    assert lds_layout(3, 1024, False, largest_slots(3, 1024) + 1, 1).bytes == 0
 
 
 @pytest.mark.parametrize("model", ["links", "links4", "relu_po_links"])  # (one per point type)
@@ -104,7 +104,7 @@ def test_lds_bytes_is_the_rule(model):
                     before = now
     seen = set()
     for n_max, slots, lanes in sorted(points):
-        want = links_lds_bytes(n_floats, n_max, slots, lanes)
+        want = lds_layout(n_floats, n_max, False, slots, lanes).bytes
         assert LinkedEnsemble.lds_bytes(model, n_max, slots, lanes) == want, (n_max, slots, lanes)
         seen.add(binding(n_floats, n_max, slots, lanes))
     # every term decided somewhere (Po_cell's budget holds fewer partners than the longest tile, whatever the lanes)

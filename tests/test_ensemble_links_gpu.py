@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ensemble_support import DT, bits, largest_slots, links_lds_bytes, seeded_rows  # noqa: E402
+from ensemble_support import DT, bits, largest_slots, lds_layout, seeded_rows  # noqa: E402
 from ensemble_support import LINKED_MODELS as MODELS  # noqa: E402
 from ensemble_support import LINKED_N_FLOATS as N_FLOATS  # noqa: E402
 from links_support import reference_linked_steps  # noqa: E402
@@ -206,13 +206,13 @@ def test_hubs_bit_for_bit(model, lanes):
     Po_cell with 4 lanes: the term buffer does not fit beside the list, so the launches run with one lane."""
     slots = 3 * 1024
     n_floats = N_FLOATS[model]
-    assert links_lds_bytes(n_floats, 1024, slots, 1) > 0
+    assert lds_layout(n_floats, 1024, False, slots, 1).bytes > 0
     want = hub_reference(model, slots)
     run = hub_run(model, slots, whole_steps=1, whole_step_lanes=lanes)
     try:
         run.ens.take_step(DT, 3)
         assert run.ens.whole_step_launches == 1
-        fits = links_lds_bytes(n_floats, 1024, slots, lanes) > 0
+        fits = lds_layout(n_floats, 1024, False, slots, lanes).bytes > 0
         assert fits == (not (model == "relu_po_links" and lanes == 4))  # the lanes fallback to 1
         assert run.ens.whole_step_lanes_used == (lanes if fits else 1)
         same(want, run.state(), "hub")
@@ -427,7 +427,7 @@ def test_the_largest_list_that_fits_and_one_beyond():
     """n_max = 1024 of float3: the largest S the rule admits runs whole; one slot more is the six-launch loop with
     link_forces_ordered -- 0 launches -- and the same bits."""
     fits = largest_slots(3, 1024)
-    assert links_lds_bytes(3, 1024, fits, 1) > 0 and links_lds_bytes(3, 1024, fits + 1, 1) == 0
+    assert lds_layout(3, 1024, False, fits, 1).bytes > 0 and lds_layout(3, 1024, False, fits + 1, 1).bytes == 0
     counts = [1024, 500]
     # every slot in use: eleven links per cell, all of them counted
     links = [random_links(n, fits, 20 + r) for r, n in enumerate(counts)]
@@ -435,7 +435,7 @@ def test_the_largest_list_that_fits_and_one_beyond():
     for slots, launches in ((fits, 1), (fits + 1, 0)):
         run = Run("links", counts, 1024, slots, links, seed=8, strength=0.01, whole_steps=1, whole_step_lanes=16)
         try:
-            assert LinkedEnsemble.lds_bytes("links", 1024, slots, 1) == links_lds_bytes(3, 1024, slots, 1)
+            assert LinkedEnsemble.lds_bytes("links", 1024, slots, 1) == lds_layout(3, 1024, False, slots, 1).bytes
             run.ens.take_step(DT, 2)
             assert run.ens.whole_step_launches == launches
             if launches:  # (no room for the terms of 16 lanes beside that list)

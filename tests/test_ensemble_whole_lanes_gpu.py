@@ -8,8 +8,8 @@ import functools
 
 import numpy as np
 import pytest
-from ensemble_support import (DT, LDS, MIN_TILE, STATIC_LDS, WHOLE, Twins, bits, capacity, coop_lds_bytes,
-                              coop_rule_edges, coop_tile, seeded_rows)
+from ensemble_support import (DT, LDS, MIN_TILE, STATIC_LDS, WHOLE, Twins, bits, capacity, coop_rule_edges,
+                              lds_layout, seeded_rows)
 
 from yalla_amd.ensemble import Ensemble, YallaError
 from yalla_amd.solution import Solution
@@ -24,7 +24,7 @@ N_FLOATS = {"springs": 3, "clipped": 3, "fading": 3, "relu": 3, "relu_po": 5, "o
 
 
 def rule_edges(n_floats, n_max_up_to):
-    """Every n_max either side of a point where another term of ya::ens::whole_step_coop_lds_bytes' rule (restated in
+    """Every n_max either side of a point where another term of ya::ens::lds_layout's term-buffer rule (restated in
     ensemble_support) starts to decide, for any of LANES."""
     return coop_rule_edges(n_floats, n_max_up_to, LANES)
 
@@ -34,10 +34,10 @@ def test_the_restated_rule():
     for n_floats in (3, 4, 5, 8):
         for lanes in LANES:
             for n_max in (1, 16, 17, 64, 300, capacity(n_floats)):
-                tile = coop_tile(n_floats, n_max, lanes)
+                tile = lds_layout(n_floats, n_max, lanes=lanes).tile
                 assert tile % 4 == 0 and (tile == 0 or tile >= min(MIN_TILE, -(-n_max // 4) * 4))
-                assert coop_lds_bytes(n_floats, n_max, lanes) + STATIC_LDS <= LDS
-    assert coop_tile(8, 1024, 16) == 0 and coop_tile(8, 1024, 64) > 0  # (about 9 KiB are left there)
+                assert lds_layout(n_floats, n_max, lanes=lanes).bytes + STATIC_LDS <= LDS
+    assert lds_layout(8, 1024, lanes=16).tile == 0 and lds_layout(8, 1024, lanes=64).tile > 0  # (about 9 KiB are left there)
     assert rule_edges(3, 1024) == [16, 17, 72, 73, 256, 257]
     assert rule_edges(5, 1024) == [16, 17, 56, 57, 224, 225]
 
@@ -99,7 +99,7 @@ def test_ragged_counts_bit_for_bit(model, lanes, case):
     start, v0, six_X, six_v, singles = ragged_reference(model, case)
     steps = 1 if case == "1 step" else 5
     with Ensemble(model, len(RAGGED), 1024) as ens:
-        assert ens.n_floats == N_FLOATS[model] and coop_tile(ens.n_floats, 1024, lanes) >= MIN_TILE
+        assert ens.n_floats == N_FLOATS[model] and lds_layout(ens.n_floats, 1024, lanes=lanes).tile >= MIN_TILE
         ens.set_param("whole_steps", 1)
         ens.set_param("whole_step_lanes", lanes)
         ens.h_X[:] = start

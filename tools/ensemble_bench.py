@@ -476,10 +476,10 @@ def main_grid_links(args):
                       "max_ratio_lds_256": max(r["ratio_ordered_lds_256_steps_per_launch"] for r in rows)}))
 
 
-def measure_whole_lanes(m, n, lanes_list, window, repeats):
+def measure_whole_lanes(m, n, lanes_list, window, repeats, steps_per_launch=256):
     b = Together(m, n)
     try:
-        b.whole(1, 256)
+        b.whole(1, steps_per_launch)
         ks = {}
         for lanes in lanes_list:
             b.whole_lanes(lanes)
@@ -502,14 +502,14 @@ def measure_whole_lanes(m, n, lanes_list, window, repeats):
     return row
 
 
-def measure_lds_lanes(m, n, lanes_list, window, repeats):
+def measure_lds_lanes(m, n, lanes_list, window, repeats, steps_per_launch=256):
     """One GridEnsemble: launches that step from LDS (up to 256 steps each) with every lds_step_lanes setting of
     lanes_list, and the 14-launch step of the same object, alternated."""
     b = Together(m, n)
     settings = [("lanes_%d" % lanes, 1, lanes) for lanes in lanes_list] + [("fourteen_launches", -1, 1)]
 
     def apply(lds_steps, lanes):
-        b.lds(lds_steps, 256)
+        b.lds(lds_steps, steps_per_launch)
         b.ens.set_param("lds_step_lanes", lanes)
     try:
         ks, used = {}, {}
@@ -555,7 +555,7 @@ def main_lds_lanes(args):
     rows = []
     keys = ["lanes_%d" % lanes for lanes in lanes_list] + ["fourteen_launches"]
     for m, n in shapes:
-        rows.append(measure_lds_lanes(m, n, lanes_list, args.window, args.repeats))
+        rows.append(measure_lds_lanes(m, n, lanes_list, args.window, args.repeats, args.steps_per_launch))
         r = rows[-1]
         print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"{key}: {r[key]['us_per_step']:9.2f}" for key in keys)
               + " us/step   ratios " + " ".join(f"{r['ratio_' + key]:.2f}" for key in keys)
@@ -584,7 +584,7 @@ def main_whole_lanes(args):
         run.close()
     rows = []
     for m, n in shapes:
-        rows.append(measure_whole_lanes(m, n, lanes_list, args.window, args.repeats))
+        rows.append(measure_whole_lanes(m, n, lanes_list, args.window, args.repeats, args.steps_per_launch))
         r = rows[-1]
         print(f"M {m:5d}  n {n:5d}   " + "  ".join(f"L{lanes}: {r[f'lanes_{lanes}']['us_per_step']:9.2f}" for lanes in lanes_list)
               + " us/step   ratios " + " ".join(f"{r[f'ratio_lanes_{lanes}']:.2f}" for lanes in lanes_list)
@@ -609,6 +609,9 @@ def main():
     ap.add_argument("--trace-shape", type=int, nargs=2, metavar=("M", "N"), default=None,
                     help="only step one Ensemble of this shape --steps times (for a kernel trace)")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps-per-launch", type=int, default=256,
+                    help="with --whole-step-lanes or --lds-step-lanes: steps_per_launch / lds_steps_max of the launches "
+                         "(1: what a launch costs beside its steps)")
     ap.add_argument("--solver", choices=("tile", "grid", "gabriel"), default="tile")
     ap.add_argument("--whole-steps", action="store_true",
                     help="whole-step launches against the six-launch step of the same Ensemble (tile solver only)")

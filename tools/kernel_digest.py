@@ -49,6 +49,8 @@ def disassembly(path):
         if m:
             symbol = m.group(1)
             text[symbol] = []
+        elif symbol is not None and line.strip() == "...":
+            continue  # zero padding up to the next symbol's alignment: it comes and goes with the kernel's neighbours
         elif symbol is not None and line.startswith("\t"):
             # "\tinstruction operands   // 0000000012A4: ENCODING ..." -> without the address
             line = re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line).rstrip()

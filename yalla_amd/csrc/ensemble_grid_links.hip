@@ -98,7 +98,7 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
 template<typename Pt>
 long lds_bytes_of(int n_max, int slots)
 {
-    return (long)ya::ens::grid_lds_links_bytes<Pt>(n_max, slots);
+    return (long)ya::ens::lds_layout<Pt, true, true>(n_max, slots, 1).bytes;
 }
 
 // (name, point type, pairwise force, friction)

@@ -84,7 +84,7 @@ struct Sim : public Tile_replicas_of<Ensemble<Pt>, Base> {
 template<typename Pt>
 long lds_bytes_of(int n_max, int slots, int lanes)
 {
-    return (long)ya::ens::whole_step_links_lds_bytes<Pt>(n_max, slots, lanes);
+    return (long)ya::ens::lds_layout<Pt, false, true>(n_max, slots, lanes).bytes;
 }
 
 // (name, point type, pairwise force, friction)

@@ -346,7 +346,7 @@ class LinkedEnsemble(Ensemble):
 
     @staticmethod
     def lds_bytes(model, n_max, slots_per_replica, lanes=1, lib=None):
-        """ya::ens::whole_step_links_lds_bytes for the model's point type: the dynamic LDS of a linked whole-step
+        """ya::ens::lds_layout<Pt, false, true>(...).bytes for the model's point type: the dynamic LDS of a linked whole-step
         launch, 0 where there is no room.  Needs no GPU."""
         lib = lib if lib is not None else _ffi.linked_ensemble_lib()
         code = lib.ya_lens_lds_bytes(model.encode(), int(n_max), int(slots_per_replica), int(lanes))
@@ -395,7 +395,7 @@ class LinkedGridEnsemble(GridEnsemble):
 
     @staticmethod
     def lds_bytes(model, n_max, slots_per_replica, lib=None):
-        """ya::ens::grid_lds_links_bytes for the model's point type: the dynamic LDS of a linked launch that steps
+        """ya::ens::lds_layout<Pt, true, true>(...).bytes for the model's point type: the dynamic LDS of a linked launch that steps
         from LDS, 0 where there is no room.  Needs no GPU."""
         lib = lib if lib is not None else _ffi.linked_grid_ensemble_lib()
         code = lib.ya_glens_lds_bytes(model.encode(), int(n_max), int(slots_per_replica))
