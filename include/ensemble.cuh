@@ -50,7 +50,7 @@
 // same bits as the six-launch step with ya::ens::link_forces_ordered as its generic force.
 //
 // Ensemble<Pt, Gabriel_solver> (ensemble_gabriel.cuh, included after it) is the same for M Gabriel_solver systems,
-// on the grid form's build.
+// on the grid form's build; its take_steps steps from LDS too (ya::ens::gabriel_lds_steps).
 //
 // Not here ("Ensembles"): the fast-arithmetic tier, graph capture, a per-replica dt or
 // gabriel_coefficient, slabs.
@@ -842,6 +842,7 @@ protected:
     //     template<pw_int, pw_friction, int LANES, bool LINKED> static auto lds_kernel()
     //     template<int LANES, bool LINKED> auto lds_kernel_args(const Lds_layout&)    a tuple: the kernel's arguments
     //                                                         behind d_old_v (LINKED: the Links_view follows them)
+    // and may supply lds_layout_of (below).
     struct Lds_knobs {
         int capacity;          // the largest n_max that fits (whole_step_capacity / grid_lds_capacity)
         int allowed;           // -1 = never, 1 = whenever eligible, 0 = where `pays` (whole_steps / lds_steps)
@@ -863,10 +864,18 @@ protected:
         int lanes;
         Lds_layout layout;  // of that many lanes: tile and bytes
     };
+    // THE FORM'S LAYOUT, which the plan asks for: lds_layout with the form's keys -- unless the form declares an
+    // lds_layout_of of its own, whose .bytes cover what it lays out behind lds_layout's regions (the Gabriel form's
+    // lists, ya::ens::gabriel_lds_layout) and are 0 where that has no room.
+    template<bool LINKED>
+    static constexpr Lds_layout lds_layout_of(const int n_max, const int slots, const int lanes)
+    {
+        return lds_layout<Pt, Form::lds_keys, LINKED>(n_max, slots, lanes);
+    }
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
     Lds_plan plan_lds_steps(const Lds_knobs& k, const int slots, const bool has_gen) const
     {
-        const auto layout_of = [&](const int lanes) { return lds_layout<Pt, Form::lds_keys, LINKED>(n_max, slots, lanes); };
+        const auto layout_of = [&](const int lanes) { return Form::template lds_layout_of<LINKED>(n_max, slots, lanes); };
         const bool eligible = n_max <= k.capacity && !has_gen && layout_of(1).bytes != 0;
         if (!eligible || k.allowed < 0 || (k.allowed == 0 && !k.pays)) return {false, 0, Lds_layout{}};
         assert(k.steps_per_launch >= 1);

@@ -30,7 +30,8 @@
 // SEVERAL LANES PER CELL  Inside such a launch `lds_step_lanes` = 4, 16 or 64 lanes share a cell's candidates
 // (ya::ens::grid_lds_walk_coop: terms into an LDS buffer behind the keys, one lane per component adds them in the walk's
 // order), for replicas of a few dozen cells, which leave most of the workgroup idle otherwise: the same bits.
-// Not built for these launches: the Gabriel form, the fast tier, graph capture.
+// Not built for these launches: the fast tier, graph capture.  (The Gabriel form steps from LDS by a kernel of its
+// own, ya::ens::gabriel_lds_steps in ensemble_gabriel.cuh, on this file's order and search of the keys.)
 //
 // LINKS  cells.take_steps<my_force>(dt, K, ya::ens::Replica_links{links, S}) steps with the ORDERED link forces of a
 // Links object over the flat id space (ensemble_links.cuh: slot s belongs to replica s / S, a == b is inert, slots
@@ -596,7 +597,7 @@ __device__ __forceinline__ void grid_lds_walk_coop(const int n, const int id_bas
 // LANES (4, 16 or 64; Ensemble<Pt, Grid_solver>::lds_step_lanes): the walk is grid_lds_walk_coop, its term buffer
 // behind all that, the tile length the layout's, read from the same constexpr function as the host's.  LANES == 1 is
 // the one-lane code as it was.  (lanes_per_cell, the 14-launch step's knob, plays no part.)
-// Not here: the Gabriel form, the fast tier, graph capture.
+// Not here: the fast tier, graph capture (the Gabriel form's launch is ya::ens::gabriel_lds_steps, ensemble_gabriel.cuh).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED, int LANES = 1>
 __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, const int* __restrict__ d_n,
     const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,

@@ -1711,11 +1711,27 @@ __device__ __forceinline__ bool occluded(const int rank, const float mx, const f
     }
     return false;
 }
+// WHERE THE STAGES FIND THE CUBE-SORTED CELLS.  The stages below read a system's cells through `rows`: entry(k) = the
+// cell in sorted slot k (position and id), X(k) its position alone, v(k) its old_v, cube(k) its cube,
+// first_slot(c) = offs[c], c in [0, n_cubes].  Sorted_rows is a build's global arrays (every kernel of this file);
+// ya::ens::Lds_rows (include/ensemble_gabriel.cuh) a replica's keys and step arrays in LDS.
+template<typename Pt>
+struct Sorted_rows {
+    const Entry<Pt>* __restrict__ sorted;
+    const float4* __restrict__ sorted_v;
+    const int* __restrict__ cube_id;
+    const int* __restrict__ offs;
+    __device__ __forceinline__ Entry<Pt> entry(const int k) const { return sorted[k]; }
+    __device__ __forceinline__ Pt X(const int k) const { return sorted[k].X; }
+    __device__ __forceinline__ float4 v(const int k) const { return sorted_v[k]; }
+    __device__ __forceinline__ int cube(const int k) const { return cube_id[k]; }
+    __device__ __forceinline__ int first_slot(const int c) const { return offs[c]; }
+};
 // A cell's candidates into the list (x, y, z, d, slot) in the reference's order, by the `lanes` lanes
 // from `first_lane` of the wavefront; returns the number of candidates (entries beyond cap are not written).
-template<typename Pt>
+template<typename Pt, typename Rows>
 __device__ __forceinline__ int collect(const int lane, const int lanes, const int first_lane, const Pt Xi,
-    const int c, const Entry<Pt>* __restrict__ sorted, const int* __restrict__ offs, const int gs,
+    const int c, const Rows& rows, const int gs,
     const int n_cubes, const float cube_size, const int cap, float* x, float* y, float* z, float* d, int* slot)
 {
     const unsigned long long group = (lanes == 64 ? ~0ull : ((1ull << lanes) - 1)) << first_lane;
@@ -1723,15 +1739,15 @@ __device__ __forceinline__ int collect(const int lane, const int lanes, const in
     int count = 0;
     for (int row = 0; row < 9; row++) {
         const int mid = c + stencil_row_offset(row, gs);
-        const int k_begin = offs[min(max(mid - 1, 0), n_cubes)];
-        const int k_end = offs[min(max(mid + 2, 0), n_cubes)];
+        const int k_begin = rows.first_slot(min(max(mid - 1, 0), n_cubes));
+        const int k_end = rows.first_slot(min(max(mid + 2, 0), n_cubes));
         for (int base = k_begin; base < k_end; base += lanes) {
             const int k = base + lane;
             bool hit = false;
             Pt Xk;
             float dist = 0;
             if (k < k_end) {
-                Xk = sorted[k].X;
+                Xk = rows.X(k);
                 const Pt r = Xi - Xk;
                 dist = dist3(r.x, r.y, r.z);
                 hit = !(dist >= cube_size);  // (solvers.cuh:540: a NaN distance is a candidate)
@@ -1787,11 +1803,11 @@ __device__ __forceinline__ void rank_list(const int lane, const int lanes, const
 // functors that count per cell, `d_n_nbs[i] += 1` of tests/test_solvers.cu:343-352, stay right).
 // i and the sorted entries' ids are rows of d_dX; the functors are handed id_base + id (an ensemble's replica
 // starts at id_base, include/ensemble_gabriel.cuh; a lone system's constant 0 folds away).
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Index>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Index, typename Rows>
 __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, const int s, const Pt Xi,
     const int i, const int id_base, const int count, const float gabriel_coefficient, const float* x, const float* y,
     const float* z, const float* d, const int* slot, const Index* rank, const Index* order, Index* kept,
-    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, Pt* __restrict__ d_dX,
+    const Rows& rows, Pt* __restrict__ d_dX,
     const bool has_gen)
 {
     for (int p = lane; p < count; p += lanes) {  // solvers.cuh:575-593
@@ -1813,7 +1829,7 @@ __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, co
         if (!kept[m]) continue;
         const int p = order[m];
         const float dist = d[p];
-        const Entry<Pt> other = sorted[slot[p]];
+        const Entry<Pt> other = rows.entry(slot[p]);
         const Pt r = Xi - other.X;
         F += pw_int(Xi, r, dist, id_base + i, id_base + other.id);
         const float friction = pw_friction(Xi, r, dist, id_base + i, id_base + other.id);
@@ -1821,7 +1837,7 @@ __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, co
         // the old_v term only where the friction is not zero: the same bits as the reference's
         // unconditional `sum_v += friction * d_old_v[j]` unless old_v is not finite (0 * inf)
         if (friction != 0) {
-            const float4 v = sorted_v[slot[p]];
+            const float4 v = rows.v(slot[p]);
             sum_v.x += friction * v.x;
             sum_v.y += friction * v.y;
             sum_v.z += friction * v.z;
@@ -1829,59 +1845,46 @@ __device__ __forceinline__ void test_and_sum(const int lane, const int lanes, co
     }
     store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
 }
-}  // namespace gabriel
-
-// ya::gabriel_force's workgroup over ONE system's arrays: the GABRIEL_CELLS sorted slots from `first_slot`.  The
-// functors are handed the ids id_base + id, and a cell left to the dense kernel is appended as dense_base + its
-// slot (an ensemble's replica starts at row id_base = dense_base of the flat arrays and its cube ids and offs[]
-// are its own, include/ensemble_gabriel.cuh; a lone system's constant 0 folds away).
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-__device__ __forceinline__ void gabriel_force_cells(const int n, const int first_slot, const int id_base,
-    const int dense_base, const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
-    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
-    const int n_cubes, const float cube_size, const float gabriel_coefficient,
-    Pt* __restrict__ d_dX, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
+// One cell, sorted slot s, by its group of GABRIEL_LANES lanes (lane of the group, whose first lane is first_lane of
+// the wavefront): collect, rank, test, sum -- gabriel_force's stages, this file's comment above -- on the group's
+// lists: `list` = GABRIEL_CAP floats for each of x, y, z, d while the list is tested, then, for stateless functors,
+// for each of the NF + 4 terms of the kept pairs by rank (F, friction, friction * old_v); `slot` = GABRIEL_CAP ints;
+// `ranks` = GABRIEL_CAP bytes each of rank, order, kept.  The right-hand side goes to d_dX[the cell's id] by store_rhs,
+// the functors are handed id_base + id.  A cell with more than GABRIEL_CAP candidates is not done here: every lane of
+// the group calls left_to_dense(count) and leaves, with nothing written to d_dX, and the caller sees that
+// gabriel_force_dense_cell does the cell.  Lanes leave at different points: the caller's next statement is reached by
+// all of them, and only wave_syncs lie in here.
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Rows,
+    typename Left_to_dense>
+__device__ __forceinline__ void cell_by_group(const int lane, const int first_lane, const int s, const int id_base,
+    const Rows& rows, const int gs, const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    float (*list)[GABRIEL_CAP], int* slot, unsigned char (*ranks)[GABRIEL_CAP], Pt* __restrict__ d_dX,
+    const bool has_gen, const Left_to_dense& left_to_dense)
 {
     constexpr int NF = N_floats<Pt>::value;
     constexpr int CAP = GABRIEL_CAP;
     constexpr int SLOTS = CAP / GABRIEL_LANES;
-    // x, y, z, d while the list is tested; then, for stateless functors, the kept pairs' terms by rank:
-    // F (NF floats), friction, friction * old_v (3)
-    constexpr int WORDS = NF + 4;
-    __shared__ float sh_list[GABRIEL_CELLS][WORDS][CAP];
-    __shared__ int sh_slot[GABRIEL_CELLS][CAP];
-    __shared__ unsigned char sh_rank[GABRIEL_CELLS][3][CAP];  // rank, order, kept
-
-    const int cell = threadIdx.x / GABRIEL_LANES;
-    const int lane = threadIdx.x % GABRIEL_LANES;
-    const int s = first_slot + cell;
-    if (s >= n) return;  // (whole groups leave: everything below is per group)
-
-    float* x = sh_list[cell][0];
-    float* y = sh_list[cell][1];
-    float* z = sh_list[cell][2];
-    float* d = sh_list[cell][3];
-    unsigned char* rank = sh_rank[cell][0];
-    unsigned char* order = sh_rank[cell][1];
-    unsigned char* kept = sh_rank[cell][2];
-    const Entry<Pt> self = sorted[s];
+    float* x = list[0];
+    float* y = list[1];
+    float* z = list[2];
+    float* d = list[3];
+    unsigned char* rank = ranks[0];
+    unsigned char* order = ranks[1];
+    unsigned char* kept = ranks[2];
+    const Entry<Pt> self = rows.entry(s);
     const Pt Xi = self.X;
     const int i = self.id;
-    const int count = gabriel::collect(lane, GABRIEL_LANES, cell * GABRIEL_LANES, Xi, cube_id[s], sorted, offs, gs,
-        n_cubes, cube_size, CAP, x, y, z, d, sh_slot[cell]);
-    if (count > CAP) {  // ya::gabriel_force_dense does this cell
-        if (lane == 0) {
-            const int at = atomicAdd(&n_dense[0], 1);
-            dense[at] = dense_base + s;
-            atomicMax(&n_dense[1], count);
-        }
+    const int count = gabriel::collect(lane, GABRIEL_LANES, first_lane, Xi, rows.cube(s), rows, gs,
+        n_cubes, cube_size, CAP, x, y, z, d, slot);
+    if (count > CAP) {
+        left_to_dense(count);
         return;
     }
     coop::wave_sync();
-    gabriel::rank_list(lane, GABRIEL_LANES, cell * GABRIEL_LANES, count, d, rank, order);
+    gabriel::rank_list(lane, GABRIEL_LANES, first_lane, count, d, rank, order);
     if constexpr (!stateless_pair<Pt, pw_int, pw_friction>()) {
         gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, GABRIEL_LANES, s, Xi, i, id_base, count,
-            gabriel_coefficient, x, y, z, d, sh_slot[cell], rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+            gabriel_coefficient, x, y, z, d, slot, rank, order, kept, rows, d_dX, has_gen);
         return;
     } else {
         // Functors declared stateless (YA_STATELESS): each lane also evaluates the terms of the pairs it keeps
@@ -1896,7 +1899,7 @@ __device__ __forceinline__ void gabriel_force_cells(const int n, const int first
             if (p < count) {
                 dist[a] = d[p];
                 rk[a] = rank[p];
-                k[a] = sh_slot[cell][p];
+                k[a] = slot[p];
                 keep[a] = true;
                 if (k[a] != s) {  // j != i
                     const float radius = 0.5f * dist[a] * gabriel_coefficient;
@@ -1912,18 +1915,18 @@ __device__ __forceinline__ void gabriel_force_cells(const int n, const int first
             if (p >= count) continue;
             kept[rk[a]] = keep[a];
             if (!keep[a]) continue;
-            const Entry<Pt> other = sorted[k[a]];
+            const Entry<Pt> other = rows.entry(k[a]);
             const Pt r = Xi - other.X;
             const Pt F = pw_int(Xi, r, dist[a], id_base + i, id_base + other.id);
             const float friction = pw_friction(Xi, r, dist[a], id_base + i, id_base + other.id);
 #pragma unroll
-            for (int q = 0; q < NF; q++) sh_list[cell][q][rk[a]] = field(F, q);
-            sh_list[cell][NF][rk[a]] = friction;
+            for (int q = 0; q < NF; q++) list[q][rk[a]] = field(F, q);
+            list[NF][rk[a]] = friction;
             if (friction != 0) {  // (see test_and_sum)
-                const float4 v = sorted_v[k[a]];
-                sh_list[cell][NF + 1][rk[a]] = friction * v.x;
-                sh_list[cell][NF + 2][rk[a]] = friction * v.y;
-                sh_list[cell][NF + 3][rk[a]] = friction * v.z;
+                const float4 v = rows.v(k[a]);
+                list[NF + 1][rk[a]] = friction * v.x;
+                list[NF + 2][rk[a]] = friction * v.y;
+                list[NF + 3][rk[a]] = friction * v.z;
             }
         }
         coop::wave_sync();
@@ -1935,18 +1938,57 @@ __device__ __forceinline__ void gabriel_force_cells(const int n, const int first
             if (!kept[m]) continue;
             Pt term;
 #pragma unroll
-            for (int q = 0; q < NF; q++) field(term, q) = sh_list[cell][q][m];
+            for (int q = 0; q < NF; q++) field(term, q) = list[q][m];
             F += term;
-            const float friction = sh_list[cell][NF][m];
+            const float friction = list[NF][m];
             sum_friction += friction;
             if (friction != 0) {
-                sum_v.x += sh_list[cell][NF + 1][m];
-                sum_v.y += sh_list[cell][NF + 2][m];
-                sum_v.z += sh_list[cell][NF + 3][m];
+                sum_v.x += list[NF + 1][m];
+                sum_v.y += list[NF + 2][m];
+                sum_v.z += list[NF + 3][m];
             }
         }
         store_rhs(d_dX, i, has_gen, F, sum_v, sum_friction);
+        return;
     }
+}
+}  // namespace gabriel
+
+// ya::gabriel_force's workgroup over ONE system's arrays: the GABRIEL_CELLS sorted slots from `first_slot`, each by
+// gabriel::cell_by_group on lists in static LDS.  The functors are handed the ids id_base + id, and a cell left to
+// the dense kernel is appended as dense_base + its slot (an ensemble's replica starts at row id_base = dense_base of
+// the flat arrays and its cube ids and offs[] are its own, include/ensemble_gabriel.cuh; a lone system's constant 0
+// folds away).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void gabriel_force_cells(const int n, const int first_slot, const int id_base,
+    const int dense_base, const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v,
+    const int* __restrict__ cube_id, const int* __restrict__ offs, const int gs,
+    const int n_cubes, const float cube_size, const float gabriel_coefficient,
+    Pt* __restrict__ d_dX, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
+{
+    constexpr int NF = N_floats<Pt>::value;
+    constexpr int CAP = GABRIEL_CAP;
+    // x, y, z, d while the list is tested; then, for stateless functors, the kept pairs' terms by rank:
+    // F (NF floats), friction, friction * old_v (3)
+    constexpr int WORDS = NF + 4;
+    __shared__ float sh_list[GABRIEL_CELLS][WORDS][CAP];
+    __shared__ int sh_slot[GABRIEL_CELLS][CAP];
+    __shared__ unsigned char sh_rank[GABRIEL_CELLS][3][CAP];  // rank, order, kept
+
+    const int cell = threadIdx.x / GABRIEL_LANES;
+    const int lane = threadIdx.x % GABRIEL_LANES;
+    const int s = first_slot + cell;
+    if (s >= n) return;  // (whole groups leave: everything below is per group)
+
+    const gabriel::Sorted_rows<Pt> rows{sorted, sorted_v, cube_id, offs};
+    gabriel::cell_by_group<Pt, pw_int, pw_friction>(lane, cell * GABRIEL_LANES, s, id_base, rows, gs, n_cubes, cube_size,
+        gabriel_coefficient, sh_list[cell], sh_slot[cell], sh_rank[cell], d_dX, has_gen, [&](const int count) {
+            if (lane == 0) {  // ya::gabriel_force_dense does this cell
+                const int at = atomicAdd(&n_dense[0], 1);
+                dense[at] = dense_base + s;
+                atomicMax(&n_dense[1], count);
+            }
+        });
 }
 
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
@@ -1961,12 +2003,12 @@ __global__ __launch_bounds__(64) void gabriel_force(const int n,
 }
 
 // One cell ya::gabriel_force left (more than GABRIEL_CAP candidates), by one wavefront: the same stages on
-// lists of `stride` >= the cell's count entries each, in global memory from x on.  s is the cell's sorted slot in
-// ONE system's arrays, the functors are handed id_base + id (gabriel_force_cells' comment).
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+// lists of `stride` >= the cell's count entries each, from x on (global memory here; LDS in
+// ya::ens::gabriel_lds_steps).  s is the cell's sorted slot in ONE system's `rows`, the functors are handed
+// id_base + id (gabriel_force_cells' comment).
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Rows>
 __device__ __forceinline__ void gabriel_force_dense_cell(const int lane, const int s, const int id_base,
-    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, const int* __restrict__ cube_id,
-    const int* __restrict__ offs, const int gs, const int n_cubes, const float cube_size,
+    const Rows& rows, const int gs, const int n_cubes, const float cube_size,
     const float gabriel_coefficient, Pt* __restrict__ d_dX, const bool has_gen, float* x, const long stride)
 {
     float* y = x + stride;
@@ -1976,9 +2018,9 @@ __device__ __forceinline__ void gabriel_force_dense_cell(const int lane, const i
     int* rank = slot + stride;
     int* order = rank + stride;
     int* kept = order + stride;
-    const Entry<Pt> self = sorted[s];
+    const Entry<Pt> self = rows.entry(s);
     const Pt Xi = self.X;
-    const int count = gabriel::collect(lane, 64, 0, Xi, cube_id[s], sorted, offs, gs, n_cubes, cube_size,
+    const int count = gabriel::collect(lane, 64, 0, Xi, rows.cube(s), rows, gs, n_cubes, cube_size,
         (int)stride, x, y, z, d, slot);
     __threadfence_block();
     coop::wave_sync();
@@ -1986,9 +2028,20 @@ __device__ __forceinline__ void gabriel_force_dense_cell(const int lane, const i
     __threadfence_block();
     coop::wave_sync();
     gabriel::test_and_sum<Pt, pw_int, pw_friction>(lane, 64, s, Xi, self.id, id_base, count, gabriel_coefficient, x,
-        y, z, d, slot, rank, order, kept, sorted, sorted_v, d_dX, has_gen);
+        y, z, d, slot, rank, order, kept, rows, d_dX, has_gen);
     __threadfence_block();
     coop::wave_sync();  // the next cell reuses the workspace
+}
+// (the global arrays of a build)
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+__device__ __forceinline__ void gabriel_force_dense_cell(const int lane, const int s, const int id_base,
+    const Entry<Pt>* __restrict__ sorted, const float4* __restrict__ sorted_v, const int* __restrict__ cube_id,
+    const int* __restrict__ offs, const int gs, const int n_cubes, const float cube_size,
+    const float gabriel_coefficient, Pt* __restrict__ d_dX, const bool has_gen, float* x, const long stride)
+{
+    gabriel_force_dense_cell<Pt, pw_int, pw_friction>(lane, s, id_base,
+        gabriel::Sorted_rows<Pt>{sorted, sorted_v, cube_id, offs}, gs, n_cubes, cube_size, gabriel_coefficient, d_dX,
+        has_gen, x, stride);
 }
 
 // The cells ya::gabriel_force left: one wavefront per cell, lists in a global workspace of `stride` >= the

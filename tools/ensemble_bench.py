@@ -10,6 +10,7 @@
     python tools/ensemble_bench.py --whole-steps --whole-step-lanes 0,1,4,16,64 [--out profiles/ensemble_whole_lanes_bench.json]
     python tools/ensemble_bench.py --solver grid --lds-steps [--out profiles/ensemble_grid_lds_steps_bench.json]
     python tools/ensemble_bench.py --solver grid --lds-steps --lds-step-lanes 0,1,4,16,64 [--out profiles/ensemble_grid_lds_lanes_bench.json]
+    python tools/ensemble_bench.py --solver gabriel --lds-steps [--out profiles/ensemble_gabriel_lds_steps_bench.json]
     python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
     python tools/ensemble_bench.py --solver grid --links [--out profiles/ensemble_grid_links_bench.json]
 
@@ -66,6 +67,13 @@ alternating: the ordered forces on the 14-launch step (lds_steps -1: link_forces
 baseline) and inside launches that step from LDS of one step each (lds_steps 1, lds_steps_max 1: a model that renews
 its links every step) and of up to 256 steps each.  M in {16, 256, 1024, 4096} x n in {100, 256, 512, 1024}.
 ratio_* = the setting's rate over the baseline's.  A record, not a gate.
+
+--solver gabriel --lds-steps: ONE GabrielLdsEnsemble("relu", M, n, grid_size fitted to the ball) per shape under the
+protocol of --lds-steps, two settings alternating: the 16-launch step (lds_steps -1, the baseline) and launches that
+step from LDS of up to 256 steps each (lds_steps 1).  M in {1, 16, 64, 256, 1024, 4096} x n in {20, 64, 100, 256,
+1024} (`--shapes M:n,...` for others; `--steps-per-launch 1` adds launches of ONE step each as a third setting:
+what a caller of take_steps(dt, 1) pays), then the balls ensemble of the tests (48 replicas of K + 1 <= 258 cells, K candidates per cell: the dense path
+inside the launch from K = 65 on; its rates count n_max rows per replica).  Each setting's spread is recorded.
 """
 import argparse
 import json
@@ -78,7 +86,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from yalla_amd.ensemble import (Ensemble, GabrielEnsemble, GridEnsemble, LinkedEnsemble,  # noqa: E402
+from yalla_amd.ensemble import (Ensemble, GabrielEnsemble, GabrielLdsEnsemble, GridEnsemble, LinkedEnsemble,  # noqa: E402
                                 LinkedGridEnsemble)
 from yalla_amd.solution import Solution  # noqa: E402
 
@@ -105,6 +113,13 @@ GRID_LINKS_SETTINGS = {"ordered_fourteen_launches": (-1, 256), "ordered_lds_1_st
                        "ordered_lds_256_steps_per_launch": (1, 256)}
 GABRIEL_SHAPES = [(m, n) for n in (100, 500, 2000, 10000) for m in (1, 8, 64, 512) if m * n <= 5000000]
 GABRIEL_LANES = (0,)  # (no lanes setting: one column)
+# --solver gabriel --lds-steps: one GabrielLdsEnsemble("relu", M, n), (lds_steps, lds_steps_max); and the balls
+GABRIEL_LDS_SHAPES = [(m, n) for n in (20, 64, 100, 256, 1024) for m in (1, 16, 64, 256, 1024, 4096)]
+GABRIEL_LDS_SETTINGS = {"sixteen_launches": (-1, 256), "lds_256_steps_per_launch": (1, 256)}
+# --steps-per-launch 1 adds launches of one step each (a caller of take_steps(dt, 1))
+GABRIEL_LDS_ONE_STEP = {"lds_1_step_per_launch": (1, 1)}
+BALL_SIZES = [1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 66, 127, 128, 129, 255, 256, 257]
+GABRIEL_LDS = False  # --solver gabriel --lds-steps
 DT = 0.01
 GRID = False  # --solver grid
 GABRIEL = False  # --solver gabriel
@@ -146,7 +161,8 @@ class Singles:
 
 class Together:
     def __init__(self, m, n):
-        self.ens = (GabrielEnsemble("relu", m, n, grid_size_for(n), 1.0) if GABRIEL
+        self.ens = (GabrielLdsEnsemble("relu", m, n, grid_size_for(n), 1.0) if GABRIEL_LDS
+                    else GabrielEnsemble("relu", m, n, grid_size_for(n), 1.0) if GABRIEL
                     else GridEnsemble("relu", m, n, grid_size_for(n), 1.0) if GRID else Ensemble("relu", m, n))
         for r in range(m):
             self.ens.h_X[r] = ball(n, r)
@@ -174,6 +190,24 @@ class Together:
 
     def close(self):
         self.ens.close()
+
+
+class Balls(Together):
+    """One GabrielLdsEnsemble("relu", 48, 258, 16): for each K of BALL_SIZES two replicas of K cells inside a ball of
+    radius 0.45 (K candidates per cell, the dense path from 65 on) and a lone cell, the shape of the tests' balls."""
+
+    def __init__(self, m=48, n=258):
+        self.ens = GabrielLdsEnsemble("relu", m, n, 16, 1.0)
+        rng = np.random.default_rng(164)
+        self.cells = 0
+        for r, k in enumerate(k for k in BALL_SIZES for _ in (0, 1)):
+            v = rng.standard_normal((k, 3))
+            v *= (0.45 * rng.random(k) ** (1 / 3) / np.linalg.norm(v, axis=1))[:, None]
+            self.ens.h_X[r, 0] = 3.5
+            self.ens.h_X[r, 1:k + 1] = (0.5 * (r % 2) + v).astype(np.float32)
+            self.ens.h_n[r] = k + 1
+            self.cells += k + 1
+        self.ens.copy_to_device()
 
 
 class Linked:
@@ -283,10 +317,11 @@ def measure(m, n, window, repeats):
     return row
 
 
-def measure_whole(m, n, window, repeats, settings=None, apply=Together.whole, counter="whole_step_launches"):
+def measure_whole(m, n, window, repeats, settings=None, apply=Together.whole, counter="whole_step_launches",
+                  make=Together):
     """One ensemble, every setting of `settings` (the first is the baseline of the ratios) alternated."""
     settings = WHOLE_SETTINGS if settings is None else settings
-    b = Together(m, n)
+    b = make(m, n)
     try:
         ks = {}
         for key, setting in settings.items():
@@ -331,6 +366,39 @@ def main_lds(args):
               + f"  spread {r['spread']:.3f}", flush=True)
         if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
             result = {"tool": "tools/ensemble_bench.py --solver grid --lds-steps", "model": "relu", "dt": DT,
+                      "window_s": args.window, "repeats": args.repeats, "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "min_ratio": min(r["ratio_lds_256_steps_per_launch"] for r in rows),
+                      "max_ratio": max(r["ratio_lds_256_steps_per_launch"] for r in rows)}))
+
+
+def main_gabriel_lds(args):
+    """--solver gabriel --lds-steps: launches that step from LDS (lds_steps 1) against the 16-launch step (lds_steps -1)
+    of the same GabrielLdsEnsemble, alternating; after the sweep the balls ensemble (48 replicas, the dense path)."""
+    shapes = GABRIEL_LDS_SHAPES if not args.shapes else [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")]
+    cases = [(m, n, Together) for m, n in shapes] + ([] if args.shapes else [(48, 258, Balls)])
+    settings = dict(GABRIEL_LDS_SETTINGS, **(GABRIEL_LDS_ONE_STEP if args.steps_per_launch == 1 else {}))
+    for m, n, make in cases:  # the warm-up of every shape and setting
+        run = make(m, n)
+        for setting in settings.values():
+            run.lds(*setting)
+            run.steps(5)
+        run.close()
+    rows = []
+    for m, n, make in cases:
+        rows.append(measure_whole(m, n, args.window, args.repeats, settings, Together.lds,
+                                  "lds_step_launches", make))
+        r = rows[-1]
+        r["input"] = "balls" if make is Balls else "ball of n cells at random_sphere(0.75)'s density"
+        print(f"M {m:5d}  n {n:5d}   "
+              + "  ".join(f"{key}: {r[key]['us_per_step']:10.1f} us/step" for key in settings)
+              + "   ratios " + " ".join(f"{r['ratio_' + key]:.2f}" for key in list(settings)[1:]) + "  spreads "
+              + " ".join(f"{r[key]['spread']:.3f}" for key in settings) + f"  {r['input'][:5]}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --solver gabriel --lds-steps", "model": "relu", "dt": DT,
                       "window_s": args.window, "repeats": args.repeats, "rows": rows}
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
@@ -621,17 +689,24 @@ def main():
                     help="ordered link forces (six launches, whole steps) against link_forces with atomics; with "
                          "--solver grid: ordered link forces from LDS against the 14-launch step of the same ensemble")
     ap.add_argument("--lds-steps", action="store_true",
-                    help="with --solver grid: launches that step from LDS against the 14-launch step of the same ensemble")
+                    help="with --solver grid (gabriel): launches that step from LDS against the 14-launch (16-launch) "
+                         "step of the same ensemble")
     ap.add_argument("--lds-step-lanes", default=None, metavar="L,L,...",
                     help="with --solver grid --lds-steps: these lds_step_lanes settings against lanes 1 of the same "
                          "ensemble, the 14-launch step beside them")
     args = ap.parse_args()
-    global GRID, GABRIEL, LANES, SHAPES
+    global GRID, GABRIEL, GABRIEL_LDS, LANES, SHAPES
     if args.lds_step_lanes and not args.lds_steps:
         ap.error("--lds-step-lanes goes with --solver grid --lds-steps")
+    if args.lds_steps and args.solver == "gabriel":
+        if args.trace_shape or args.whole_steps or args.links or args.lds_step_lanes:
+            ap.error("--solver gabriel --lds-steps measures the Gabriel ensemble on its own (it has no lanes setting)")
+        GABRIEL = GABRIEL_LDS = True
+        main_gabriel_lds(args)
+        return
     if args.lds_steps:
         if args.solver != "grid" or args.trace_shape or args.whole_steps or args.links:
-            ap.error("--lds-steps measures the grid ensemble (--solver grid) on its own")
+            ap.error("--lds-steps measures the grid or the Gabriel ensemble (--solver grid | gabriel) on its own")
         GRID = True
         if args.lds_step_lanes:
             if not set(args.lds_step_lanes.split(",")) <= {"0", "1", "4", "16", "64"}:

@@ -17,6 +17,7 @@ CORE_LIB = os.path.join(_HERE, "libyalla_hip.so")
 ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble.so")  # include/yalla_ensemble.h
 GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid.so")  # include/yalla_ensemble_grid.h
 GABRIEL_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel.so")  # include/yalla_ensemble_gabriel.h
+GABRIEL_LDS_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel_lds.so")  # include/yalla_ensemble_gabriel_lds.h
 LINKED_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_links.so")  # include/yalla_ensemble_links.h
 LINKED_GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid_links.so")  # include/yalla_ensemble_grid_links.h
 
@@ -108,6 +109,13 @@ GABRIEL_ENSEMBLE_ABI = {name.replace("ya_gens_", "ya_gabens_"): sig for name, si
 GABRIEL_ENSEMBLE_ABI["ya_gabens_create"] = (
     C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(_ens)])
 GABRIEL_ENSEMBLE_ABI["ya_gabens_dense_cells"] = (C.c_int, [_ens])
+
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_gabriel_lds.h one to one: the Gabriel ensemble's functions
+# under another prefix (take_steps returns the launches that stepped from LDS), the in-launch dense count and the LDS
+# rule.
+GABRIEL_LDS_ENSEMBLE_ABI = {name.replace("ya_gabens_", "ya_gablds_"): sig for name, sig in GABRIEL_ENSEMBLE_ABI.items()}
+GABRIEL_LDS_ENSEMBLE_ABI["ya_gablds_lds_dense_cells"] = (C.c_longlong, [_ens])
+GABRIEL_LDS_ENSEMBLE_ABI["ya_gablds_lds_bytes"] = (C.c_long, [C.c_char_p, C.c_int])
 
 # name -> (restype, argtypes); mirrors include/yalla_ensemble_links.h one to one: the ensemble's functions under
 # another prefix, create with the slots per replica and the links' strength, the links' host mirror and count, the
@@ -206,6 +214,14 @@ def gabriel_ensemble_lib():
     """The Gabriel ensemble harness, yalla_amd/libyalla_ensemble_gabriel.so (include/yalla_ensemble_gabriel.h),
     every entry point typed.  Raises if it has not been built: there is no fallback."""
     return _load(GABRIEL_ENSEMBLE_LIB, GABRIEL_ENSEMBLE_ABI)
+
+
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
+def gabriel_lds_ensemble_lib():
+    """The Gabriel ensemble harness whose take_steps can step from LDS, yalla_amd/libyalla_ensemble_gabriel_lds.so
+    (include/yalla_ensemble_gabriel_lds.h), every entry point typed.  Raises if it has not been built: there is no
+    fallback."""
+    return _load(GABRIEL_LDS_ENSEMBLE_LIB, GABRIEL_LDS_ENSEMBLE_ABI)
 
 
 @functools.lru_cache(maxsize=None)  # (the same object on every call)

@@ -20,6 +20,7 @@
 
 #include "yalla_ensemble_gabriel.h"
 #include "ensemble_harness.h"  // No_gen, Push_gen, Grid_replicas, Grid_replicas_of, Model, the entry points' bodies
+#include "ensemble_gabriel_models.h"
 
 namespace gabens_harness {
 using ens_harness::No_gen;
@@ -47,19 +48,10 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Gabriel_solver>, Base> {
     int dense_cells() override { return cells.dense_cells(); }
 };
 
-static const Model<Base* (*)(int, int, int, float, float)> model_table[] = {
-    YA_ENSEMBLE_MODEL("relu", float3, relu_force<float3>, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENSEMBLE_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENSEMBLE_MODEL("relu_plain", float3, models::relu_plain, friction_w_neighbour<float3>, No_gen<float3>),
-    YA_ENSEMBLE_MODEL("relu_po", Po_cell, relu_force<Po_cell>, friction_w_neighbour<Po_cell>, No_gen<Po_cell>),
-    YA_ENSEMBLE_MODEL("relu_cell", Cell, relu_force<Cell>, friction_w_neighbour<Cell>, No_gen<Cell>),
-    YA_ENSEMBLE_MODEL("clipped_push", float3, models::clipped_spring, friction_w_neighbour<float3>, Push_gen<float3>),
-    // user-written frictions (model_functors.h; tests/test_friction_functors_gpu.py): ids through local ids
-    // (ensemble_harness.h), declared and `_plain`, and field on the wide point
-    YA_ENSEMBLE_MODEL("friction_ids", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction>, ens_harness::Local_friction_ids),
-    YA_ENSEMBLE_MODEL("friction_ids_plain", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction_plain>, ens_harness::Local_friction_ids),
-    YA_ENSEMBLE_MODEL("friction_field", Po_cell, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
-};
+// (the table is ensemble_gabriel_models.h's, shared with ensemble_gabriel_lds.hip)
+#define YA_GABRIEL_ROW(name, Pt, pw_int, pw_friction, Policy) YA_ENSEMBLE_MODEL(name, Pt, pw_int, pw_friction, Policy),
+static const Model<Base* (*)(int, int, int, float, float)> model_table[] = {YA_GABRIEL_ENSEMBLE_MODELS(YA_GABRIEL_ROW)};
+#undef YA_GABRIEL_ROW
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
 }  // namespace gabens_harness

@@ -25,7 +25,8 @@ otherwise), 0 leaves it to the engine: one lane unless the model's functors are 
 largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice gives the same bits.
 
 `GridEnsemble` (below) is the same for M Grid_solver systems (include/ensemble_grid.cuh), six launches and a grid
-build per stage (or whole steps from LDS, `lds_steps`); `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh);
+build per stage (or whole steps from LDS, `lds_steps`); `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh),
+`GabrielLdsEnsemble` the same with whole steps from LDS (`lds_steps`, libyalla_ensemble_gabriel_lds.so);
 `LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh);
 `LinkedGridEnsemble` the same for M Grid_solver systems, inside launches that step from LDS too.
 """
@@ -297,6 +298,47 @@ class GabrielEnsemble(GridEnsemble):
         return n
 
 
+class GabrielLdsEnsemble(GabrielEnsemble):
+    """`GabrielEnsemble` over include/yalla_ensemble_gabriel_lds.h (libyalla_ensemble_gabriel_lds.so): the same models
+    through `Ensemble<Pt, Gabriel_solver>::take_steps`.  `set_param("lds_steps", 1)` lets `take_step(dt, steps)` run
+    as launches of one workgroup per replica that step from LDS (ya::ens::gabriel_lds_steps: up to
+    `set_param("lds_steps_max", k)` steps per launch, cells with more than 64 candidates done inside the launch)
+    wherever the model has no generic force and n_max is at most the point type's capacity
+    (`GabrielLdsEnsemble.lds_bytes(model, n_max) > 0`); 0 leaves the choice to the engine, -1 (this harness's default)
+    never does.  The bits are the same either way, grid arrays and status included.  `lds_step_launches` counts the
+    launches made, `lds_dense_cells()` the (cell, stage) pairs that took the dense path inside them since the ensemble
+    was created; `dense_cells()` keeps its meaning for the 16-launch path.
+
+        with GabrielLdsEnsemble("relu", n_replicas=256, n_max=100, grid_size=12) as cells:
+            ...; cells.copy_to_device(); cells.set_param("lds_steps", 1); cells.take_step(0.05, 100)
+    """
+    _PREFIX, _LOADER, _NOUN = "ya_gablds_", "gabriel_lds_ensemble_lib", "Gabriel ensemble"
+
+    @property
+    def lds_step_launches(self):
+        """Launches that stepped from LDS so far (Ensemble<Pt, Gabriel_solver>::lds_step_launches): 0 unless
+        set_param("lds_steps", 0 | 1) allowed them and the call was eligible."""
+        return self._whole_step_launches
+
+    def lds_dense_cells(self):
+        """Blocking read: the (cell, stage) pairs done on the dense path inside launches that stepped from LDS, over
+        all replicas, since the ensemble was created."""
+        n = self._f("lds_dense_cells")(self._h)
+        if n < 0:
+            raise YallaError(f"lds_dense_cells() failed with harness code {n}")
+        return n
+
+    @staticmethod
+    def lds_bytes(model, n_max, lib=None):
+        """ya::ens::gabriel_lds_layout<Pt>(n_max).bytes for the model's point type: the dynamic LDS of a launch that
+        steps from LDS, 0 where n_max is beyond the capacity.  Needs no GPU."""
+        lib = lib if lib is not None else _ffi.gabriel_lds_ensemble_lib()
+        code = lib.ya_gablds_lds_bytes(model.encode(), int(n_max))
+        if code < 0:
+            raise YallaError(f"ya_gablds_lds_bytes({model!r}, {n_max}) failed with {code}")
+        return code
+
+
 class LinkedEnsemble(Ensemble):
     """Host-side mirror of `Ensemble<Pt, Tile_solver>` stepped with `ya::ens::Replica_links` (include/ensemble_links.cuh)
     over include/yalla_ensemble_links.h: M all-pairs systems of one model, each with `slots_per_replica` link slots of
@@ -423,6 +465,10 @@ def grid_models(lib=None):
 
 def gabriel_models(lib=None):
     return _models(lib if lib is not None else _ffi.gabriel_ensemble_lib(), "ya_gabens_")
+
+
+def gabriel_lds_models(lib=None):
+    return _models(lib if lib is not None else _ffi.gabriel_lds_ensemble_lib(), "ya_gablds_")
 
 
 def linked_models(lib=None):
