@@ -52,8 +52,14 @@
 // Ensemble<Pt, Gabriel_solver> (ensemble_gabriel.cuh, included after it) is the same for M Gabriel_solver systems,
 // on the grid form's build; its take_steps steps from LDS too (ya::ens::gabriel_lds_steps).
 //
-// Not here ("Ensembles"): the fast-arithmetic tier, graph capture, a per-replica dt or
-// gabriel_coefficient, slabs.
+// PER-REPLICA dt  cells.take_step<my_force>(ya::ens::Replica_dt{d_dt}) and take_steps<my_force>(ya::ens::Replica_dt{d_dt},
+// K[, gen_forces | links]) step replica r with d_dt[r]: n_replicas floats ON THE DEVICE, caller-owned, read by the
+// kernels when they run (a model kernel queued before the call may have written them; the host reads nothing).  Every
+// form, every path and every fixed mode; the path taken does not depend on it; each replica holds the bits of a lone
+// Solution stepped with its value (0.0f is a value like any other).  Ensemble<Pt, Gabriel_solver>::d_gabriel_coefficients
+// is the same for that form's coefficient.
+//
+// Not here ("Ensembles"): the fast-arithmetic tier, graph capture, slabs.
 #pragma once
 
 #include <tuple>
@@ -71,6 +77,31 @@ struct Where {
 __device__ __forceinline__ Where where(const int blocks_per_replica)
 {
     return Where{(int)(blockIdx.x / (unsigned)blocks_per_replica), (int)(blockIdx.x % (unsigned)blocks_per_replica)};
+}
+// A time step per replica: n_replicas floats on the device, caller-owned, read by the step's kernels when they run.
+struct Replica_dt {
+    const float* d_dt;
+};
+// What the step's launches are handed as their time step: the scalar of take_step(float) (PER_REPLICA = false, d_dt
+// NULL) or the array of take_step(Replica_dt), which takes the scalar's place.  The kind is a type, so that a program
+// that never steps with a Replica_dt instantiates no kernel that exists for one (whole_steps<..., true>).
+template<bool PER_REPLICA>
+struct Step_dt {
+    static constexpr bool per_replica = PER_REPLICA;
+    float dt;
+    const float* d_dt;
+};
+inline Step_dt<false> step_dt(const float dt) { return {dt, nullptr}; }
+inline Step_dt<true> step_dt(const Replica_dt per_replica)
+{
+    assert(per_replica.d_dt != nullptr);  // (an array that was never allocated would step with dt = 0)
+    return {0.f, per_replica.d_dt};
+}
+// The replica's value of a parameter that is one scalar for the ensemble or, where d_per_replica is set, a float per
+// replica (dt, the Gabriel coefficient).  The replica is the same for a whole workgroup: so is the value.
+__device__ __forceinline__ float value_of(const float* __restrict__ d_per_replica, const float scalar, const int replica)
+{
+    return d_per_replica ? d_per_replica[replica] : scalar;
 }
 // the replica's count as the device holds it now (never beyond the replica's rows)
 __device__ __forceinline__ int count_of(const int* __restrict__ d_n, const int replica, const int n_max)
@@ -170,13 +201,14 @@ __device__ __forceinline__ float3 resolve_fix(const int kind, const float* __res
 }
 
 // euler_step for every replica: X1 = X0 + (dX - fix) dt on the replica's n_r rows; the replica's first
-// workgroup leaves the stage's velocity in d_fix_first[4 r ..] for the corrector.  d_zero (may be NULL): the
+// workgroup leaves the stage's velocity in d_fix_first[4 r ..] for the corrector.  d_dt (may be NULL): the replicas'
+// own time steps, d_dt[r] instead of dt.  d_zero (may be NULL): the
 // next stage's right-hand side, left zeroed for the generic forces -- ALL of the replica's rows, used or not.
 template<typename Pt>
 __global__ __launch_bounds__(UPDATE_BLOCK) void euler_step_batched(const int n_max, const int blocks_per_replica,
-    const int* __restrict__ d_n, const float dt, const int kind, const int fix_point, const float* __restrict__ partials,
-    const int max_blocks, float* __restrict__ d_fix_first, const Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_X0_all,
-    Pt* __restrict__ d_X1_all, Pt* __restrict__ d_zero_all)
+    const int* __restrict__ d_n, const float dt, const float* __restrict__ d_dt, const int kind, const int fix_point,
+    const float* __restrict__ partials, const int max_blocks, float* __restrict__ d_fix_first,
+    const Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_X0_all, Pt* __restrict__ d_X1_all, Pt* __restrict__ d_zero_all)
 {
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
@@ -191,17 +223,19 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void euler_step_batched(const int n_m
         d_fix_first[4 * (size_t)w.replica + 1] = fix.y;
         d_fix_first[4 * (size_t)w.replica + 2] = fix.z;
     }
-    if (local < n) d_X1_all[base + local] = d_X0_all[base + local] + ya::minus_fix(d_dX[local], fix) * dt;
+    const float dt_r = value_of(d_dt, dt, w.replica);
+    if (local < n) d_X1_all[base + local] = d_X0_all[base + local] + ya::minus_fix(d_dX[local], fix) * dt_r;
 }
 
 // heun_step for every replica: X += ((dX - fix) + (dX1 - fix1)) / 2 dt and old_v, fix as the predictor left
-// it, fix1 from this stage.  zero_dX: the replica's rows of d_dX, dead after this, are left zeroed -- all of
+// it, fix1 from this stage, dt or d_dt[r] as in euler_step_batched.  zero_dX: the replica's rows of d_dX, dead after this, are left zeroed -- all of
 // them -- for the next step's generic forces; the fixed point's stage-1 row is therefore never read here.
 template<typename Pt>
 __global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_max, const int blocks_per_replica,
-    const int* __restrict__ d_n, const float dt, const int kind, const int fix_point, const float* __restrict__ partials,
-    const int max_blocks, const float* __restrict__ d_fix_first, Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_dX1_all,
-    Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const bool zero_dX)
+    const int* __restrict__ d_n, const float dt, const float* __restrict__ d_dt, const int kind, const int fix_point,
+    const float* __restrict__ partials, const int max_blocks, const float* __restrict__ d_fix_first,
+    Pt* __restrict__ d_dX_all, const Pt* __restrict__ d_dX1_all, Pt* __restrict__ d_X_all,
+    float3* __restrict__ d_old_v_all, const bool zero_dX)
 {
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
@@ -212,8 +246,9 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void heun_step_batched(const int n_ma
         return;
     }
     const float3 fix1 = resolve_fix<Pt>(kind, partials, max_blocks, w.replica, n, d_dX1_all + base, fix_point);
+    const float dt_r = value_of(d_dt, dt, w.replica);
     if (local < n) {
-        ya::heun_row(local, dt, d_fix_first + 4 * (size_t)w.replica, fix1, d_dX_all + base, d_dX1_all + base,
+        ya::heun_row(local, dt_r, d_fix_first + 4 * (size_t)w.replica, fix1, d_dX_all + base, d_dX1_all + base,
             d_X_all + base, d_old_v_all + base, zero_dX);
     } else if (zero_dX && local < n_max) {
         d_dX_all[base + local] = ya::zero<Pt>();
@@ -554,7 +589,8 @@ __device__ __forceinline__ void whole_steps_in_lds(const int n_max, const int n,
 // n_steps Heun steps of replica blockIdx.x by ONE 256-thread workgroup, from LDS.  Nothing crosses workgroups.
 // Global memory: d_n[r] is read once, rows [0, n_r) of d_X and d_old_v are read at the start and written at the
 // end; nothing else is written (unused rows, other replicas, d_n and the ensemble's right-hand-side arrays are
-// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.
+// left as they are).  kind1 / kind2: the Fix_kind of stage 1 and of stage 2.  dt: the replica's, which the kernels
+// below resolve from their scalar and their array.
 // The body of the kernels below: whole_steps_in_lds with the all-pairs forces of a stage.  LANES = 1: they are
 // whole_stage_force; 4, 16 or 64: whole_stage_force_coop with tiles of `tile` partners.
 // LINKED (whole_steps_linked below): once per launch the workgroup builds the replica's incidence list behind the
@@ -586,36 +622,53 @@ __device__ __forceinline__ void whole_steps_of_a_replica(const int n_max, const 
             whole_stage_forces<Pt, pw_int, pw_friction, LANES, LINKED>(n, (int)base, sh_in, sh_v, sh_rhs, sh_part, tile);
         });
 }
+// The time step of replica blockIdx.x in the two unlinked kernels below.  REPLICA_DT is a template parameter there
+// because it was measured (profiles/ensemble_replica_dt_bench.json, "before_the_template_parameter"): with a nullable
+// pointer tested at run time whole_steps_coop's scalar calls ran 0.44 % slower than the parent commit's at M = 256,
+// n = 64 (945.1 against 949.3 M cell updates / s, spreads 0.03 % and 0.15 %; the loop's instructions were the same,
+// their registers and addresses were not); with the parameter the two agree.  The scalar instance reads no array, and
+// only a program that steps with a Replica_dt instantiates the other (ya::ens::Step_dt).
+template<bool REPLICA_DT>
+__device__ __forceinline__ float whole_step_dt(const float* __restrict__ d_dt, const float dt)
+{
+    if constexpr (REPLICA_DT)
+        return d_dt[blockIdx.x];
+    else
+        return dt;
+}
 // One thread per cell: dynamic LDS of lds_layout<Pt, false, false>(n_max, 0, 1).bytes.
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool REPLICA_DT = false>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps(const int n_max, const int* __restrict__ d_n, const float dt,
-    const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all)
+    const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2, const int fix_point,
+    Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all)
 {
     whole_steps_of_a_replica<Pt, pw_int, pw_friction, 1>(
-        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, 0);
+        n_max, d_n, whole_step_dt<REPLICA_DT>(d_dt, dt), n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, 0);
 }
 // COOP_LANES (4, 16 or 64) lanes per cell, for functors that keep no per-cell state: dynamic LDS and tile of
 // lds_layout<Pt, false, false>(n_max, 0, COOP_LANES), which has room (.bytes > 0).
-template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
+template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES,
+    bool REPLICA_DT = false>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_coop(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const int tile)
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2,
+    const int fix_point, Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const int tile)
 {
     whole_steps_of_a_replica<Pt, pw_int, pw_friction, COOP_LANES>(
-        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile);
+        n_max, d_n, whole_step_dt<REPLICA_DT>(d_dt, dt), n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile);
 }
 // The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage; LANES = 1,
 // 4, 16 or 64: dynamic LDS and tile of lds_layout<Pt, false, true>(n_max, links.slots_per_replica, LANES), which has
-// room.  Besides what whole_steps reads, the replica's
+// room.  d_dt (may be NULL): d_dt[r] instead of dt, decided at run time (not measured against the parent; the linked
+// kernels keep their instance count).  Besides what whole_steps reads, the replica's
 // slots of links.d_link and *links.d_n are read, at the start of the launch.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES>
 __global__ __launch_bounds__(UPDATE_BLOCK) void whole_steps_linked(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const int tile, const Links_view links)
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2,
+    const int fix_point, Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const int tile,
+    const Links_view links)
 {
     whole_steps_of_a_replica<Pt, pw_int, pw_friction, LANES, true>(
-        n_max, d_n, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile, links);
+        n_max, d_n, value_of(d_dt, dt, blockIdx.x), n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, tile, links);
 }
 
 // Whether whole-step launches beat the six-launch step when the model leaves the choice to the engine
@@ -778,6 +831,25 @@ public:
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_step(float dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
+        one_step<pw_int, pw_friction>(step_dt(dt), gen_forces);
+    }
+    // The same step with replica r's own time step d_dt[r], which the update kernels read on the device.
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_step(Replica_dt dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_step<pw_int, friction_w_neighbour<Pt>>(dt, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_step(Replica_dt dt, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        one_step<pw_int, pw_friction>(step_dt(dt), gen_forces);
+    }
+
+protected:
+    // take_step with either kind of time step
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool PER_REPLICA>
+    void one_step(const Step_dt<PER_REPLICA> dt, Generic_forces<Pt> gen_forces)
+    {
         const bool has_gen = !ya::is_no_gen_forces<Pt>(gen_forces);
         const int update_blocks = (n_max + ya::UPDATE_BLOCK - 1) / ya::UPDATE_BLOCK;
         for (int stage = 1; stage <= 2; stage++) {
@@ -800,18 +872,19 @@ public:
                 ya::ens::reduce_partials_batched<n_floats><<<grid_of(max_blocks()), ya::UPDATE_BLOCK>>>(
                     n_max, max_blocks(), d_n, reinterpret_cast<const float*>(d_rhs), d_partials);
             if (stage == 1) {
-                ya::ens::euler_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n, dt,
-                    kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_X, d_X1, has_gen ? d_dX1 : nullptr);
+                ya::ens::euler_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n,
+                    dt.dt, dt.d_dt, kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_X, d_X1,
+                    has_gen ? d_dX1 : nullptr);
                 rhs_zeroed[1] = has_gen;
             } else {
-                ya::ens::heun_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n, dt,
-                    kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_dX1, d_X, d_old_v, has_gen);
+                ya::ens::heun_step_batched<Pt><<<grid_of(update_blocks), ya::UPDATE_BLOCK>>>(n_max, update_blocks, d_n,
+                    dt.dt, dt.d_dt, kind, fix_point, d_partials, max_blocks(), d_fix_first, d_dX, d_dX1, d_X, d_old_v,
+                    has_gen);
                 rhs_zeroed[0] = has_gen;
             }
         }
     }
 
-protected:
     Pt *d_dX, *d_X1, *d_dX1;
     float* d_fix_first;  // [n_replicas][4] stage 1's fixed velocity, left by the predictor for the corrector
     float* d_partials;   // [n_replicas][max_blocks()][n_floats] partial sums of a stage's right-hand sides
@@ -839,7 +912,9 @@ protected:
     // form's lds steps) supplies
     //     static constexpr bool lds_keys                      its lds_layout has keys
     //     Lds_knobs lds_knobs()                               its capacity, settings and rules, as below
-    //     template<pw_int, pw_friction, int LANES, bool LINKED> static auto lds_kernel()
+    //     template<pw_int, pw_friction, int LANES, bool LINKED, bool REPLICA_DT> static auto lds_kernel()
+    //                                                         REPLICA_DT: the call has a time step per replica (a form
+    //                                                         whose kernels decide that at run time returns the same)
     //     template<int LANES, bool LINKED> auto lds_kernel_args(const Lds_layout&)    a tuple: the kernel's arguments
     //                                                         behind d_old_v (LINKED: the Links_view follows them)
     // and may supply lds_layout_of (below).
@@ -898,8 +973,8 @@ protected:
     }
     // n_steps steps as launches of at most steps_per_launch steps each of the form's kernel of the plan's lanes, if
     // the plan is to step from LDS; false: nothing was launched.
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED>
-    bool steps_from_lds(const float dt, const int n_steps, const bool has_gen, const Links_view links = Links_view{})
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED, bool PER_REPLICA>
+    bool steps_from_lds(const Step_dt<PER_REPLICA> dt, const int n_steps, const bool has_gen, const Links_view links = Links_view{})
     {
         Form& form = *static_cast<Form*>(this);
         const Lds_knobs k = form.lds_knobs();
@@ -909,7 +984,7 @@ protected:
         const size_t lds = plan.layout.bytes;
         with_lds_lanes(plan.lanes, [&](auto lanes) {
             constexpr int LANES = decltype(lanes)::value;
-            const auto kernel = Form::template lds_kernel<pw_int, pw_friction, LANES, LINKED>();
+            const auto kernel = Form::template lds_kernel<pw_int, pw_friction, LANES, LINKED, PER_REPLICA>();
             // beyond 64 KiB of dynamic LDS a kernel has to be told once (per kernel: the static is this instance's)
             static size_t lds_allowed = 64 * 1024;
             if (lds > lds_allowed) {
@@ -918,8 +993,8 @@ protected:
                 lds_allowed = lds;
             }
             const auto launch = [&](const int steps, auto... more) {
-                kernel<<<dim3((unsigned)n_replicas), ya::UPDATE_BLOCK, lds>>>(n_max, d_n, dt, steps, fix_kind_of(1),
-                    fix_kind_of(2), fix_point, d_X, d_old_v, more...);
+                kernel<<<dim3((unsigned)n_replicas), ya::UPDATE_BLOCK, lds>>>(n_max, d_n, dt.dt, dt.d_dt, steps,
+                    fix_kind_of(1), fix_kind_of(2), fix_point, d_X, d_old_v, more...);
                 (*k.launches)++;
             };
             const auto args = form.template lds_kernel_args<LANES, LINKED>(plan.layout);
@@ -936,18 +1011,21 @@ protected:
         rhs_zeroed[0] = rhs_zeroed[1] = false;
         return true;
     }
-    // take_steps(dt, n_steps, gen_forces) of such a form: from LDS, or n_steps calls of take_step
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void steps(const float dt, const int n_steps, Generic_forces<Pt> gen_forces)
+    // take_steps(dt, n_steps, gen_forces) of such a form: from LDS, or n_steps calls of take_step.  The plan does not
+    // look at the kind of time step.
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Dt>
+    void steps(const Dt float_or_replica_dt, const int n_steps, Generic_forces<Pt> gen_forces)
     {
+        const auto dt = step_dt(float_or_replica_dt);
         if (steps_from_lds<pw_int, pw_friction, false>(dt, n_steps, !ya::is_no_gen_forces<Pt>(gen_forces))) return;
-        for (int s = 0; s < n_steps; s++) take_step<pw_int, pw_friction>(dt, gen_forces);
+        for (int s = 0; s < n_steps; s++) one_step<pw_int, pw_friction>(dt, gen_forces);
     }
     // take_steps(dt, n_steps, links): from LDS, or n_steps calls of take_step with ya::ens::link_forces_ordered as the
     // generic force
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
-    void steps(const float dt, const int n_steps, const Replica_links links)
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, typename Dt>
+    void steps(const Dt float_or_replica_dt, const int n_steps, const Replica_links links)
     {
+        const auto dt = step_dt(float_or_replica_dt);
         const int slots = links.slots_per_replica;
         assert(slots >= 0 && (size_t)n_replicas * (size_t)slots <= (size_t)links.links.n_max);
         if (steps_from_lds<pw_int, pw_friction, true>(dt, n_steps, false, view_of(links))) return;
@@ -957,7 +1035,7 @@ protected:
         Generic_forces<Pt> gen = [l, slots, n_max, d_n](const int n, const Pt* __restrict__ d_X, Pt* d_dX) {
             link_forces_ordered<Pt>(Replica_links{*l, slots}, n, n_max, d_n, d_X, d_dX);
         };
-        for (int s = 0; s < n_steps; s++) take_step<pw_int, pw_friction>(dt, gen);
+        for (int s = 0; s < n_steps; s++) one_step<pw_int, pw_friction>(dt, gen);
     }
 };
 
@@ -1047,6 +1125,28 @@ public:
         this->template steps<pw_int, pw_friction>(dt, n_steps, links);
     }
 
+    // The same calls with replica r's own time step dt.d_dt[r] (this file's header): the same plan, the same launches.
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, ya::ens::Replica_links links)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, links);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, ya::ens::Replica_links links)
+    {
+        this->template steps<pw_int, pw_friction>(dt, n_steps, links);
+    }
+
 protected:
     // What ya::ens::Stepper's launches from LDS ask of a form: the layout has no keys; the settings above; the kernels.
     static constexpr bool lds_keys = false;
@@ -1056,15 +1156,15 @@ protected:
         return {capacity, whole_steps, ya::ens::whole_steps_pay(this->n_replicas, this->n_max), steps_per_launch, whole_step_lanes, ya::ens::whole_step_lanes_for(this->n_max), &whole_step_launches,
             &whole_step_lanes_used};
     }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED, bool REPLICA_DT>
     static auto lds_kernel()
     {
         if constexpr (LINKED)
             return &ya::ens::whole_steps_linked<Pt, pw_int, pw_friction, LANES>;
         else if constexpr (LANES > 1)
-            return &ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES>;
+            return &ya::ens::whole_steps_coop<Pt, pw_int, pw_friction, LANES, REPLICA_DT>;
         else
-            return &ya::ens::whole_steps<Pt, pw_int, pw_friction>;
+            return &ya::ens::whole_steps<Pt, pw_int, pw_friction, REPLICA_DT>;
     }
     template<int LANES, bool LINKED>
     auto lds_kernel_args(const ya::ens::Lds_layout& layout) const

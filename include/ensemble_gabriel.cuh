@@ -31,6 +31,12 @@
 //
 // cube_size and gabriel_coefficient hold for every replica and may be changed between steps.
 //
+// PER-REPLICA COEFFICIENT AND dt  d_gabriel_coefficients (default NULL) = n_replicas floats ON THE DEVICE, caller-owned:
+// where it is set replica r's forces use [r] and the scalar member is ignored, on the 16-launch path (dense kernel
+// included) and in launches that step from LDS.  The kernels read it when they run, in stream order: a model kernel
+// queued before the call may have written it.  take_step / take_steps with ya::ens::Replica_dt{d_dt} in place of dt
+// are ensemble.cuh's.  Each replica holds the bits of a lone Solution<Pt, Gabriel_solver> with its two values.
+//
 // WHOLE STEPS FROM LDS  cells.take_steps<my_force>(dt, 100) is 100 calls of take_step, bit for bit (positions, old_v,
 // d_status, the public grid arrays); where a replica fits one workgroup's LDS (n_max <=
 // ya::ens::gabriel_lds_capacity<Pt>()), there are no generic forces and `lds_steps` allows it, it runs as ONE launch
@@ -55,7 +61,7 @@
 // capacities (ya::ens::gabriel_lds_capacity: the largest n_max with room, at most 1024): 1024 rows for a 3-float
 // point (142384 bytes, one set), 995 for 4 floats, 826 for 5, 592 for 7, 512 for 8 (513 rows lay out 1024 keys).
 //
-// Not here: a per-replica gabriel_coefficient, cube_size or dt, the fast-arithmetic tier, graph capture, the wall
+// Not here: a per-replica cube_size, the fast-arithmetic tier, graph capture, the wall
 // model's wall_forces (one wall node per system); in launches that step from LDS also ordered links.
 #pragma once
 
@@ -66,13 +72,13 @@ namespace ens {
 // replica, GABRIEL_LANES lanes per cell, by gabriel_force's own body (ya::gabriel_force_cells).  Cube ids and
 // offs are the replica's own and gabriel::collect clamps the stencil to [0, n_cubes], so no row of another
 // replica is read.  A cell with more than GABRIEL_CAP candidates appends its FLAT row r * n_max + slot to the
-// ensemble's one dense list.
+// ensemble's one dense list.  d_coefficients (may be NULL): the replicas' own coefficients, [r] instead of the scalar.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
 __global__ __launch_bounds__(64) void gabriel_force_batched(const int n_max, const int blocks_per_replica,
     const int* __restrict__ d_n, const Entry<Pt>* __restrict__ sorted_all, const float4* __restrict__ sorted_v_all,
     const int* __restrict__ cube_id_all, const int* __restrict__ offs_all, const int gs, const int n_cubes,
-    const float cube_size, const float gabriel_coefficient, Pt* __restrict__ d_dX_all, const bool has_gen,
-    int* __restrict__ dense, int* __restrict__ n_dense)
+    const float cube_size, const float gabriel_coefficient, const float* __restrict__ d_coefficients,
+    Pt* __restrict__ d_dX_all, const bool has_gen, int* __restrict__ dense, int* __restrict__ n_dense)
 {
     const Where w = where(blocks_per_replica);
     const int n = count_of(d_n, w.replica, n_max);
@@ -80,17 +86,18 @@ __global__ __launch_bounds__(64) void gabriel_force_batched(const int n_max, con
     const size_t base = (size_t)w.replica * n_max;
     gabriel_force_cells<Pt, pw_int, pw_friction>(n, w.block * GABRIEL_CELLS, (int)base, (int)base, sorted_all + base,
         sorted_v_all + base, cube_id_all + base, offs_all + (size_t)w.replica * (n_cubes + 1), gs, n_cubes, cube_size,
-        gabriel_coefficient, d_dX_all + base, has_gen, dense, n_dense);
+        value_of(d_coefficients, gabriel_coefficient, w.replica), d_dX_all + base, has_gen, dense, n_dense);
 }
 
 // ya::gabriel_force_dense for the ensemble's one list of flat rows: a grid-stride walk, one wavefront per cell
-// (ya::gabriel_force_dense_cell), the replica is row / n_max, the lists hold n_max entries each.
+// (ya::gabriel_force_dense_cell), the replica is row / n_max -- and with it the coefficient, d_coefficients[replica]
+// where that is set --, the lists hold n_max entries each.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
 __global__ __launch_bounds__(64) void gabriel_force_dense_batched(const int n_max, const int* __restrict__ dense,
     const int* __restrict__ n_dense, const Entry<Pt>* __restrict__ sorted_all, const float4* __restrict__ sorted_v_all,
     const int* __restrict__ cube_id_all, const int* __restrict__ offs_all, const int gs, const int n_cubes,
-    const float cube_size, const float gabriel_coefficient, Pt* __restrict__ d_dX_all, const bool has_gen,
-    float* __restrict__ workspace)
+    const float cube_size, const float gabriel_coefficient, const float* __restrict__ d_coefficients,
+    Pt* __restrict__ d_dX_all, const bool has_gen, float* __restrict__ workspace)
 {
     const int listed = n_dense[0];
     if ((int)blockIdx.x >= listed) return;  // (the usual case: no dense cell at all)
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(64) void gabriel_force_dense_batched(const int n_ma
         const size_t base = (size_t)replica * n_max;
         gabriel_force_dense_cell<Pt, pw_int, pw_friction>(threadIdx.x, row - (int)base, (int)base, sorted_all + base,
             sorted_v_all + base, cube_id_all + base, offs_all + (size_t)replica * (n_cubes + 1), gs, n_cubes, cube_size,
-            gabriel_coefficient, d_dX_all + base, has_gen, x, stride);
+            value_of(d_coefficients, gabriel_coefficient, replica), d_dX_all + base, has_gen, x, stride);
     }
 }
 
@@ -211,8 +218,9 @@ struct Lds_rows {
 // header).  Every barrier is reached by all 256 threads; the trip counts around them depend on n_r, n_max and n_steps.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
 __global__ __launch_bounds__(UPDATE_BLOCK) void gabriel_lds_steps(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float gabriel_coefficient,
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2,
+    const int fix_point, Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const float cs, const int gs,
+    const int n_cubes, const float gabriel_coefficient, const float* __restrict__ d_coefficients,
     int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status, unsigned long long* __restrict__ d_lds_dense)
 {
@@ -238,7 +246,9 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void gabriel_lds_steps(const int n_ma
     const int id_base = replica * n_max;
     bool outside = false;
     int dense_done = 0;  // (cell, stage) pairs this wavefront did on the dense path
-    whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all,
+    // (the replica's own time step and coefficient where the call has them, read once)
+    const float dt_r = value_of(d_dt, dt, replica), coefficient = value_of(d_coefficients, gabriel_coefficient, replica);
+    whole_steps_in_lds<Pt>(n_max, n, replica, dt_r, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all,
         gabriel_step_lds, [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
             outside |= grid_lds_order<Pt>(n, sh_in, cs, gs, n_cubes, sh_key);
             const Lds_rows<Pt> rows{sh_key, n, sh_in, sh_v};
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void gabriel_lds_steps(const int n_ma
                 if (s < n) {
                     if (dense_sets > 0 && lane == 0) sh_dense_flag[s] = 0;
                     gabriel::cell_by_group<Pt, pw_int, pw_friction>(lane, first_lane, s, id_base, rows, gs, n_cubes, cs,
-                        gabriel_coefficient, list, slot, ranks, sh_rhs, false, [&](const int) {
+                        coefficient, list, slot, ranks, sh_rhs, false, [&](const int) {
                             if (dense_sets > 0 && lane == 0) sh_dense_flag[s] = 1;  // (without flags no cell has so many)
                         });
                 }
@@ -259,7 +269,7 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void gabriel_lds_steps(const int n_ma
                     for (int s = wave; s < n; s += dense_sets) {
                         if (!sh_dense_flag[s]) continue;
                         gabriel_force_dense_cell<Pt, pw_int, pw_friction>(wave_lane, s, id_base, rows, gs, n_cubes, cs,
-                            gabriel_coefficient, sh_rhs, false, dense_lists, (long)n_max);
+                            coefficient, sh_rhs, false, dense_lists, (long)n_max);
                         dense_done++;
                     }
                 }
@@ -319,6 +329,8 @@ public:
     // (grid_size, n_cubes, cube_size, d_cube_id, d_point_id, d_offs, d_status, sizes_ok, status, check_status,
     // copy_to_host: ya::ens::Grid_form)
     float gabriel_coefficient;  // of every replica; may be changed between steps
+    // n_replicas floats on the device, caller-owned; non-null: replica r uses [r], the scalar member is ignored
+    const float* d_gabriel_coefficients = nullptr;
     const int dense_blocks;     // workgroups of the dense launch, ya::ens::gabriel_dense_blocks
 
     // take_steps as launches that step from LDS (ya::ens::gabriel_lds_steps: one workgroup per replica): -1 = never,
@@ -361,6 +373,17 @@ public:
     // After such launches d_dX / d_X1 / d_dX1, the build's private arrays and dense_cells() are left as they were.
     template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
     void take_steps(float dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
+    }
+    // The same calls with replica r's own time step dt.d_dt[r] (ensemble.cuh's header): the same plan, the same launches.
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
     {
         this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
     }
@@ -408,16 +431,16 @@ protected:
         return {capacity, lds_steps, ya::ens::gabriel_lds_steps_pay(this->n_replicas, this->n_max, this->n_cubes),
             lds_steps_max, 1, 1, &lds_step_launches, &lds_lanes_used};
     }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
-    static auto lds_kernel()
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED, bool REPLICA_DT>
+    static auto lds_kernel()  // (REPLICA_DT: the kernel decides at run time)
     {
         return &ya::ens::gabriel_lds_steps<Pt, pw_int, pw_friction>;
     }
     template<int LANES, bool LINKED>
     auto lds_kernel_args(const ya::ens::Lds_layout&) const
     {
-        return std::make_tuple(this->cube_size, this->grid_size, this->n_cubes, gabriel_coefficient, this->d_cube_id,
-            this->d_point_id, this->d_offs, this->d_status, d_lds_dense);
+        return std::make_tuple(this->cube_size, this->grid_size, this->n_cubes, gabriel_coefficient,
+            d_gabriel_coefficients, this->d_cube_id, this->d_point_id, this->d_offs, this->d_status, d_lds_dense);
     }
 
     // A memset and six launches: the counters, the grid of every replica from d_in, then the forces.
@@ -430,9 +453,9 @@ protected:
         const int blocks = (n_max + ya::GABRIEL_CELLS - 1) / ya::GABRIEL_CELLS;
         ya::ens::gabriel_force_batched<Pt, pw_int, pw_friction><<<this->grid_of(blocks), 64>>>(n_max, blocks, this->d_n,
             this->d_sorted, this->d_sorted_v, this->d_cube_id, this->d_offs, this->grid_size, this->n_cubes,
-            this->cube_size, gabriel_coefficient, d_rhs, has_gen, d_dense + 2, d_dense);
+            this->cube_size, gabriel_coefficient, d_gabriel_coefficients, d_rhs, has_gen, d_dense + 2, d_dense);
         ya::ens::gabriel_force_dense_batched<Pt, pw_int, pw_friction><<<dense_blocks, 64>>>(n_max, d_dense + 2, d_dense,
             this->d_sorted, this->d_sorted_v, this->d_cube_id, this->d_offs, this->grid_size, this->n_cubes,
-            this->cube_size, gabriel_coefficient, d_rhs, has_gen, d_workspace);
+            this->cube_size, gabriel_coefficient, d_gabriel_coefficients, d_rhs, has_gen, d_workspace);
     }
 };

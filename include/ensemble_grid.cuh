@@ -54,7 +54,10 @@
 // SHARED  The build, its arrays and the status code are ya::ens::Grid_form (below), which Ensemble<Pt, Gabriel_solver>
 // (ensemble_gabriel.cuh) derives from too.
 //
-// Not here: the fast-arithmetic tier, graph capture, a per-replica dt, cube_size or grid_size, the sorted-space
+// PER-REPLICA dt  take_step / take_steps with ya::ens::Replica_dt{d_dt} in place of dt (ensemble.cuh's header): every
+// path of this form, the linked ones included.
+//
+// Not here: the fast-arithmetic tier, graph capture, a per-replica cube_size or grid_size, the sorted-space
 // second stage, grid_force_bits' tails, slabs.
 #pragma once
 
@@ -600,7 +603,7 @@ __device__ __forceinline__ void grid_lds_walk_coop(const int n, const int id_bas
 // Not here: the fast tier, graph capture (the Gabriel form's launch is ya::ens::gabriel_lds_steps, ensemble_gabriel.cuh).
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, bool LINKED, int LANES = 1>
 __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
     float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status, const Links_view links = Links_view{})
@@ -623,7 +626,8 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
     const int tile = layout.tile;
     const int id_base = replica * n_max;
     bool outside = false;
-    whole_steps_in_lds<Pt>(n_max, n, replica, dt, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
+    const float dt_r = value_of(d_dt, dt, replica);  // (d_dt[r] where the call has a time step per replica)
+    whole_steps_in_lds<Pt>(n_max, n, replica, dt_r, n_steps, kind1, kind2, fix_point, d_X_all, d_old_v_all, grid_step_lds,
         [&](const Pt* sh_in, const float3* sh_v, Pt* sh_rhs) __attribute__((always_inline)) {
             if constexpr (LINKED) whole_stage_links<Pt>(n, sh_in, sh_rhs, sh_off, sh_ent, links.strength);
             outside |= grid_lds_order<Pt>(n, sh_in, cs, gs, n_cubes, sh_key);
@@ -658,12 +662,12 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
 }
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2,
+    const int fix_point, Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status)
 {
-    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, false, LANES>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, false, LANES>(n_max, d_n, dt, d_dt, n_steps, kind1, kind2, fix_point,
         d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status);
 }
 // The same steps with the ordered link forces of `links` (ensemble_links.cuh) at the start of every stage: bit for
@@ -673,12 +677,12 @@ __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, 
 // writes.  No atomics but the status bit, no scratch, no cooperative launch.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps_linked(const int n_max, const int* __restrict__ d_n,
-    const float dt, const int n_steps, const int kind1, const int kind2, const int fix_point, Pt* __restrict__ d_X_all,
-    float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
+    const float dt, const float* __restrict__ d_dt, const int n_steps, const int kind1, const int kind2,
+    const int fix_point, Pt* __restrict__ d_X_all, float3* __restrict__ d_old_v_all, const float cs, const int gs, const int n_cubes, const float cut2,
     const bool by_plane, int* __restrict__ d_cube_id_all, int* __restrict__ d_point_id_all, int* __restrict__ d_offs_all,
     int* __restrict__ d_status, const Links_view links)
 {
-    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, true, LANES>(n_max, d_n, dt, n_steps, kind1, kind2, fix_point,
+    grid_lds_steps_of_a_replica<Pt, pw_int, pw_friction, true, LANES>(n_max, d_n, dt, d_dt, n_steps, kind1, kind2, fix_point,
         d_X_all, d_old_v_all, cs, gs, n_cubes, cut2, by_plane, d_cube_id_all, d_point_id_all, d_offs_all, d_status,
         links);
 }
@@ -917,6 +921,28 @@ public:
         this->template steps<pw_int, pw_friction>(dt, n_steps, links);
     }
 
+    // The same calls with replica r's own time step dt.d_dt[r] (ensemble.cuh's header): the same plan, the same launches.
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, Generic_forces<Pt> gen_forces = no_gen_forces<Pt>)
+    {
+        this->template steps<pw_int, pw_friction>(dt, n_steps, gen_forces);
+    }
+    template<Pairwise_interaction<Pt> pw_int>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, ya::ens::Replica_links links)
+    {
+        take_steps<pw_int, friction_w_neighbour<Pt>>(dt, n_steps, links);
+    }
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction>
+    void take_steps(ya::ens::Replica_dt dt, int n_steps, ya::ens::Replica_links links)
+    {
+        this->template steps<pw_int, pw_friction>(dt, n_steps, links);
+    }
+
 protected:
     // What ya::ens::Stepper's launches from LDS ask of a form: the layout has keys; the settings above; the kernels,
     // which read the tile length from the layout themselves.
@@ -928,8 +954,8 @@ protected:
             ya::ens::lds_steps_pay(this->n_replicas, this->n_max, this->n_cubes), lds_steps_max, lds_step_lanes,
             ya::ens::grid_lds_lanes_for(this->n_max), &lds_step_launches, &lds_step_lanes_used};
     }
-    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED>
-    static auto lds_kernel()
+    template<Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES, bool LINKED, bool REPLICA_DT>
+    static auto lds_kernel()  // (REPLICA_DT: the kernel decides at run time)
     {
         if constexpr (LINKED)
             return &ya::ens::grid_lds_steps_linked<Pt, pw_int, pw_friction, LANES>;

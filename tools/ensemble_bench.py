@@ -13,6 +13,7 @@
     python tools/ensemble_bench.py --solver gabriel --lds-steps [--out profiles/ensemble_gabriel_lds_steps_bench.json]
     python tools/ensemble_bench.py --links [--out profiles/ensemble_links_bench.json]
     python tools/ensemble_bench.py --solver grid --links [--out profiles/ensemble_grid_links_bench.json]
+    python tools/ensemble_bench.py --replica-dt [--baseline-libs DIR --baseline-commit HASH] [--out profiles/ensemble_replica_dt_bench.json]
 
 In ONE process, after a warm-up of every shape, the two ways alternate (A, B with each lanes setting, A, B ...):
   A  M Solution("relu_tile", n) objects, one take_step each, round-robin -- how a sweep over M systems runs
@@ -74,6 +75,15 @@ step from LDS of up to 256 steps each (lds_steps 1).  M in {1, 16, 64, 256, 1024
 1024} (`--shapes M:n,...` for others; `--steps-per-launch 1` adds launches of ONE step each as a third setting:
 what a caller of take_steps(dt, 1) pays), then the balls ensemble of the tests (48 replicas of K + 1 <= 258 cells, K candidates per cell: the dense path
 inside the launch from K = 65 on; its rates count n_max rows per replica).  Each setting's spread is recorded.
+
+--replica-dt: what a time step per replica costs the scalar call.  Per shape ONE SweepEnsemble("relu") timed twice,
+with a scalar dt and with an array of M equal values (ya::ens::Replica_dt), alternating with the existing class of the
+same shape and settings (Ensemble / GabrielEnsemble, this tree's libraries) and -- with --baseline-libs DIR, a directory
+that holds libyalla_ensemble.so and libyalla_ensemble_gabriel.so built from another commit (--baseline-commit HASH says
+which, for the record) -- with that class on those libraries, all in one process under the protocol above.  The shapes: all-pairs M = 64, n = 800, six launches; all-pairs
+M = 256, n = 64, whole steps with the engine's lanes; Gabriel M = 64, n = 256, 16 launches.  Each setting's rate and
+spread are recorded; `agrees` says whether the sweep object's scalar rate and the baseline's (the existing class
+where there is no DIR) differ by at most the larger of their two spreads.  A figure that was not taken is "not measured".
 """
 import argparse
 import json
@@ -86,8 +96,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from yalla_amd import _ffi  # noqa: E402
 from yalla_amd.ensemble import (Ensemble, GabrielEnsemble, GabrielLdsEnsemble, GridEnsemble, LinkedEnsemble,  # noqa: E402
-                                LinkedGridEnsemble)
+                                LinkedGridEnsemble, SweepEnsemble)
 from yalla_amd.solution import Solution  # noqa: E402
 
 SHAPES = [(m, n) for n in (100, 800, 2000) for m in (1, 8, 64, 256)] + [(1024, 100)]
@@ -262,6 +273,116 @@ class LinkedGrid:
 
     def close(self):
         self.ens.close()
+
+
+# --replica-dt: (name, form, M, n, the sweep object's settings, the existing class's)
+REPLICA_DT_CASES = [
+    ("all_pairs_six_launches", "tile", 64, 800, {"whole_steps": -1}, {"whole_steps": -1}),
+    ("all_pairs_whole_steps", "tile", 256, 64, {"whole_steps": 1, "whole_step_lanes": 0},
+     {"whole_steps": 1, "whole_step_lanes": 0}),
+    ("gabriel_sixteen_launches", "gabriel", 64, 256, {"lds_steps": -1}, {}),
+]
+
+
+class Sweep:
+    """One SweepEnsemble("relu") of the shape; array: stepped with M equal values of DT instead of the scalar."""
+
+    def __init__(self, form, m, n, params):
+        self.ens = SweepEnsemble(form, "relu", m, n, grid_size=grid_size_for(n))
+        for name, value in params.items():
+            self.ens.set_param(name, value)
+        for r in range(m):
+            self.ens.h_X[r] = ball(n, r)
+        self.ens.copy_to_device()
+
+    def setting(self, array):
+        self.ens.dt = np.full(self.ens.n_replicas, DT, np.float32) if array else None
+
+    def steps(self, k):
+        self.ens.take_step(DT, k)
+        self.ens.synchronize()
+
+    def close(self):
+        self.ens.close()
+
+
+class Existing(Sweep):
+    """The existing class of the form, on this tree's library or on the one in `libs` (another commit's build)."""
+
+    def __init__(self, form, m, n, params, libs=None):
+        name, table = (("libyalla_ensemble.so", _ffi.ENSEMBLE_ABI) if form == "tile"
+                       else ("libyalla_ensemble_gabriel.so", _ffi.GABRIEL_ENSEMBLE_ABI))
+        lib = _ffi._load(os.path.join(os.path.abspath(libs), name), table) if libs else None
+        self.ens = Ensemble("relu", m, n, lib=lib) if form == "tile" else GabrielEnsemble(
+            "relu", m, n, grid_size_for(n), 1.0, lib=lib)
+        for name, value in params.items():
+            self.ens.set_param(name, value)
+        for r in range(m):
+            self.ens.h_X[r] = ball(n, r)
+        self.ens.copy_to_device()
+
+    def setting(self, array):
+        pass
+
+
+def measure_replica_dt(case, window, repeats, libs):
+    name, form, m, n, params, existing_params = case
+    sweep = Sweep(form, m, n, params)
+    runs = {"sweep_scalar_dt": (sweep, False), "sweep_array_of_equal_dt": (sweep, True),
+            "existing_class": (Existing(form, m, n, existing_params), False)}
+    if libs:
+        runs["baseline_libs_existing_class"] = (Existing(form, m, n, existing_params, libs), False)
+    try:
+        ks = {}
+        for key, (run, array) in runs.items():
+            run.setting(array)
+            run.steps(5)
+            ks[key] = calibrate(run, window)
+        samples = {key: [] for key in runs}
+        for _ in range(repeats):  # scalar, array, existing[, baseline], scalar, ...
+            for key, (run, array) in runs.items():
+                run.setting(array)
+                samples[key].append(timed(run, ks[key]))
+        launches = sweep.ens.lds_launches
+    finally:
+        for run in {id(run): run for run, _ in runs.values()}.values():
+            run.close()
+    row = {"shape": name, "form": form, "n_replicas": m, "n": n, "launches_from_lds": launches}
+    for key in runs:
+        row[key] = summary(samples[key], m * n, ks[key])
+    baseline = "baseline_libs_existing_class" if libs else "existing_class"
+    if not libs:
+        row["baseline_libs_existing_class"] = "not measured"
+    mine, theirs = row["sweep_scalar_dt"], row[baseline]
+    row["compared_with"] = baseline
+    row["ratio_scalar_over_baseline"] = mine["cell_updates_per_s"] / theirs["cell_updates_per_s"]
+    row["ratio_array_over_scalar"] = row["sweep_array_of_equal_dt"]["cell_updates_per_s"] / mine["cell_updates_per_s"]
+    row["larger_spread"] = max(mine["spread"], theirs["spread"])
+    row["agrees"] = abs(mine["cell_updates_per_s"] - theirs["cell_updates_per_s"]) <= row["larger_spread"] * max(
+        mine["cell_updates_per_s"], theirs["cell_updates_per_s"])
+    return row
+
+
+def main_replica_dt(args):
+    rows = []
+    for case in REPLICA_DT_CASES:
+        rows.append(measure_replica_dt(case, args.window, args.repeats, args.baseline_libs))
+        r = rows[-1]
+        keys = [key for key in r if isinstance(r[key], dict)]
+        print(f"{r['shape']:26s} M {r['n_replicas']:4d}  n {r['n']:4d}   "
+              + "  ".join(f"{key}: {r[key]['us_per_step']:8.2f} us/step ({r[key]['spread']:.3f})" for key in keys)
+              + f"   scalar / {r['compared_with']} {r['ratio_scalar_over_baseline']:.3f}  agrees {r['agrees']}", flush=True)
+        if args.out:  # after every shape: a run that is cut short leaves the shapes it finished
+            result = {"tool": "tools/ensemble_bench.py --replica-dt", "model": "relu", "dt": DT, "window_s": args.window,
+                      "repeats": args.repeats,
+                      "baseline_commit": (args.baseline_commit or "not recorded") if args.baseline_libs else "not measured",
+                      "rows": rows}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print(json.dumps({"shapes": len(rows), "agree": [r["agrees"] for r in rows],
+                      "ratio_scalar_over_baseline": [round(r["ratio_scalar_over_baseline"], 4) for r in rows]}))
 
 
 def timed(run, k):
@@ -694,7 +815,17 @@ def main():
     ap.add_argument("--lds-step-lanes", default=None, metavar="L,L,...",
                     help="with --solver grid --lds-steps: these lds_step_lanes settings against lanes 1 of the same "
                          "ensemble, the 14-launch step beside them")
+    ap.add_argument("--replica-dt", action="store_true",
+                    help="one SweepEnsemble with a scalar dt and with an array of equal values against the existing class")
+    ap.add_argument("--baseline-libs", default=None, metavar="DIR",
+                    help="with --replica-dt: libyalla_ensemble.so and libyalla_ensemble_gabriel.so of another commit's build")
+    ap.add_argument("--baseline-commit", default=None, metavar="HASH", help="the commit those libraries were built from")
     args = ap.parse_args()
+    if args.replica_dt:
+        if args.trace_shape or args.whole_steps or args.links or args.lds_steps or args.solver != "tile":
+            ap.error("--replica-dt measures its three shapes on its own")
+        main_replica_dt(args)
+        return
     global GRID, GABRIEL, GABRIEL_LDS, LANES, SHAPES
     if args.lds_step_lanes and not args.lds_steps:
         ap.error("--lds-step-lanes goes with --solver grid --lds-steps")

@@ -16,3 +16,4 @@ tests/ and bench.py: a ctypes binding and a mirror of the Solution facade.
 from ._ffi import device_lib, bind, DEVICE_LIB, CORE_LIB  # noqa: F401
 from .solution import Solution, YallaError, models  # noqa: F401
 from .ensemble import Ensemble, GabrielEnsemble, GabrielLdsEnsemble, GridEnsemble, LinkedEnsemble  # noqa: F401
+from .ensemble import SweepEnsemble  # noqa: F401

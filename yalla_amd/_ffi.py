@@ -20,6 +20,7 @@ GABRIEL_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel.so")  # in
 GABRIEL_LDS_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_gabriel_lds.so")  # include/yalla_ensemble_gabriel_lds.h
 LINKED_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_links.so")  # include/yalla_ensemble_links.h
 LINKED_GRID_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_grid_links.so")  # include/yalla_ensemble_grid_links.h
+SWEEP_ENSEMBLE_LIB = os.path.join(_HERE, "libyalla_ensemble_sweep.so")  # include/yalla_ensemble_sweep.h
 
 _pf = C.POINTER(C.c_float)
 _pi = C.POINTER(C.c_int)
@@ -139,6 +140,26 @@ LINKED_GRID_ENSEMBLE_ABI["ya_glens_set_n_links"] = (C.c_int, [_ens, C.c_int])
 LINKED_GRID_ENSEMBLE_ABI["ya_glens_get_n_links"] = (C.c_int, [_ens])
 LINKED_GRID_ENSEMBLE_ABI["ya_glens_lds_bytes"] = (C.c_long, [C.c_char_p, C.c_int, C.c_int])
 
+# name -> (restype, argtypes); mirrors include/yalla_ensemble_sweep.h one to one: the shared entry points of the other
+# harnesses under the prefix ya_swp_ (the model tables and create take the form's name), the grid forms' and the links'
+# entry points, and what a time step and a Gabriel coefficient per replica add.
+SWEEP_ENSEMBLE_ABI = {name.replace("ya_ens_", "ya_swp_"): sig for name, sig in ENSEMBLE_ABI.items()}
+SWEEP_ENSEMBLE_ABI["ya_swp_models_count"] = (C.c_int, [C.c_char_p])
+SWEEP_ENSEMBLE_ABI["ya_swp_models_name"] = (C.c_char_p, [C.c_char_p, C.c_int])
+SWEEP_ENSEMBLE_ABI["ya_swp_create"] = (
+    C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(_ens)])
+SWEEP_ENSEMBLE_ABI["ya_swp_status"] = (C.c_int, [_ens, C.c_int, C.c_int])
+SWEEP_ENSEMBLE_ABI["ya_swp_get_grid"] = (C.c_int, [_ens, C.c_int, _pi, _pi, _pi, _pi])
+SWEEP_ENSEMBLE_ABI["ya_swp_h_link"] = (_pi, [_ens])
+SWEEP_ENSEMBLE_ABI["ya_swp_set_n_links"] = (C.c_int, [_ens, C.c_int])
+SWEEP_ENSEMBLE_ABI["ya_swp_get_n_links"] = (C.c_int, [_ens])
+SWEEP_ENSEMBLE_ABI["ya_swp_set_dt"] = (C.c_int, [_ens, _pf])
+SWEEP_ENSEMBLE_ABI["ya_swp_set_gabriel_coefficients"] = (C.c_int, [_ens, _pf])
+SWEEP_ENSEMBLE_ABI["ya_swp_scale_dt"] = (C.c_int, [_ens, C.c_float])
+SWEEP_ENSEMBLE_ABI["ya_swp_lanes_used"] = (C.c_int, [_ens])
+SWEEP_ENSEMBLE_ABI["ya_swp_dense_cells"] = (C.c_int, [_ens])
+SWEEP_ENSEMBLE_ABI["ya_swp_lds_dense_cells"] = (C.c_longlong, [_ens])
+
 # include/yalla_hip.h, for the export check (no compute calls without a GPU).
 CORE_ABI = [
     "ya_abi_version", "ya_malloc", "ya_free", "ya_memset_async", "ya_memcpy_h2d",
@@ -237,3 +258,10 @@ def linked_grid_ensemble_lib():
     (include/yalla_ensemble_grid_links.h), every entry point typed.  Raises if it has not been built: there is no
     fallback."""
     return _load(LINKED_GRID_ENSEMBLE_LIB, LINKED_GRID_ENSEMBLE_ABI)
+
+
+@functools.lru_cache(maxsize=None)  # (the same object on every call)
+def sweep_ensemble_lib():
+    """The sweep harness, yalla_amd/libyalla_ensemble_sweep.so (include/yalla_ensemble_sweep.h), every entry point
+    typed.  Raises if it has not been built: there is no fallback."""
+    return _load(SWEEP_ENSEMBLE_LIB, SWEEP_ENSEMBLE_ABI)

@@ -28,7 +28,8 @@ largest L with n_max * L <= 256.  Any other value is refused (-3).  Every choice
 build per stage (or whole steps from LDS, `lds_steps`); `GabrielEnsemble` for M Gabriel_solver systems (include/ensemble_gabriel.cuh),
 `GabrielLdsEnsemble` the same with whole steps from LDS (`lds_steps`, libyalla_ensemble_gabriel_lds.so);
 `LinkedEnsemble` for M all-pairs systems with link forces summed in slot order (include/ensemble_links.cuh);
-`LinkedGridEnsemble` the same for M Grid_solver systems, inside launches that step from LDS too.
+`LinkedGridEnsemble` the same for M Grid_solver systems, inside launches that step from LDS too;
+`SweepEnsemble` any of the three forms with a time step (and a Gabriel coefficient) per replica.
 """
 import ctypes as C
 
@@ -444,6 +445,154 @@ class LinkedGridEnsemble(GridEnsemble):
         if code < 0:
             raise YallaError(f"ya_glens_lds_bytes({model!r}, {n_max}, {slots_per_replica}) failed with {code}")
         return code
+
+
+class SweepEnsemble(GridEnsemble):
+    """The three forms of Ensemble behind one class (include/yalla_ensemble_sweep.h, libyalla_ensemble_sweep.so), stepped
+    with A TIME STEP PER REPLICA (ya::ens::Replica_dt) and, form "gabriel", A COEFFICIENT PER REPLICA
+    (Ensemble<Pt, Gabriel_solver>::d_gabriel_coefficients).  form: "tile", "grid" or "gabriel"; the models of each:
+    `sweep_models(form)`.  Replica r holds, bit for bit, what a lone `Solution("<model>_<form>", n_max, ...)` of its rows
+    holds when stepped with dt[r] (and gabriel_coefficients[r]).
+
+        with SweepEnsemble("tile", "relu", n_replicas=64, n_max=200) as cells:
+            ...; cells.copy_to_device()
+            cells.dt = np.linspace(0.01, 0.1, 64)     # uploaded; None returns to the scalar of take_step(dt)
+            cells.take_step(steps=100)                # replica r with dt[r]
+            cells.scale_dt(0.5); cells.take_step(steps=100)   # the array changed ON THE DEVICE, no synchronise
+
+    `dt` and `gabriel_coefficients` read back what was set (float32), not what a kernel made of it since.  What the
+    form's own class offers is here under the same names: grid(r), status(r) and the cube_size setter ("grid",
+    "gabriel"), h_link and n_links (a model with links, slots_per_replica > 0), dense_cells() and lds_dense_cells()
+    ("gabriel"), and set_param with "whole_steps", "whole_step_lanes" ("tile"), "lds_steps" ("grid", "gabriel"),
+    "lds_step_lanes" ("grid"), "steps_per_launch" (every form), "gabriel_coefficient", "cube_size".  `lds_launches` counts
+    the launches that stepped from LDS (whole-step launches of form "tile"), `lanes_used` is the lanes per cell of the
+    last one."""
+    _PREFIX, _LOADER, _NOUN = "ya_swp_", "sweep_ensemble_lib", "sweep ensemble"
+    FORMS = ("tile", "grid", "gabriel")
+
+    def __init__(self, form, model, n_replicas, n_max, slots_per_replica=0, grid_size=50, cube_size=1.0,
+                 gabriel_coefficient=0.8, lib=None):
+        self.lib = lib if lib is not None else _ffi.sweep_ensemble_lib()
+        handle = C.c_void_p()
+        code = self._f("create")(form.encode(), model.encode(), int(n_replicas), int(n_max), int(slots_per_replica),
+                                 int(grid_size), C.c_float(cube_size), C.c_float(gabriel_coefficient), C.byref(handle))
+        if code == -4:
+            raise YallaError(f"unknown form {form!r}; known: {list(self.FORMS)}")
+        if code == -1:
+            raise YallaError(f"unknown {form} sweep model {model!r}; known: {sweep_models(form, self.lib)}")
+        _check(code, "ya_swp_create")
+        self._attach(model, handle, n_replicas, n_max)
+        self.form = form
+        self.grid_size = int(grid_size)
+        self.slots_per_replica = int(slots_per_replica)
+        self._dt = self._coefficients = None
+        shape = (self.n_replicas, self.slots_per_replica, 2)
+        if self.n_replicas * self.slots_per_replica > 0:
+            self.h_link = np.ctypeslib.as_array(self._f("h_link")(self._h), shape=shape)
+        else:
+            self.h_link = np.zeros(shape, np.int32)
+
+    def close(self):
+        self.h_link = None
+        super().close()
+
+    n_links = LinkedEnsemble.n_links
+
+    def _per_replica(self, values, what):
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        if values.shape != (self.n_replicas,):
+            raise ValueError(f"{what} takes {self.n_replicas} values, one per replica, not an array of shape {values.shape}")
+        return values.copy()
+
+    @property
+    def dt(self):
+        """The time steps set last, one per replica (float32), or None: take_step steps with its scalar."""
+        return None if self._dt is None else self._dt.copy()
+
+    @dt.setter
+    def dt(self, values):
+        if values is None:
+            _check(self._f("set_dt")(self._h, None), "set dt")
+            self._dt = None
+            return
+        values = self._per_replica(values, "dt")
+        _check(self._f("set_dt")(self._h, values.ctypes.data_as(C.POINTER(C.c_float))), "set dt")
+        self._dt = values
+
+    @property
+    def gabriel_coefficients(self):
+        """The coefficients set last, one per replica (float32), or None: every replica uses "gabriel_coefficient"."""
+        return None if self._coefficients is None else self._coefficients.copy()
+
+    @gabriel_coefficients.setter
+    def gabriel_coefficients(self, values):
+        if values is None:
+            _check(self._f("set_gabriel_coefficients")(self._h, None), "set gabriel_coefficients")
+            self._coefficients = None
+            return
+        values = self._per_replica(values, "gabriel_coefficients")
+        _check(self._f("set_gabriel_coefficients")(self._h, values.ctypes.data_as(C.POINTER(C.c_float))),
+               "set gabriel_coefficients")
+        self._coefficients = values
+
+    def scale_dt(self, factor):
+        """Multiplies the device's dt array by `factor` (binary32), by a kernel queued behind the steps so far and not
+        waited for: what a model's own adaptive-dt kernel does.  `dt` keeps reading what was set."""
+        _check(self._f("scale_dt")(self._h, C.c_float(factor)), "scale_dt")
+
+    def take_step(self, dt=None, steps=1):
+        """`steps` Heun steps of every replica: with the array `dt` was set to, or with the scalar given here."""
+        if dt is None and self._dt is None:
+            raise ValueError("take_step needs a dt: set the dt property or pass a scalar")
+        super().take_step(0.0 if dt is None else dt, steps)
+
+    @property
+    def whole_step_launches(self):
+        return self._whole_step_launches
+
+    lds_launches = lds_step_launches = whole_step_launches
+
+    @property
+    def lanes_used(self):
+        return self._f("lanes_used")(self._h)
+
+    lds_step_lanes_used = whole_step_lanes_used = lanes_used
+
+    @property
+    def gabriel_coefficient(self):
+        raise AttributeError("gabriel_coefficient is write-only here")
+
+    @gabriel_coefficient.setter
+    def gabriel_coefficient(self, value):
+        self.set_param("gabriel_coefficient", value)
+
+    @property
+    def cube_size(self):
+        raise AttributeError("cube_size is write-only here")
+
+    @cube_size.setter
+    def cube_size(self, value):
+        self.set_param("cube_size", value)
+
+    def dense_cells(self):
+        n = self._f("dense_cells")(self._h)
+        if n < 0:
+            raise YallaError(f"dense_cells() failed with harness code {n}")
+        return n
+
+    def lds_dense_cells(self):
+        n = self._f("lds_dense_cells")(self._h)
+        if n < 0:
+            raise YallaError(f"lds_dense_cells() failed with harness code {n}")
+        return n
+
+
+def sweep_models(form, lib=None):
+    lib = lib if lib is not None else _ffi.sweep_ensemble_lib()
+    count = lib.ya_swp_models_count(form.encode())
+    if count < 0:
+        raise YallaError(f"unknown form {form!r}; known: {list(SweepEnsemble.FORMS)}")
+    return [lib.ya_swp_models_name(form.encode(), i).decode() for i in range(count)]
 
 
 def linked_grid_models(lib=None):
