@@ -2078,6 +2078,21 @@ __global__ void make_fix(int mode, const float* __restrict__ d_mean,
     }
 }
 
+// A fixed velocity that was computed in registers, `sum * float(1. / n)`, as the ROUNDED binary32 value that
+// ya_reduce_mean would have left in memory.  The fast-arithmetic tier (YA_ARITH_FAST, -ffp-contract=fast, which
+// disregards `#pragma clang fp contract(off)`; __fmul_rn is a plain `*` in HIP) is otherwise free to fuse the product
+// into the update kernels' `dX - fix`, and did so in one instantiation (one use: v_fma_f32 d, -inv, sum, dX) and not
+// in another (the four tiles of heun_step_sorted<Pt, true, 4> use it four times: v_mul_f32, v_sub_f32):
+// take_step(dt, k) and k calls of take_step(dt, 1) then differed by one rounding of the centre-of-mass velocity per
+// stage (tests/test_fast_tier_carry_gpu.py).  The empty statement makes the three values opaque to the optimiser
+// where they are, in vector registers, and emits no instruction.  Without contraction there is nothing to fuse, and
+// the exact tier is compiled without the statement: its instructions and their order stay what they were.
+__device__ __forceinline__ void round_fix(float3& fix)
+{
+#ifdef YA_ARITH_FAST
+    asm volatile("" : "+v"(fix.x), "+v"(fix.y), "+v"(fix.z));
+#endif
+}
 // The fixed velocity from a z-slab stage's ALL-REDUCED totals (ya_slab_pack on every rank, summed):
 // {sum[n_floats], count in two pieces, two votes, the fixed point's right-hand side}.
 // fix_mode 0 (set_fixed()): fix = sum * float(1. / n), the reference's Pt / n arithmetic
@@ -2088,7 +2103,8 @@ __device__ __forceinline__ float3 fix_from_total(const float* __restrict__ total
 {
     const double n = (double)total[n_floats] + 4096. * (double)total[n_floats + 1];
     const float inv = (float)(1. / (double)(float)n);
-    const float3 mean{total[0] * inv, total[1] * inv, total[2] * inv};
+    float3 mean{total[0] * inv, total[1] * inv, total[2] * inv};
+    round_fix(mean);
     if (fix_mode == 0) return mean;
     const float* point = total + n_floats + 4;
     return float3{point[0], point[1], fix_mode == 1 ? point[2] : mean.z};
@@ -2142,7 +2158,9 @@ __device__ __forceinline__ float3 fixed_velocity_from_partials(const float* __re
     }
     fold256<3>(acc, sh);
     const float inv = (float)(1. / (double)(float)n);  // Pt / n == Pt * float(1. / float(n))
-    return float3{sh[0] * inv, sh[UPDATE_BLOCK] * inv, sh[2 * UPDATE_BLOCK] * inv};
+    float3 mean{sh[0] * inv, sh[UPDATE_BLOCK] * inv, sh[2 * UPDATE_BLOCK] * inv};
+    round_fix(mean);
+    return mean;
 }
 
 // Where an update kernel takes a stage's fixed velocity from (solvers.cuh:241-253,265-272).  A template
@@ -2167,7 +2185,9 @@ struct Sorted_buffers {
     const Pt* carried_rhs = nullptr;     // stage 2's right-hand sides in stage 2's sorted order
     const int* carried_slots = nullptr;  // stage-1 slot -> stage-2 slot
 };
-// Every thread of the workgroup calls it, before any early return: the partials fold has barriers.
+// Every thread of the workgroup calls it, before any early return: the partials fold has barriers.  What it
+// returns is rounded (a value from memory is; a mean computed here goes through round_fix), so every update kernel
+// subtracts the same bits whatever the contraction mode and however often it uses them.
 template<Fix_src S, typename Pt>
 __device__ __forceinline__ float3 resolve_fix(const Fix_args& f, const int n)
 {

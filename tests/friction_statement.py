@@ -56,6 +56,11 @@ def friction_w_neighbour(Xi, r, dist, i, j, real=f32):
     return np.where((i != j) & (dist < real(1)), real(1), real(0)).astype(real)
 
 
+def friction_on_background(Xi, r, dist, i, j, real=f32):
+    """return 0;  (solvers.cuh:37-41: sum_friction stays 0 and the stage's right-hand side is F alone)"""
+    return np.zeros(np.shape(dist), real)
+
+
 # ---- the forces (on x, y, z; `Pt dF{0}` leaves the further fields of a wide point without force) ------------------
 def relu_force(Xi, r, dist, i, j, real=f32):
     c = real(f32(0.8))

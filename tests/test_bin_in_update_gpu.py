@@ -8,69 +8,12 @@ Compared are the bit patterns of X, old_v, the count and the four public grid ar
 that the rebuilds really ran without k_bin (2 k - 1 per carried call of k steps) and `carried_steps()` that the call
 was carried: no case can pass on a fallback.  No case takes a cell out of its grid.
 """
-import functools
-
 import numpy as np
 import pytest
 
-from yalla_amd.solution import Solution
+from carry_support import GRID_KEYS, GS, Before_call, advance, carried_and_fused, cube_changes, same, single_steps
 
 pytestmark = pytest.mark.gpu
-
-GS = 16
-SPHERE = (0.5, 42)
-GRID_KEYS = ("cube_id", "point_id", "cube_start", "cube_end")
-
-
-def snapshot(s):
-    X = s.positions()  # (copy_to_host: h_n becomes the device's count)
-    n = s.get_d_n()
-    cube_id, point_id, cube_start, cube_end = s.grid()
-    return {"X": X, "old_v": s.old_v()[:n].copy(), "n": n, "cube_id": cube_id[:n].copy(),
-            "point_id": point_id[:n].copy(), "cube_start": cube_start, "cube_end": cube_end}
-
-
-def same(a, b):
-    assert a.keys() == b.keys()
-    for key in a:
-        if key == "n":
-            assert a[key] == b[key], key
-        else:
-            assert a[key].shape == b[key].shape, key
-            assert np.array_equal(np.ascontiguousarray(a[key]).view(np.uint32),
-                                  np.ascontiguousarray(b[key]).view(np.uint32)), key
-
-
-def advance(model, n, calls, dt, *, n_max=None, gs=GS, params=(), sphere=SPHERE, between=None):
-    """The system after take_step(dt, c) for every c of `calls` (between(s) in between two of them): a snapshot after
-    every call, the counters, and the positions it started from."""
-    snaps = []
-    with Solution(model, n_max or n, gs, 1.0) as s:
-        for name, value in params:
-            s.set_param(name, value)
-        s.h_n = n
-        s.random_sphere(*sphere)
-        first = s.h_X[:n].copy()
-        for i, c in enumerate(calls):
-            if i and between:
-                between(s)
-            s.take_step(dt, c)
-            snaps.append(snapshot(s))
-        counters = {"carried": s.carried_steps(), "fused": s.fused_bin_rebuilds()}
-    return snaps, counters, first
-
-
-@functools.lru_cache(maxsize=None)
-def single_steps(model, n, n_max, steps, dt, params=(), gs=GS, sphere=SPHERE):
-    """Snapshots after each of `steps` one-step calls (the reference, shared by the cases that start alike)."""
-    snaps, counters, first = advance(model, n, [1] * steps, dt, n_max=n_max, gs=gs, params=params, sphere=sphere)
-    assert counters == {"carried": 0, "fused": 0}
-    return snaps, first
-
-
-def carried_and_fused(calls):
-    carried = [c for c in calls if c >= 2]
-    return {"carried": sum(c - 1 for c in carried), "fused": sum(2 * c - 1 for c in carried)}
 
 
 # ---- the switch ----------------------------------------------------------------------------------------------------
@@ -130,10 +73,6 @@ def test_runs_longer_than_a_wavefront():
 
 # ---- cells that change cube between steps --------------------------------------------------------------------------
 
-def cube_changes(before, after):
-    return int(np.any(np.floor(before[:, :3]) != np.floor(after[:, :3]), axis=1).sum())
-
-
 @pytest.mark.parametrize("model, dt", [("springs_grid", 0.02), ("relu_grid", 0.05)])
 def test_cells_that_change_cube(model, dt):
     """Large steps: hundreds of the 3000 cells sit in another cube after every step, so an update kernel that binned
@@ -162,18 +101,6 @@ def test_counters_are_zero_between_calls(calls):
     assert counters == carried_and_fused(calls)
     for snap, steps in zip(got, np.cumsum(calls)):
         same(snap, ref[steps - 1])
-
-
-class Before_call:
-    """`between` of a run in single steps: `action` before the call-th call (0-based), nothing before the others."""
-
-    def __init__(self, action, call):
-        self.action, self.call, self.seen = action, call, 0
-
-    def __call__(self, s):
-        self.seen += 1
-        if self.seen == self.call:
-            self.action(s)
 
 
 def test_fewer_cells_and_other_positions_between_two_calls():
