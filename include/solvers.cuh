@@ -513,6 +513,15 @@ __device__ __forceinline__ float coop_ordered_sum(float sum, const float* terms,
 // the functor is called for one i from several lanes at once, so functors that update per-cell
 // state non-atomically (d_mes_nbs[i] += 1, examples/passive_growth.cu:48-51) must keep the
 // default of one lane per cell.
+// Partners per tile of that kernel: a multiple of 64, at most 512, whose terms -- N_floats + 4 components for each of the
+// workgroup's 256 / COOP_LANES cells -- fill at most 56 KiB of LDS.  Less than 64 (16 lanes per cell from 11 floats on)
+// means that the kernel does not exist for the type: Tile_computer asks before it names it.
+template<typename Pt, int COOP_LANES>
+constexpr int tile_coop_partners()
+{
+    constexpr int fit = (57344 / ((256 / COOP_LANES) * (N_floats<Pt>::value + 4) * 4)) / 64 * 64;
+    return fit > 512 ? 512 : fit;
+}
 // The body, with tile_force_rows' arguments: the workgroup serves 256 / COOP_LANES of the system's rows.
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int COOP_LANES>
 __device__ __forceinline__ void tile_force_coop_rows(const int n, const int block, const int id_base,
@@ -522,7 +531,7 @@ __device__ __forceinline__ void tile_force_coop_rows(const int n, const int bloc
     constexpr int NF = N_floats<Pt>::value;
     constexpr int NC = NF + 4;  // components summed per cell: F (NF), friction, friction * old_v (3)
     // partners per tile: a multiple of 64 whose terms fill at most 56 KiB of LDS
-    constexpr int TILE = (57344 / (COOP_CELLS * NC * 4)) / 64 * 64 > 512 ? 512 : (57344 / (COOP_CELLS * NC * 4)) / 64 * 64;
+    constexpr int TILE = tile_coop_partners<Pt, COOP_LANES>();
     static_assert(TILE >= 64, "point type too large for tile_force_coop");
     constexpr int THREADS = COOP_CELLS * COOP_LANES;
     constexpr int LOADS = (TILE + THREADS - 1) / THREADS;  // partners a thread carries per tile
@@ -2694,6 +2703,10 @@ protected:
         graph_key = Step_key{};
     }
     static constexpr int n_floats = ya::N_floats<Pt>::value;
+    // libyalla_hip.so's reductions, grid builds and packs are built per width, for 3 to 16 floats: a wider point would
+    // end in hipErrorInvalidValue from them at the first step
+    static_assert(n_floats >= 3 && n_floats <= 16, "yalla-hip: a point type has 3 to 16 floats (the 16-float limit of "
+                                                   "libyalla_hip.so's per-width kernels)");
     Pt *d_X, *d_dX, *d_X1, *d_dX1;
     float3* d_old_v;
     int* d_n;
@@ -3121,6 +3134,11 @@ public:
     // lanes per cell whatever the functor says (bit-identical sums; force launch at 800 cells
     // 196 -> 32 us with 64 lanes, at 3000 cells 631 -> 135 us with 16).
     int lanes_per_cell = 0;
+    // Whether ya::tile_force_coop exists for Pt with 16 lanes per cell: 64 partners' terms for 16 cells must fit LDS,
+    // which they do up to 10 floats (ya::tile_coop_partners).  Wider points get 64 lanes at every size when the
+    // functors are stateless, and lanes_per_cell = 16 is refused for them at the first step.
+    static constexpr bool has_16_lanes = ya::tile_coop_partners<Pt, 16>() >= 64;
+    static_assert(ya::tile_coop_partners<Pt, 64>() >= 64, "64 lanes per cell fit LDS for every point of up to 16 floats");
 
 protected:
     hipStream_t stream = nullptr;  // every launch of a step goes here (null = the default stream)
@@ -3133,14 +3151,22 @@ protected:
         hipEvent_t start, stop;
         profiler.next(&start, &stop);
         int lanes = lanes_per_cell;
-        if (lanes == 0) lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? (n <= 4096 ? 64 : 16) : 1;
+        if (lanes == 0)
+            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? (n <= 4096 || !has_16_lanes ? 64 : 16) : 1;
         if (lanes >= 64)
             hipExtLaunchKernelGGL((ya::tile_force_coop<Pt, pw_int, pw_friction, 64>), dim3((n + 3) / 4),
                 dim3(256), 0, stream, start, stop, 0, n, d_X, d_old_v, d_dX, has_gen);
-        else if (lanes > 1)
-            hipExtLaunchKernelGGL((ya::tile_force_coop<Pt, pw_int, pw_friction, 16>), dim3((n + 15) / 16),
-                dim3(256), 0, stream, start, stop, 0, n, d_X, d_old_v, d_dX, has_gen);
-        else
+        else if (lanes > 1) {
+            if constexpr (has_16_lanes) {
+                hipExtLaunchKernelGGL((ya::tile_force_coop<Pt, pw_int, pw_friction, 16>), dim3((n + 15) / 16),
+                    dim3(256), 0, stream, start, stop, 0, n, d_X, d_old_v, d_dX, has_gen);
+            } else {
+                fprintf(stderr, "yalla-hip: Tile_computer::lanes_per_cell %d: points of %d floats have no 16-lane "
+                                "kernel (a tile of their pair terms does not fit LDS); 0, 1 or 64\n", lanes,
+                    ya::N_floats<Pt>::value);
+                abort();
+            }
+        } else
             hipExtLaunchKernelGGL((ya::tile_force<Pt, pw_int, pw_friction>),
                 dim3((n + ya::TILE_BLOCK - 1) / ya::TILE_BLOCK), dim3(ya::TILE_BLOCK), 0, stream, start,
                 stop, 0, n, d_X, d_old_v, d_dX, has_gen);

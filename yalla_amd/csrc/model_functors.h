@@ -166,6 +166,28 @@ __device__ inline float field_friction_plain(Po_cell Xi, Po_cell r, float dist, 
     return field_friction_body(Xi, r, dist, i, j);
 }
 
+// --- a force that uses EVERY field of a point of any width (NOT a reference model; tests/test_point_widths*.py).
+// x, y, z are relu_force's.  Every further field k of an interacting pair gets -c_k * r[k] with c_k = (k - 2) / 16,
+// which is exact in binary32: the product rounds once, and a field that a kernel dropped, swapped or staged from the
+// wrong word changes the result (relu_force alone never reads them).  Only + - * and comparisons.
+template<typename Pt>
+__device__ inline Pt field_coupling(Pt Xi, Pt r, float dist, int i, int j)
+{
+    Pt dF = relu_force<Pt>(Xi, r, dist, i, j);
+    constexpr int NF = sizeof(Pt) / sizeof(float);
+    float* out = reinterpret_cast<float*>(&dF);
+    const float* in = reinterpret_cast<const float*>(&r);
+    const bool coupled = i != j && dist < 1;
+#ifndef YA_ORACLE
+#pragma unroll
+#endif
+    for (int k = 3; k < NF; k++) {
+        const float c_k = 0.0625f * float(k - 2);
+        out[k] = coupled ? -c_k * in[k] : 0.f;
+    }
+    return dF;
+}
+
 // --- sorting: examples/sorting.cu:9-28 (differential adhesion between two cell
 // types; the first half of the ids is the strongly adhering type).  n_cells is
 // a compile-time constant in the example and a model parameter here. -----------
@@ -554,4 +576,9 @@ static_assert(ya::stateless_pair<float3, relu_force<float3>, models::ids_frictio
 static_assert(ya::stateless_pair<Po_cell, relu_force<Po_cell>, models::field_friction>() &&
                   !ya::stateless_pair<Po_cell, relu_force<Po_cell>, models::field_friction_plain>(),
     "field_friction is declared stateless, field_friction_plain is not");
+#endif
+
+// The point widths' library (libyalla_models_widths.so, liboracle_models_widths.so): its types and its model table
+#ifdef YA_MODELS_WIDTHS
+#include "widths_models.h"
 #endif

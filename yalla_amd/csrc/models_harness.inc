@@ -90,6 +90,7 @@ struct Cells<Pt, TILE> : public Solution<Pt, Tile_solver> {
 #ifdef YA_ORACLE
         return -2;
 #else
+        if (v == 16 && !this->has_16_lanes) return -1;  // (no such kernel for points of 11 floats and more)
         this->lanes_per_cell = v;
         return 0;
 #endif
@@ -848,7 +849,11 @@ Sim_base* make_sim(int n_max, int gs, float cs)
 #define YA_MODEL(name, Pt, SOLVER, pw_int, pw_friction, Policy) \
     Model { name, &make_sim<Sim<Pt, SOLVER, pw_int, pw_friction, Policy>> }
 
+// -DYA_MODELS_WIDTHS (widths_models.h): another library's table, compiled instead of this one
 static const Model model_table[] = {
+#ifdef YA_MODEL_TABLE
+    YA_MODEL_TABLE
+#else
     // BASELINE configs 1 and 5: springs (examples/springs.cu)
     YA_MODEL("springs_tile", float3, false, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
     YA_MODEL("springs_grid", float3, true, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
@@ -915,6 +920,7 @@ static const Model model_table[] = {
     YA_MODEL("friction_ids_plain_gabriel", float3, GABRIEL, relu_force<float3>, models::ids_friction_plain, No_gen<float3>),
     YA_MODEL("friction_field_gabriel", Po_cell, GABRIEL, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
     YA_MODEL_EXTRA
+#endif
 };
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
