@@ -322,9 +322,8 @@ struct Lds_layout {
 //                       bytes; a 7-float point's leave 18320: room for 16 and 64 lanes, none for 4).  No bit depends on
 //                       the tile length: a cell's terms are added in ascending order into one running sum, tile
 //                       after tile.
-// The rule may fill the LDS to the byte: kernels with a list or a term buffer keep their static LDS at
-// WHOLE_STEP_STATIC_LDS (the one-lane unlinked grid kernel's __syncthreads_or takes 256 bytes on top, which its
-// launches spare).  Whether the step's arrays (and keys) fit at all is whole_step_capacity's question
+// The rule may fill the LDS to the byte, and so may the capacities (a 9-float point's 918 rows and keys leave 8 bytes):
+// every kernel that steps from LDS keeps its static LDS at WHOLE_STEP_STATIC_LDS.  Whether the step's arrays (and keys) fit at all is whole_step_capacity's question
 // (grid_lds_capacity's), not this function's: without a list and with one lane `bytes` is never 0.
 template<typename Pt, bool KEYS, bool LINKED>
 constexpr Lds_layout lds_layout(const int n_max, const int slots, const int lanes)
@@ -1181,16 +1180,28 @@ protected:
         const int n_max = this->n_max, n_replicas = this->n_replicas;
         const int* d_n = this->d_n;
         const float3* d_old_v = this->d_old_v;
+        // (as Tile_computer::has_16_lanes: points of more than 10 floats have no 16-lane kernel, 64 partners' terms for
+        // 16 cells do not fit LDS; the engine's choice is 64 lanes for them, lanes_per_cell = 16 is refused)
+        constexpr bool has_16_lanes = ya::tile_coop_partners<Pt, 16>() >= 64;
         int lanes = lanes_per_cell;
-        if (lanes == 0) lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::lanes_for(n_replicas, n_max) : 1;
+        if (lanes == 0) {
+            lanes = ya::stateless_pair<Pt, pw_int, pw_friction>() ? ya::ens::lanes_for(n_replicas, n_max) : 1;
+            if (lanes == 16 && !has_16_lanes) lanes = 64;
+        }
         if (lanes >= 64) {
             const int blocks = (n_max + 3) / 4;
             ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 64><<<this->grid_of(blocks), 256>>>(
                 n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
         } else if (lanes > 1) {
-            const int blocks = (n_max + 15) / 16;
-            ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 16><<<this->grid_of(blocks), 256>>>(
-                n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
+            if constexpr (has_16_lanes) {
+                const int blocks = (n_max + 15) / 16;
+                ya::ens::tile_force_coop_batched<Pt, pw_int, pw_friction, 16><<<this->grid_of(blocks), 256>>>(
+                    n_max, blocks, d_n, d_in, d_old_v, d_rhs, has_gen);
+            } else {
+                fprintf(stderr, "yalla-hip: Ensemble::lanes_per_cell %d: points of %d floats have no 16-lane kernel (a "
+                                "tile of their pair terms does not fit LDS); 0, 1 or 64\n", lanes, ya::N_floats<Pt>::value);
+                abort();
+            }
         } else {
             const int blocks = (n_max + ya::TILE_BLOCK - 1) / ya::TILE_BLOCK;
             ya::ens::tile_force_batched<Pt, pw_int, pw_friction><<<this->grid_of(blocks), ya::TILE_BLOCK>>>(

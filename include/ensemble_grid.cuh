@@ -646,19 +646,16 @@ __device__ __forceinline__ void grid_lds_steps_of_a_replica(const int n_max, con
         d_point_id_all[base + s] = (int)(unsigned)key;
     }
     for (int c = threadIdx.x; c <= n_cubes; c += UPDATE_BLOCK) d_offs[c] = grid_lds_lower_bound(sh_key, n, c);
-    if constexpr (LINKED || LANES > 1) {
-        // The threads' flags meet in the fold's scratch, which nothing uses after the last step: __syncthreads_or costs
-        // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and a list or a term buffer that lds_layout admits may
-        // leave none.
-        int* sh_flag = lds_fold_scratch<Pt>(grid_step_lds, n_max);
-        if (threadIdx.x == 0) *sh_flag = 0;
-        __syncthreads();
-        if (outside) *sh_flag = 1;  // (every writer writes the same value)
-        __syncthreads();
-        if (threadIdx.x == 0 && *sh_flag) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
-    } else {
-        if (__syncthreads_or(outside) && threadIdx.x == 0) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
-    }
+    // The threads' flags meet in the fold's scratch, which nothing uses after the last step.  (__syncthreads_or would cost
+    // 256 bytes of static LDS beyond WHOLE_STEP_STATIC_LDS, and the rule may leave none: a list or a term buffer that
+    // lds_layout admits, or the rows alone -- a 9-float point's 918 rows and keys leave 8 bytes, an 11-float point's
+    // 750 leave 136 -- so no kernel here uses it.)
+    int* sh_flag = lds_fold_scratch<Pt>(grid_step_lds, n_max);
+    if (threadIdx.x == 0) *sh_flag = 0;
+    __syncthreads();
+    if (outside) *sh_flag = 1;  // (every writer writes the same value)
+    __syncthreads();
+    if (threadIdx.x == 0 && *sh_flag) atomicOr(d_status + replica, YA_STATUS_OUT_OF_GRID);
 }
 template<typename Pt, Pairwise_interaction<Pt> pw_int, Pairwise_friction<Pt> pw_friction, int LANES = 1>
 __global__ __launch_bounds__(UPDATE_BLOCK) void grid_lds_steps(const int n_max, const int* __restrict__ d_n,

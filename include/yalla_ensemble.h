@@ -65,7 +65,9 @@ int ya_ens_set_old_v(ya_ens* ens, const float* in);
  * "whole_step_lanes": Ensemble::whole_step_lanes, the lanes per cell inside such a launch -- 1 (the harness's
  * default) = one thread per cell (ya::ens::whole_steps), 4, 16 or 64 = that many (ya::ens::whole_steps_coop, whatever
  * the functor declares), 0 = the engine's choice; any other value is refused (-3).
- * Any setting gives the same bits. */
+ * Any setting gives the same bits.
+ * "whole_step_lanes_used" is the getter: with value 0 it sets nothing and returns the lanes per cell of the last
+ * whole-step launch (0 before any; 1 where the term buffer of several lanes did not fit the workgroup's LDS). */
 int ya_ens_set_param(ya_ens* ens, const char* name, double value);
 
 #pragma GCC visibility pop

@@ -52,15 +52,16 @@ def same_grid(mine, theirs, n):
 class Lockstep:
     """An ensemble -- ensemble(model, M, n_max, *args, *ens_args) -- and one Solution(<single_model or model> +
     suffix, n_max, *args) per compared replica (`singles`, default all), fed the same rows (`rows`, default
-    seeded_rows with seed 1000 * seed + r), old_v and settings.  grids: the four grid arrays are part of a result."""
+    seeded_rows with seed 1000 * seed + r), old_v and settings.  grids: the four grid arrays are part of a result.
+    lib / single_lib: the libraries of the ensemble and of the Solutions where they are not the classes' own."""
 
     def __init__(self, ensemble, suffix, model, counts, n_max, args=(), ens_args=(), grids=False, seed=0,
-                 singles=None, rows=None, single_model=None):
+                 singles=None, rows=None, single_model=None, lib=None, single_lib=None):
         from yalla_amd.solution import Solution
         self.model, self.n_max, self.grids = model, n_max, grids
-        self.ens = ensemble(model, len(counts), n_max, *args, *ens_args)
+        self.ens = ensemble(model, len(counts), n_max, *args, *ens_args, **({} if lib is None else {"lib": lib}))
         self.which = list(range(len(counts))) if singles is None else list(singles)
-        self.single = {r: Solution((single_model or model) + suffix, n_max, *args) for r in self.which}
+        self.single = {r: Solution((single_model or model) + suffix, n_max, *args, lib=single_lib) for r in self.which}
         self.counts = list(counts)
         for r, n in enumerate(counts):
             X = seeded_rows(self.ens.n_floats, n, 1000 * seed + r) if rows is None else rows[r]
@@ -150,6 +151,12 @@ def capacity(n_floats):
     fold256's scratch, <= 4 partial sums, and the 3 x 256 floats ya::fixed_velocity_from_partials folds in, within a
     workgroup's 160 KiB; at most 1024 rows."""
     return min((LDS - whole_step_bytes(n_floats, 0) - STATIC_LDS) // (4 * 4 * n_floats + 12), 1024)
+
+
+def grid_capacity(n_floats):
+    """ya::ens::grid_lds_capacity<Pt>() restated: the largest n_max <= 1024 whose step arrays and keys (one 64-bit key
+    per row of the power of two from n_max up) fit a workgroup's 160 KiB beside the static fold scratch."""
+    return max(n for n in range(1, 1025) if lds_layout(n_floats, n, keys=True).bytes + STATIC_LDS <= LDS)
 
 
 def launches_of(model, steps, steps_per_launch=256):

@@ -1,7 +1,9 @@
 """The LDS layout of the launches that step a replica from LDS (ya::ens::lds_layout, include/ensemble.cuh) is pure
 arithmetic: host plans and kernels read the same function.  Compiled here into a stand-alone host program (no device, no
 HIP runtime call) that prints the layout for point types of 3, 4, 5, 7 and 8 floats, with and without keys, n_max =
-1 .. 1024, lanes 1, 4, 16, 64 and seven link settings, and held line for line to the Python restatement
+1 .. 1024, lanes 1, 4, 16, 64 and seven link settings -- and, without links, for points of 6, 9, 11 and 16 floats
+(sizeof 24, 36, 44, 64: from 9 floats on fewer than 1024 rows fit, so the sweep crosses each type's capacity and runs
+to 1025) --, and held line for line to the Python restatement
 (ensemble_support.lds_layout, written from the function's comment) and to a table worked out by hand:
 
     step's arrays   X1 .. old_v at 1 .. 4 x n_max x 4 NF, fold at n_max (16 NF + 12), partials 1024 NF further, 16 NF more
@@ -16,7 +18,7 @@ import os
 import subprocess
 
 import pytest
-from ensemble_support import Layout, largest_slots, lds_layout
+from ensemble_support import Layout, capacity, grid_capacity, largest_slots, lds_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,6 +27,11 @@ SRC = r'''
 #include "ensemble.cuh"
 MAKE_PT(Pt7, a, b, c, d);
 MAKE_PT(Pt8, a, b, c, d, e);
+MAKE_PT(Pt6, a, b, c);
+MAKE_PT(Pt9, a, b, c, d, e, f);
+MAKE_PT(Pt11, a, b, c, d, e, f, g, h);
+MAKE_PT(Pt16, a, b, c, d, e, f, g, h, k, l, m, n, o);
+static_assert(sizeof(Pt6) == 24 && sizeof(Pt9) == 36 && sizeof(Pt11) == 44 && sizeof(Pt16) == 64, "no padding");
 using ya::ens::Lds_layout;
 using ya::ens::lds_layout;
 template<typename Pt, bool KEYS, bool LINKED>
@@ -57,6 +64,14 @@ void sweep()
         print<Pt, KEYS, true>(n, 20000);
     }
 }
+// the wide types: without links, across the capacities (the rule itself does not stop there) and one row past 1024
+template<typename Pt>
+void wide()
+{
+    for (int n = 1; n <= 1025; n++) print<Pt, false, false>(n, 0), print<Pt, true, false>(n, 0);
+    printf("capacities of %d floats: %d %d\n", ya::N_floats<Pt>::value, ya::ens::whole_step_capacity<Pt>(),
+        ya::ens::grid_lds_capacity<Pt>());
+}
 int main()
 {
     sweep<float3, false>(), sweep<float3, true>(), sweep<float4, false>(), sweep<float4, true>();
@@ -64,11 +79,17 @@ int main()
     sweep<Pt8, false>(), sweep<Pt8, true>();
     printf("capacities %d %d %d %d\n", ya::ens::whole_step_capacity<float3>(), ya::ens::whole_step_capacity<Pt8>(),
         ya::ens::grid_lds_capacity<float3>(), ya::ens::grid_lds_capacity<Pt8>());
+    wide<Pt6>(), wide<Pt9>(), wide<Pt11>(), wide<Pt16>();
     return 0;
 }
 '''
 
 LANES = (1, 4, 16, 64)
+WIDE = (6, 9, 11, 16)
+# (all-pairs, grid) rows that fit one workgroup, worked out by hand from the formulas in this file's header: e.g. 16
+# floats: (163840 - 3072 - 16640) / 268 = 537.8; with keys 512 rows end at 137216 + 16640 + 4096 = 157952, 513 rows lay
+# out 1024 keys and end at 162320 > 160768
+WIDE_CAPACITIES = {6: (1024, 1024), 9: (970, 918), 11: (794, 750), 16: (537, 512)}
 
 
 def restated():
@@ -86,6 +107,18 @@ def restated():
                         layout = lds_layout(n_floats, n, keys, slots, lanes)
                         lines.append("%d %d %d %d %d : 0 " % (n_floats, keys, n, -1 if slots is None else slots, lanes)
                                      + " ".join(str(x) for x in layout))
+    return lines
+
+
+def restated_wide():
+    lines = []
+    for n_floats in WIDE:
+        for n in range(1, 1026):
+            for keys in (False, True):
+                for lanes in LANES:
+                    layout = lds_layout(n_floats, n, keys, None, lanes)
+                    lines.append("%d %d %d -1 %d : 0 " % (n_floats, keys, n, lanes) + " ".join(str(x) for x in layout))
+        lines.append("capacities of %d floats: %d %d" % (n_floats, capacity(n_floats), grid_capacity(n_floats)))
     return lines
 
 
@@ -109,6 +142,13 @@ TABLE = [
     # small replicas: the tile is n_max rounded up to 4; 4 lanes' budget is 32768 / 1792 = 18 down to 16
     ((3, False, 5, None, 64), Layout(60, 120, 180, 240, 300, 3372, 0, 0, 3424, 8, 3424 + 8 * 112)),
     ((3, False, 300, None, 4), Layout(3600, 7200, 10800, 14400, 18000, 21072, 0, 0, 21120, 16, 21120 + 16 * 1792)),
+    # a 16-float point's 512 rows and 512 keys end at 157952: 2816 bytes left beside the fold scratch, no term buffer
+    ((16, True, 512, None, 1), Layout(32768, 65536, 98304, 131072, 137216, 153600, 153856, 0, 157952, 0, 157952)),
+    ((16, True, 512, None, 64), Layout(32768, 65536, 98304, 131072, 137216, 153600, 153856, 0, 157952, 0, 0)),
+    # ... 16 floats and 4 lanes: 64 cells x 20 floats = 5120 bytes per partner, 16 partners 80 KiB; 200 rows end at 70240
+    # and leave 90528: room 17 down to 16; 250 rows end at 83640, the buffer would start at 83648 and have 77120 < 81920: no room
+    ((16, False, 200, None, 4), Layout(12800, 25600, 38400, 51200, 53600, 69984, 0, 0, 70240, 16, 70240 + 16 * 5120)),
+    ((16, False, 250, None, 4), Layout(16000, 32000, 48000, 64000, 67000, 83384, 0, 0, 83648, 0, 0)),
 ]
 
 
@@ -125,10 +165,24 @@ def printed(tmp_path_factory):
 
 def test_the_layout_is_the_restatement_line_for_line(printed):
     want = restated()
-    assert len(printed) == len(want) + 1
+    wide = restated_wide()
+    assert len(printed) == len(want) + 1 + len(wide)
     for got, line in zip(printed, want):
         assert got == line
-    assert printed[-1] == "capacities 1024 1024 1024 1024"
+    assert printed[len(want)] == "capacities 1024 1024 1024 1024"
+    for got, line in zip(printed[len(want) + 1:], wide):
+        assert got == line
+
+
+def test_the_wide_types_capacities():
+    """The restatement's capacities are the hand-worked ones, the rows fit up to them and not beyond (beside the static
+    fold scratch), and 1024 is the ceiling whatever fits."""
+    from ensemble_support import LDS, STATIC_LDS
+    for n_floats, (tile, grid) in WIDE_CAPACITIES.items():
+        assert (capacity(n_floats), grid_capacity(n_floats)) == (tile, grid), n_floats
+        for keys, rows in ((False, tile), (True, grid)):
+            assert lds_layout(n_floats, rows, keys).bytes + STATIC_LDS <= LDS
+            assert rows == 1024 or lds_layout(n_floats, rows + 1, keys).bytes + STATIC_LDS > LDS
 
 
 @pytest.mark.parametrize("row", range(len(TABLE)))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPRs / SGPRs / LDS / spills of the device kernels in a built library (the gfx950 code object inside the
+"""VGPRs / SGPRs / scratch / LDS / spills of the device kernels in a built library (the gfx950 code object inside the
 fat binary): kernel_resources.py yalla_amd/libyalla_models.so [name filter]"""
 import re
 import struct
@@ -30,4 +30,4 @@ for _ in range(count):
                 short = re.sub(r"15HIP_vector_typeIfLj(\d)EE", r"float\1", name)
                 short = re.sub(r"TnPF[A-Za-z0-9_]*?EXadL_Z", " ", short).replace("_ZN2ya", "")
                 print(f"vgpr {get('vgpr_count'):>3} spill {get('vgpr_spill_count')} sgpr {get('sgpr_count'):>3} "
-                      f"lds {get('group_segment_fixed_size'):>6}  {short[:150]}")
+                      f"scratch {get('private_segment_fixed_size'):>4} lds {get('group_segment_fixed_size'):>6}  {short[:150]}")

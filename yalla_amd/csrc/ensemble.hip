@@ -18,10 +18,16 @@
 
 #include "yalla_ensemble.h"
 #include "ensemble_harness.h"  // No_gen, Push_gen, Tile_replicas(_of), Model, the entry points' bodies
+#ifdef YA_MODELS_WIDTHS
+#include "ensemble_widths_models.h"  // libyalla_ensemble_widths.so: another table (tests only)
+#endif
 
 namespace ens_harness {
 
-using Base = Tile_replicas;  // (the all-pairs form adds nothing to it)
+// What the all-pairs form adds to the shared interface.
+struct Base : public Tile_replicas {
+    virtual int whole_step_lanes_used() = 0;
+};
 
 // models::oscillator tells its two roles apart by `i == 0`, a LOCAL id.  An ensemble's functors get global ids
 // (i = r * n_max + local), so the ensemble's model hands the functor the local ones: the same statements, hence
@@ -60,8 +66,14 @@ struct Sim : public Tile_replicas_of<Ensemble<Pt>, Base> {
         cells.template take_steps<pw_int, pw_friction>(dt, n_steps, gen);  // (push's generic force: never whole steps)
         return cells.whole_step_launches - launches_before;
     }
+    int whole_step_lanes_used() override { return cells.whole_step_lanes_used; }
 };
 
+#ifdef YA_MODELS_WIDTHS
+#define YA_WIDTHS_ROW_HERE(name, Pt, pw_int, pw_friction, Policy) YA_ENSEMBLE_MODEL(name, Pt, pw_int, pw_friction, Policy),
+static const Model<Base* (*)(int, int)> model_table[] = {YA_WIDTHS_ENSEMBLE_MODELS(YA_WIDTHS_ROW_HERE)};
+#undef YA_WIDTHS_ROW_HERE
+#else
 static const Model<Base* (*)(int, int)> model_table[] = {
     YA_ENSEMBLE_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
     YA_ENSEMBLE_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
@@ -76,6 +88,7 @@ static const Model<Base* (*)(int, int)> model_table[] = {
     YA_ENSEMBLE_MODEL("friction_ids_plain", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction_plain>, ens_harness::Local_friction_ids),
     YA_ENSEMBLE_MODEL("friction_field", Po_cell, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
 };
+#endif
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
 }  // namespace ens_harness
@@ -115,6 +128,13 @@ int ya_ens_synchronize(ya_ens*) { return ens_harness::synchronize(); }
 int ya_ens_set_fixed(ya_ens* e, int mode, int local_point) { return ens_harness::set_fixed(*e->p, mode, local_point); }
 int ya_ens_get_old_v(ya_ens* e, float* out) { return ens_harness::get_old_v(*e->p, out); }
 int ya_ens_set_old_v(ya_ens* e, const float* in) { return ens_harness::set_old_v(*e->p, in); }
-int ya_ens_set_param(ya_ens* e, const char* name, double v) { return ens_harness::set_tile_param(*e->p, name, v); }
+// "whole_step_lanes_used" is THE GETTER (as the grid harness's "lds_step_lanes_used": the exported functions are held
+// to an exact list): it sets nothing and returns the lanes per cell of the last whole-step launch, 0 before any, 1
+// where the term buffer of several lanes did not fit; the value handed over must be 0.
+int ya_ens_set_param(ya_ens* e, const char* name, double v)
+{
+    if (name && std::string(name) == "whole_step_lanes_used") return e && v == 0 ? e->p->whole_step_lanes_used() : -3;
+    return ens_harness::set_tile_param(*e->p, name, v);
+}
 
 }  // extern "C"

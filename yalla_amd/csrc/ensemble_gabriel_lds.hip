@@ -21,6 +21,11 @@
 #include "yalla_ensemble_gabriel_lds.h"
 #include "ensemble_harness.h"  // No_gen, Push_gen, Grid_replicas, Grid_replicas_of, Model, the entry points' bodies
 #include "ensemble_gabriel_models.h"
+#ifdef YA_MODELS_WIDTHS
+#include "ensemble_widths_models.h"  // libyalla_ensemble_gabriel_lds_widths.so: another table (tests only)
+#undef YA_GABRIEL_ENSEMBLE_MODELS
+#define YA_GABRIEL_ENSEMBLE_MODELS(X) YA_WIDTHS_ENSEMBLE_MODELS(X)
+#endif
 
 namespace gablds_harness {
 using ens_harness::No_gen;

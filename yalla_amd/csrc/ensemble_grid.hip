@@ -18,6 +18,9 @@
 
 #include "yalla_ensemble_grid.h"
 #include "ensemble_harness.h"  // No_gen, Push_gen, Grid_replicas, Grid_replicas_of, Model, the entry points' bodies
+#ifdef YA_MODELS_WIDTHS
+#include "ensemble_widths_models.h"  // libyalla_ensemble_grid_widths.so: another table (tests only)
+#endif
 
 namespace gens_harness {
 using ens_harness::No_gen;
@@ -63,6 +66,11 @@ struct Sim : public Grid_replicas_of<Ensemble<Pt, Grid_solver>, Base> {
     void set_sum_order(int order) override { cells.sum_order = order ? YA_SUM_BY_PLANE : YA_SUM_REFERENCE; }
 };
 
+#ifdef YA_MODELS_WIDTHS
+#define YA_WIDTHS_ROW_HERE(name, Pt, pw_int, pw_friction, Policy) YA_ENSEMBLE_MODEL(name, Pt, pw_int, pw_friction, Policy),
+static const Model<Base* (*)(int, int, int, float)> model_table[] = {YA_WIDTHS_GRID_ENSEMBLE_MODELS(YA_WIDTHS_ROW_HERE)};
+#undef YA_WIDTHS_ROW_HERE
+#else
 static const Model<Base* (*)(int, int, int, float)> model_table[] = {
     YA_ENSEMBLE_MODEL("springs", float3, models::spring, friction_w_neighbour<float3>, No_gen<float3>),
     YA_ENSEMBLE_MODEL("clipped", float3, models::clipped_spring, friction_w_neighbour<float3>, No_gen<float3>),
@@ -78,6 +86,7 @@ static const Model<Base* (*)(int, int, int, float)> model_table[] = {
     YA_ENSEMBLE_MODEL("friction_ids_plain", float3, relu_force<float3>, ens_harness::friction_by_local_id<models::ids_friction_plain>, ens_harness::Local_friction_ids),
     YA_ENSEMBLE_MODEL("friction_field", Po_cell, relu_force<Po_cell>, models::field_friction, No_gen<Po_cell>),
 };
+#endif
 static const int n_models = sizeof(model_table) / sizeof(model_table[0]);
 
 }  // namespace gens_harness
